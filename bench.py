@@ -2,7 +2,11 @@
 """bench.py -- CFR iterations/sec of the MI355X regret/strategy-update engine + the roofline of its
 dominant kernel (the river regret-update kernel), next to the CPU restatement of the reference.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B] [--clusters C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B] [--clusters C] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else described below -- the roofline of the dominant
+kernel, the per-kernel tables, the CPU baselines, the other configs and the auxiliary legs -- runs with --full only.  --dump-outputs DIR writes
+what the timed steps left in the table (a fixed, seeded sample of it; see dump_outputs) as .npy files, so that two builds can be compared.
 
 Workload (BASELINE.json configs[1]): the 14-action-node river tree of
 options::default_flop() (options.rs:52-81), C = 1000 clusters, A in {2,3}, i32 tables, with the board axis
@@ -63,7 +67,16 @@ def parse():
                     "saturating adds); 0 = the plain +-10^6 fill of rounds 1 and 2")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full result (every leg, every per-kernel table, the descriptive strings) is "
                     "written; stdout carries the compact line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every other measurement: the roofline and per-kernel passes, the CPU baselines, "
+                    "config 3 / 4 / 5, dp_deals and the auxiliary legs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what they left in the table (a seeded sample of every "
+                    "action node's regrets and strategy sums, float64) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.dp_deals:
+        ap.error("--dump-outputs covers the board sweep of the headline, not --dp-deals")
+    return a
 
 
 # ---- self-launch: python bench.py --gpus N starts its own N ranks -----------------------------------------------------------------
@@ -192,6 +205,33 @@ def run_steps(trainer, k):
     for _ in range(k):
         L.check(lib.rs_iterate(h, 0, None))
         L.check(lib.rs_iterate(h, 1, None))
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs: float64 cells written per run, all ranks together (the files stay below 64 MB)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(table, directory, prefix="", max_bytes=DUMP_BYTES):
+    """--dump-outputs: what a caller of the timed path gets back -- the regrets and strategy sums of every action node after the last timed step --
+    on a fixed, seeded sample of lanes (the whole table is 8 GB at the default size).  Writes <prefix>regrets.npy and <prefix>strategy_sum.npy: float64 (exact for i32, f32
+    and f16 cells), node by node in index order, each node's [A][k] cells flattened, k the same lane count for every node (all lanes of a smaller node).
+    The sample depends only on the table's shape, so runs with the same arguments write the same cells."""
+    import numpy as np
+    acts = [table.node_desc(n).n_actions for n in range(table.n_nodes)]
+    per_node = max(1, max_bytes // (2 * 8 * max(1, sum(acts))))
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    reg, ssum = [], []
+    for n, a in enumerate(acts):
+        if a == 0:
+            continue
+        lanes = table.lanes(n)
+        pick = np.sort(rng.choice(lanes, size=min(per_node, lanes), replace=False)).astype(np.uint32)
+        r, s = table.get_infosets(n, pick)
+        reg.append(np.asarray(r, dtype=np.float64).ravel())
+        ssum.append(np.asarray(s, dtype=np.float64).ravel())
+    os.makedirs(directory, exist_ok=True)
+    for name, parts in (("regrets", reg), ("strategy_sum", ssum)):
+        np.save(os.path.join(directory, prefix + name + ".npy"), np.concatenate(parts) if parts else np.zeros(0))
 
 
 def _timed_iterations(run, seconds):
@@ -1040,7 +1080,7 @@ pmc_traffic.info = {}
 
 
 def compact_line(out):
-    """The one line stdout carries: the contract keys, `roofline` and `cpu_baseline` as the task prescribes them, and ONE flat number per auxiliary leg."""
+    """The one line stdout carries: the contract keys and, with --full, `roofline` and `cpu_baseline` as the task prescribes them and ONE flat number per auxiliary leg."""
     def g(d, *path):
         for k in path:
             if not isinstance(d, dict) or k not in d:
@@ -1051,16 +1091,17 @@ def compact_line(out):
     def r3(x):
         return float("%.4g" % x) if isinstance(x, (int, float)) and not isinstance(x, bool) else x
 
-    if "metric" not in out or "roofline" not in out:   # the dp-deals line and the probes are short already
+    if "metric" not in out or "step_ms_hip_events" not in out:   # the dp-deals line and the probes are short already
         return out
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}
     cfg = out.get("config", {})
     line["config"] = {k: cfg[k] for k in ("workload", "n_boards_per_gpu", "n_clusters", "regret_fill", "table_bytes_per_gpu", "launches_per_step", "parallelism",
                                           "process_group_ranks") if k in cfg}
-    rf = out["roofline"]
-    line["roofline"] = {k: r3(rf[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_canned", "traffic_commit", "traffic_stale", "launches", "avg_launch_ms",
-                                               "algo_bytes_per_launch", "copy_GBps", "frac_of_copy_on_this_card") if k in rf}
-    line["roofline"]["kernel"] = "rs_tree_p{0,1}_lanes" if "rs_tree" in rf.get("kernel", "") else "rs::k_update"
+    if "roofline" in out:   # --full
+        rf = out["roofline"]
+        line["roofline"] = {k: r3(rf[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_canned", "traffic_commit", "traffic_stale", "launches",
+                                                   "avg_launch_ms", "algo_bytes_per_launch", "copy_GBps", "frac_of_copy_on_this_card") if k in rf}
+        line["roofline"]["kernel"] = "rs_tree_p{0,1}_lanes" if "rs_tree" in rf.get("kernel", "") else "rs::k_update"
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict) and "value" in cb:
         line["cpu_baseline"] = {"value": r3(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"], "sample": cb["sample"][:160]}
@@ -1229,6 +1270,56 @@ def main():
     elapsed = time.perf_counter() - t0
     step_ms = table.profile_marks()
     elapsed = _max_over_ranks(dist, elapsed)
+    if a.dump_outputs:   # before anything below sweeps the table again
+        dump_outputs(table, a.dump_outputs, "" if n_gpus == 1 else "rank%d_" % rank, DUMP_BYTES // n_gpus)
+
+    out = {
+        "metric": "cfr_iterations_per_sec",
+        "value": a.boards * n_gpus * a.steps / elapsed,
+        "unit": "board-iterations/s",
+        "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if shard is not None else "weak", "vs_baseline": None,
+        "dtype": a.dtype, "data": "synthetic",
+        "step_ms_hip_events": dict(_step_stats(step_ms) or {}, what="per-step durations of the TIMED pass itself, one event per step boundary on the table's stream (rank 0)"),
+        "config": {
+            "workload": ("config2 river-only: 14-action-node tree of options::default_flop(), %d clusters, A in {2,3}, "
+                         "%d boards per GPU" % (a.clusters, a.boards) if not three else
+                         "config3 flop+turn+river: 706-action-node tree, %d clusters per round, boards %s per GPU"
+                         % (a.clusters, "/".join(str(b) for b in boards3))) +
+                        ", %s tables, %s update, opponent %s; 1 step = 1 CFR iteration (both traversers, all lanes)"
+                        % (a.dtype, "cfr.rs:413-464 clamp scale 100" if a.mode == "clamp" else "cfr.rs:612-621 wrap scale 10000",
+                           "full width (cfr.rs:576-589)" if a.opp == "full" else "sampled (mccfr, cfr.rs:467-476)"),
+            "n_boards_per_gpu": a.boards, "n_clusters": a.clusters, "lanes_per_gpu": a.boards * a.clusters,
+            "lane_pitch": int(table.pitch(0)),
+            "table_bytes_per_gpu": table.nbytes, "workspace_bytes_per_gpu": trainer.workspace_bytes,
+            "launches_per_step": trainer.n_launches(0) + trainer.n_launches(1), "hip_graph": bool(a.graph),
+            "fused_subtrees": bool(trainer.fused),
+            "parallelism": ("boards sharded x%d, no collective (nothing replicated in a river-only tree)" % n_gpus) if shard is None else
+                           ("turn / river boards sharded x%d, flop replicated, one RCCL all-gather per traverser sweep" % n_gpus),
+            "process_group_ranks": (dist.get_world_size() if dist is not None else 1),
+            "self_launched": bool(os.environ.get("RS_BENCH_SELF_LAUNCHED")),
+            "regret_fill": ("U{-10^6..10^6}, one cell in %d beyond +-2.1e9 (SURVEY 8(d) saturation note)" % a.saturating) if (a.saturating and a.dtype == "i32")
+                           else "U{-10^6..10^6}",
+        },
+        "lane_updates_per_sec": sum(table.lanes(n) for n in range(table.n_nodes)) * n_gpus * a.steps / elapsed,
+    }
+
+    def release_headline():
+        if comm is not None:
+            from rustsolver_amd import _lib as L4
+            trainer.attach_comm(None)
+            L4.load().rs_comm_destroy(comm)
+        trainer.destroy()
+        table.destroy()
+
+    if not a.full:   # a plain run: the headline and nothing else
+        release_headline()
+        if rank == 0:
+            emit(out)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline leg: the same K steps again with every launch bracketed by HIP events on the table's
     # stream (graph replay off so that single launches can be timed) ---------------------------------------
@@ -1301,33 +1392,7 @@ def main():
                   "update of all 14 river nodes in one launch per traverser)") if dom_name == "tree" else \
                  "rs::k_update (river regret/strategy_sum update, all action counts)"
     traffic, traffic_file = pmc_traffic(a, dom_name)
-    out = {
-        "metric": "cfr_iterations_per_sec",
-        "value": a.boards * n_gpus * a.steps / elapsed,
-        "unit": "board-iterations/s",
-        "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": elapsed / a.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if shard is not None else "weak", "vs_baseline": None,
-        "dtype": a.dtype, "data": "synthetic",
-        "step_ms_hip_events": dict(_step_stats(step_ms) or {}, what="per-step durations of the TIMED pass itself, one event per step boundary on the table's stream (rank 0)"),
-        "config": {
-            "workload": ("config2 river-only: 14-action-node tree of options::default_flop(), %d clusters, A in {2,3}, "
-                         "%d boards per GPU" % (a.clusters, a.boards) if not three else
-                         "config3 flop+turn+river: 706-action-node tree, %d clusters per round, boards %s per GPU"
-                         % (a.clusters, "/".join(str(b) for b in boards3))) +
-                        ", %s tables, %s update, opponent %s; 1 step = 1 CFR iteration (both traversers, all lanes)"
-                        % (a.dtype, "cfr.rs:413-464 clamp scale 100" if a.mode == "clamp" else "cfr.rs:612-621 wrap scale 10000",
-                           "full width (cfr.rs:576-589)" if a.opp == "full" else "sampled (mccfr, cfr.rs:467-476)"),
-            "n_boards_per_gpu": a.boards, "n_clusters": a.clusters, "lanes_per_gpu": a.boards * a.clusters,
-            "lane_pitch": int(table.pitch(0)),
-            "table_bytes_per_gpu": table.nbytes, "workspace_bytes_per_gpu": trainer.workspace_bytes,
-            "launches_per_step": trainer.n_launches(0) + trainer.n_launches(1), "hip_graph": bool(a.graph),
-            "fused_subtrees": bool(trainer.fused),
-            "parallelism": ("boards sharded x%d, no collective (nothing replicated in a river-only tree)" % n_gpus) if shard is None else
-                           ("turn / river boards sharded x%d, flop replicated, one RCCL all-gather per traverser sweep" % n_gpus),
-            "process_group_ranks": (dist.get_world_size() if dist is not None else 1),
-            "self_launched": bool(os.environ.get("RS_BENCH_SELF_LAUNCHED")),
-        },
+    out.update({
         "roofline": {
             "kernel": dom_kernel,
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1345,8 +1410,7 @@ def main():
         "roofline_update_node": upd_node,
         "roofline_discount": disc,
         "kernels": kernels,
-        "lane_updates_per_sec": sum(table.lanes(n) for n in range(table.n_nodes)) * n_gpus * a.steps / elapsed,
-    }
+    })
 
     if rank == 0:
         try:   # the card's own streaming ceiling (cards of one pool differ by more than 10 %): a plain float4 copy, 2 x 2 GiB, on the same stream
@@ -1361,8 +1425,6 @@ def main():
         except Exception as e:
             out["stream_probe"] = {"error": str(e)}
 
-    out["config"]["regret_fill"] = ("U{-10^6..10^6}, one cell in %d beyond +-2.1e9 (SURVEY 8(d) saturation note)" % a.saturating) if (a.saturating and a.dtype == "i32") \
-        else "U{-10^6..10^6}"
     # ---- the same sweep with utilities that force |delta| >= 2^31 on one lane in 100 (RS_LEAF_UTIL rows with +-1e9 outliers): about half of the waves then take the exact
     # i64 branch of the clamp update (the test is made per wave, rs_device.hpp visit_i32) -- the slow path priced once, beside the headline that stays on the fast one
     if rank == 0 and n_gpus == 1 and not three and a.dtype == "i32" and a.mode == "clamp" and not a.no_extra:
@@ -1384,12 +1446,7 @@ def main():
             out["exact_i64_pass"] = {"error": str(e)}
 
     # the headline's table is no longer needed: the legs below want the memory (config 3 / 4 is 135 GB on one GPU)
-    if comm is not None:
-        from rustsolver_amd import _lib as L4
-        trainer.attach_comm(None)
-        L4.load().rs_comm_destroy(comm)
-    trainer.destroy()
-    table.destroy()
+    release_headline()
 
     if a.no_extra or three:
         if rank == 0:

@@ -93,3 +93,75 @@ def test_rank_local_setup_failures_are_reported_not_hung_on():
     with pytest.raises(RuntimeError) as e:
         b._agree(None, boom, "config4 tables and launch plan")
     assert "config4 tables and launch plan" in str(e.value) and "no room" in str(e.value)
+
+
+def test_full_and_dump_outputs_are_opt_in(monkeypatch):
+    import pytest
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir", "--steps", "3"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out_dir" and a.steps == 3
+    for argv in (["--steps", "0"], ["--dump-outputs", "d", "--dp-deals", "1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            b.parse()
+
+
+class _FakeTable:
+    """the part of InfosetTable that dump_outputs reads: the river tree's shape at the bench's default size, cell values derived from (node, action, lane)"""
+    def __init__(self, acts, lanes):
+        self.acts, self.n_lanes, self.n_nodes = acts, lanes, len(acts)
+
+    def node_desc(self, n):
+        return type("Desc", (), {"n_actions": self.acts[n]})
+
+    def lanes(self, n):
+        return self.n_lanes
+
+    def get_infosets(self, n, lanes):
+        import numpy as np
+        assert lanes.dtype == np.uint32 and (lanes < self.n_lanes).all() and len(np.unique(lanes)) == len(lanes)
+        rows = np.arange(self.acts[n], dtype=np.int64)[:, None]
+        cells = (lanes.astype(np.int64)[None, :] * 7 + rows * 1000003 + n * 65537) % (1 << 31) - (1 << 30)
+        return cells.astype(np.int32), (cells // 3).astype(np.int32)
+
+
+def test_dump_outputs_writes_a_fixed_sample_below_64_mb(tmp_path):
+    """--dump-outputs: the same table gives the same files, float64, below 64 MB in all, each cell the one its lane holds"""
+    import numpy as np
+    b = load_bench()
+    acts = [3, 3, 2, 3, 2, 3, 3, 2, 3, 2, 3, 3, 2, 2]
+    table = _FakeTable(acts, 9216 * 1000)
+    b.dump_outputs(table, str(tmp_path / "one"))
+    b.dump_outputs(table, str(tmp_path / "two"))
+    total = 0
+    for name in ("regrets", "strategy_sum"):
+        x, y = np.load(str(tmp_path / "one" / (name + ".npy"))), np.load(str(tmp_path / "two" / (name + ".npy")))
+        assert x.dtype == np.float64 and x.ndim == 1 and np.array_equal(x, y)
+        total += os.path.getsize(str(tmp_path / "one" / (name + ".npy")))
+    assert total <= 64 << 20
+    reg = np.load(str(tmp_path / "one" / "regrets.npy"))
+    k = len(reg) // sum(acts)
+    assert k * sum(acts) == len(reg) and k > 10000
+    # node 0's first row: cells lane * 7 - 2^30 (mod 2^31) at k distinct sorted lanes
+    lanes = (reg[:k].astype(np.int64) + (1 << 30)) // 7
+    assert (np.diff(lanes) > 0).all() and ((lanes * 7 - (1 << 30)) == reg[:k]).all()
+    small = _FakeTable([2, 0, 3], 100)   # nodes smaller than the per-node sample are written whole; nodes without actions are left out
+    b.dump_outputs(small, str(tmp_path / "small"), prefix="rank1_")
+    assert len(np.load(str(tmp_path / "small" / "rank1_regrets.npy"))) == 500
+
+
+def test_a_plain_run_times_the_headline_only():
+    """main(): the outputs are dumped right after the timed steps, and a run without --full returns before the first pass that is not the headline's"""
+    import ast
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    fn = {n.name: n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef)}
+    main_src = ast.get_source_segment(src, fn["main"])
+    timed = main_src.index("for _ in range(a.steps):")
+    plain_exit = main_src.index("if not a.full:")
+    assert timed < main_src.index("dump_outputs(table") < plain_exit
+    assert plain_exit < main_src.index("profile_enable(True)") and plain_exit < main_src.index("cpu_baseline(")
+    assert plain_exit < main_src.index("three_street_sweep_leg(") and plain_exit < main_src.index("deal_batch_leg(")
