@@ -344,7 +344,8 @@ int rs_solver_create(rs_table *table, const rs_tree *tree, const rs_leaf_desc *l
  * (cfr.rs:414); here the sweep is BATCH-SYNCHRONOUS and deterministic: every deal reads the table as it was when the
  * sweep started, its update becomes the i32 delta (new - old) against the value it read, deltas are accumulated with
  * atomic adds (wrapping, order-independent) and applied when the sweep ends.  RS_CHANCE_PASS (one run-out per deal,
- * cfr.rs:306-313).  Float tables (RS_F32, RS_F16: extensions, fuse_subtrees = 1, one GPU, no RS_UPD_PRUNE): a visit's deltas
+ * cfr.rs:306-313).  Float tables (RS_F32, RS_F16: extensions, fuse_subtrees = 1, no RS_UPD_PRUNE, any number of clusters per round; under a communicator the ranks exchange per-deal delta items and sum them in global deal
+ * order inside rs_iterate, rs_iterate_phase refuses them): a visit's deltas
  * (scale*reach)*(u - util) and (scale*reach)*sigma are f32, every cell's deltas are added IN DEAL ORDER from 0.0 and then to
  * the cell -- one rounding to the table's type per cell and sweep, and with RS_UPD_RMPLUS the traverser's regrets that do
  * not end the sweep above 0 end it at 0.  Leaf buffers and d_root_util hold one float per deal, pitch = round_up(n_deals, 64);
@@ -496,8 +497,8 @@ typedef struct rs_deal_trainer_params {
                                       in RS_UPD_PRUNE mode with per-deal flags that stay zero (= unpruned, bit for bit) before it */
     int32_t prefetch;              /* RS_FORM_*: deal the next batch on a second stream while the current one is swept (default: on from 65 536 deals per batch for multi-round games, beyond 262 144 for one-round games) */
     int32_t table_dtype;           /* element type of the table the trainer creates: RS_I32 (0: the reference's), or -- extensions -- RS_F32 / RS_F16: float deal sweeps
-                                      (rs_solver_create_deals: f32 per-deal deltas summed in deal order, one rounding per cell and sweep); these need prune_threshold =
-                                      UINT64_MAX and world <= 1.  (The field was `reserved`, zero, until ABI 5) */
+                                      (rs_solver_create_deals: f32 per-deal deltas summed in deal order, one rounding per cell and sweep, any number of clusters per
+                                      round, world >= 1: bit-equal to one GPU with the union batch); these need prune_threshold = UINT64_MAX.  (The field was `reserved`, zero, until ABI 5) */
 } rs_deal_trainer_params;
 /* MCCFRTrainer::init (cfr.rs:159-184): card_abs[round_idx] for the tree's rounds (borrowed: keep them alive), ranges as above;
  * creates the zero-filled table from the abstractions' sizes (create_infosets, cfr.rs:176) on `device`. */

@@ -40,6 +40,9 @@ int rs_solver_walk_counts(rs_solver *solver, int traverser, uint64_t *out /* [RS
 /* ---- data-parallel deal sweeps: the bytes THIS rank has handed to the collectives since the solver was created (the packed delta cells of every all-reduce + every rank's
  * items of every all-gather) and the sweeps that exchanged anything.  bench.py --gpus N --dp-deals 1 reports bytes per batch from it. */
 int rs_solver_exchange_bytes(const rs_solver *solver, uint64_t *bytes, uint64_t *sweeps);
+/* ---- the member lists of the float deal apply: a stable sort of 0 .. n-1 by key.  d_members[d_start[c] .. d_start[c + 1]) = the indices whose key is c, ascending;
+ * keys >= k count as k - 1.  DEVICE buffers: d_keys [n], d_start [k + 1], d_members [n]; k >= 1, n < 2^32.  Allocates its own scratch; synchronises. */
+int rs_member_lists(rs_table *table, const uint32_t *d_keys, size_t n, uint32_t k, uint32_t *d_start, uint32_t *d_members);
 
 /* ---- checks of the generated (hipRTC) kernels without a GPU ---------------------------------------------------------------------- */
 /* generate + compile (no GPU needed) the tree-specialised kernels of every chance-free subtree, both traversers */

@@ -197,6 +197,27 @@ struct ApplyF32Job {
     uint32_t n_actions, tpitch, n_clusters, pad_;
 };
 hipError_t launch_apply_f32_rows(const ApplyF32Job *d_jobs, int n_jobs, uint32_t max_clusters, uint32_t pitch, int dtype, bool rmplus, hipStream_t stream);
+// data-parallel deal sweeps on float tables (rs_solver.cpp solver_exchange_float): per traverser node (the order of the plan's ApplyF32Jobs) its [2A][pitch] per-deal rows, the
+// round whose cluster ids key it and its first key in the union sort (key = key_off + cluster)
+struct FdpJob {
+    const float *rows;
+    uint32_t n_actions, round, key_off, pad_;
+};
+struct FdpClusters {
+    const uint32_t *c[RS_MAX_ROUNDS];
+};
+// flags[j * n + d] = 1, words[j * n + d] = 2A where deal d has a non-zero delta at job j (0 and 0 elsewhere); flags[m] = words[m] = 0 (m = n_jobs * n)
+hipError_t launch_fdp_flags(const FdpJob *d_jobs, int n_jobs, uint32_t n, uint32_t pitch, uint32_t *flags, uint32_t *words, hipStream_t stream);
+// after the exclusive scans of flags and words: item flags[i] gets key, its payload offset and 2A floats at payload + words[i], in (job, deal) order
+hipError_t launch_fdp_pack(const FdpJob *d_jobs, int n_jobs, uint32_t n, uint32_t pitch, FdpClusters clusters, const uint32_t *flags, const uint32_t *words,
+                           uint32_t *keys, uint32_t *offs, float *payload, hipStream_t stream);
+// every traverser cell: its union items (start / members over the keys of all ranks' items, rank r's item i at r * most_items + i, its floats at
+// payload[r * most_words + offs[r * most_items + i]]) summed from 0.0 in list order, added to the cell, rounded once; k_apply_f32_rows' write-back
+hipError_t launch_fdp_apply(const ApplyF32Job *d_jobs, const FdpJob *d_fjobs, int n_jobs, uint32_t max_clusters, const uint32_t *start, const uint32_t *members,
+                            const uint32_t *offs, const float *payload, uint32_t most_items, size_t most_words, int dtype, bool rmplus, hipStream_t stream);
+// in-place exclusive scan of data[0 .. m) (rs_kmeans.hip); parts: exclusive_scan_parts(m) words
+size_t exclusive_scan_parts(size_t m);
+hipError_t launch_exclusive_scan_u32(uint32_t *data, size_t m, uint32_t *parts, hipStream_t stream);
 // i32 deal sweeps with delta rows: the walk of a round subtree stored, for every traverser node, [2A][pitch] i32 deltas at the list position of each walked deal (zero where
 // the deal did not come by).  One job = the A rows of one node and array + the key row beside them (the traverser's cluster of every position); a workgroup takes one chunk
 // of positions, sums it per cluster in an LDS tile [n_rows][n_clusters] and adds the non-zero cells to the delta table's rows -- integer adds: any order, same bits
@@ -224,10 +245,15 @@ hipError_t launch_pack_cells(void *dregrets, void *dssum, const ApplyJob *d_jobs
 hipError_t launch_row_sums(const RowSumJob *d_jobs, int n_jobs, uint32_t max_entries, uint32_t chunk, uint32_t max_cells, hipStream_t stream);
 constexpr uint32_t kRowSumMaxCells = 16384;   // ints of one job's LDS tile (64 KiB: two workgroups per CU)
 constexpr uint32_t kRowSumChunk = 262144;     // list positions per workgroup
-// stable counting sort of 0 .. n-1 by key (rs_kmeans.hip): members[start[c] .. start[c + 1]) = the indices with key c, ascending; scratch: tile_hist [ceil(n / 512)][k], total [k]
-hipError_t launch_member_lists(const uint32_t *keys, size_t n, int k, uint32_t *tile_hist, uint32_t *total, uint32_t *start /* [k + 1] */, uint32_t *members /* [n] */,
-                               hipStream_t stream);
-size_t member_list_tiles(size_t n);
+// stable sort of 0 .. n-1 by key (rs_kmeans.hip): members[start[c] .. start[c + 1]) = the indices with key c, ascending; keys >= k count as k - 1.  Up to
+// kMemberListsLdsMax clusters and kMemberListsCountingMaxHist tile-histogram entries a counting sort with one LDS counter per cluster (scratch: [ceil(n / 512) + 1][k]
+// words), otherwise a radix sort (scratch: about 3.2 n words)
+constexpr uint32_t kMemberListsLdsMax = 16384;
+constexpr size_t kMemberListsCountingMaxHist = size_t(1) << 22;   // the counting sort only while ceil(n / 512) x k <= this
+size_t member_lists_scratch_words(size_t n, uint32_t k);
+size_t member_lists_scratch_words_upto(size_t n, uint32_t k);   // for any n' <= n
+hipError_t launch_member_lists(const uint32_t *keys, size_t n, uint32_t k, uint32_t *scratch /* [member_lists_scratch_words] */, uint32_t *start /* [k + 1] */,
+                               uint32_t *members /* [n] */, hipStream_t stream);
 hipError_t launch_showdown_sign(const uint8_t *cards, float *sign, uint32_t n, uint32_t pitch, hipStream_t stream);
 hipError_t launch_next_seed(uint64_t *d_state /* {base, call_index, seed} */, hipStream_t stream);
 hipError_t launch_probe_copy(const void *in, void *out, size_t bytes, unsigned blocks, hipStream_t stream);   // rs_stream_probe

@@ -1119,6 +1119,82 @@ hipError_t launch_apply_f32_rows(const ApplyF32Job *d_jobs, int n_jobs, uint32_t
     else hipLaunchKernelGGL((k_apply_f32_rows<float>), grid, block, 0, stream, d_jobs, pitch, rmplus ? 1 : 0);
     return hipGetLastError();
 }
+// data-parallel float deal sweeps: the deals of each traverser node whose [2A] delta vector has a non-zero value (NaN and inf included) become items; the others add +-0 to a
+// running sum that starts at +0.0, which changes nothing, so leaving them out keeps the bits
+__global__ __launch_bounds__(kBlock) void k_fdp_flags(const FdpJob *__restrict__ jobs, int n_jobs, uint32_t n, uint32_t pitch, uint32_t *__restrict__ flags,
+                                                      uint32_t *__restrict__ words) {
+    const size_t m = (size_t)n_jobs * n;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i <= m; i += (size_t)gridDim.x * kBlock) {
+        if (i == m) {
+            flags[m] = words[m] = 0;
+            continue;
+        }
+        const size_t j = i / n, d = i - j * n;   // consecutive threads: consecutive deals of one job
+        const FdpJob job = jobs[j];
+        const uint32_t rows = 2 * job.n_actions;
+        bool nz = false;
+        for (uint32_t x = 0; x < rows; ++x) nz = nz || job.rows[(size_t)x * pitch + d] != 0.0f;
+        flags[i] = nz ? 1u : 0u;
+        words[i] = nz ? rows : 0u;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_fdp_pack(const FdpJob *__restrict__ jobs, int n_jobs, uint32_t n, uint32_t pitch, FdpClusters clusters,
+                                                     const uint32_t *__restrict__ flags, const uint32_t *__restrict__ words, uint32_t *__restrict__ keys,
+                                                     uint32_t *__restrict__ offs, float *__restrict__ payload) {
+    const size_t m = (size_t)n_jobs * n;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (size_t)gridDim.x * kBlock) {
+        const uint32_t item = flags[i];
+        if (flags[i + 1] == item) continue;   // (exclusive scans: the flag is the difference)
+        const size_t j = i / n, d = i - j * n;
+        const FdpJob job = jobs[j];
+        const uint32_t at = words[i];
+        keys[item] = job.key_off + clusters.c[job.round][d];
+        offs[item] = at;
+        for (uint32_t x = 0; x < 2 * job.n_actions; ++x) payload[(size_t)at + x] = job.rows[(size_t)x * pitch + d];
+    }
+}
+template <typename E>
+__global__ __launch_bounds__(kBlock) void k_fdp_apply(const ApplyF32Job *__restrict__ jobs, const FdpJob *__restrict__ fjobs, const uint32_t *__restrict__ start,
+                                                      const uint32_t *__restrict__ members, const uint32_t *__restrict__ offs, const float *__restrict__ payload,
+                                                      uint32_t most_items, size_t most_words, int rmplus) {
+    const ApplyF32Job job = jobs[blockIdx.y];
+    const uint32_t key0 = fjobs[blockIdx.y].key_off;
+    const uint32_t rows = 2 * job.n_actions, n = job.n_clusters * rows;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const uint32_t x = i / job.n_clusters, c = i - x * job.n_clusters;
+        float acc = 0.0f;
+        for (uint32_t q = start[key0 + c]; q < start[key0 + c + 1]; ++q) {   // rank-major, then deal order inside a rank: the order of one GPU's batch
+            const uint32_t u = members[q], r = u / most_items;
+            acc += payload[(size_t)r * most_words + offs[u] + x];
+        }
+        const bool regret = x < job.n_actions;
+        E *cell = (regret ? (E *)job.reg + (size_t)x * job.tpitch : (E *)job.ssm + (size_t)(x - job.n_actions) * job.tpitch) + c;
+        float v = (float)*cell + acc;
+        if (rmplus && regret && !(v > 0.0f)) v = 0.0f;
+        *cell = (E)v;
+    }
+}
+static dim3 fdp_grid(size_t m) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((m + kBlock) / kBlock, 65536))); }
+hipError_t launch_fdp_flags(const FdpJob *d_jobs, int n_jobs, uint32_t n, uint32_t pitch, uint32_t *flags, uint32_t *words, hipStream_t stream) {
+    hipLaunchKernelGGL(k_fdp_flags, fdp_grid((size_t)n_jobs * n), dim3(kBlock), 0, stream, d_jobs, n_jobs, n, pitch, flags, words);
+    return hipGetLastError();
+}
+hipError_t launch_fdp_pack(const FdpJob *d_jobs, int n_jobs, uint32_t n, uint32_t pitch, FdpClusters clusters, const uint32_t *flags, const uint32_t *words, uint32_t *keys,
+                           uint32_t *offs, float *payload, hipStream_t stream) {
+    if (n_jobs <= 0 || n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fdp_pack, fdp_grid((size_t)n_jobs * n), dim3(kBlock), 0, stream, d_jobs, n_jobs, n, pitch, clusters, flags, words, keys, offs, payload);
+    return hipGetLastError();
+}
+hipError_t launch_fdp_apply(const ApplyF32Job *d_jobs, const FdpJob *d_fjobs, int n_jobs, uint32_t max_clusters, const uint32_t *start, const uint32_t *members,
+                            const uint32_t *offs, const float *payload, uint32_t most_items, size_t most_words, int dtype, bool rmplus, hipStream_t stream) {
+    if (n_jobs <= 0) return hipSuccess;
+    dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((size_t(max_clusters) * 2 * RS_MAX_ACTIONS + kBlock - 1) / kBlock, 1024)), (unsigned)n_jobs), block(kBlock);
+    if (dtype == RS_F16)
+        hipLaunchKernelGGL((k_fdp_apply<_Float16>), grid, block, 0, stream, d_jobs, d_fjobs, start, members, offs, payload, std::max(most_items, 1u), most_words, rmplus ? 1 : 0);
+    else
+        hipLaunchKernelGGL((k_fdp_apply<float>), grid, block, 0, stream, d_jobs, d_fjobs, start, members, offs, payload, std::max(most_items, 1u), most_words, rmplus ? 1 : 0);
+    return hipGetLastError();
+}
 // i32 deal sweeps with delta rows (rs_kernel_forms.delta_rows): workgroup (x, y) sums positions [y * chunk, (y + 1) * chunk) of job x's rows per cluster (the JOB is the fast
 // grid axis: workgroups go to the 8 XCDs round-robin in launch order, most lists end after a few chunks, and with 16 chunks on the fast axis the working ones all landed on
 // three XCDs -- 3.0 against 0.97 ms per launch).  Streaming: every

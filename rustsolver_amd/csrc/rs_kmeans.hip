@@ -307,7 +307,7 @@ __global__ __launch_bounds__(kKmBlock) void k_kmeans_scatter(const unsigned *__r
 }
 typedef float km_f32x4 __attribute__((ext_vector_type(4)));
 size_t member_list_tiles(size_t n) { return (n + kKmTile - 1) / kKmTile; }
-hipError_t launch_member_lists(const uint32_t *keys, size_t n, int k, uint32_t *tile_hist, uint32_t *total, uint32_t *start, uint32_t *members, hipStream_t stream) {
+hipError_t launch_member_lists_lds(const uint32_t *keys, size_t n, int k, uint32_t *tile_hist, uint32_t *total, uint32_t *start, uint32_t *members, hipStream_t stream) {
     if (size_t(k) * 4 > 64 * 1024) return hipErrorInvalidValue;
     const size_t n_tiles = member_list_tiles(n);
     hipLaunchKernelGGL(k_kmeans_tile_hist, dim3((unsigned)n_tiles), dim3(kKmBlock), size_t(k) * 4, stream, (const unsigned *)keys, n, k, (unsigned *)tile_hist);
@@ -316,6 +316,217 @@ hipError_t launch_member_lists(const uint32_t *keys, size_t n, int k, uint32_t *
     hipLaunchKernelGGL(k_kmeans_scatter, dim3((unsigned)n_tiles), dim3(kKmBlock), 0, stream, (const unsigned *)keys, n, k, (const unsigned *)tile_hist, (const unsigned *)start,
                        (unsigned *)members);
     return hipGetLastError();
+}
+
+// ---- member lists for any cluster count: a least-significant-digit radix sort of (key, index) pairs, at most 8 key bits per pass (ceil(log2 k) bits in all, split evenly).
+// The counting sort above keeps one LDS counter per cluster and a [tile][k] histogram: 16 384 clusters at most, and n / 512 x k words of scratch (1.8 GB at 4 M deals
+// and 55 K clusters).  Here a pass keeps 256 counters per tile of 2048 data, so the scratch is 3 n + n / 8 words whatever k is.  Every pass is stable: a tile's data are
+// taken in chunks of one per thread, in data order; inside a wave the rank among the same digit comes from ballots (one per digit bit: the lanes that agree on every
+// bit), across the block's four waves from the per-wave counts in LDS, across chunks from a running counter per digit.  A stable sort has one result, so these lists
+// are the counting sort's, bit for bit.
+constexpr int kMlBlock = 256, kMlItems = 8, kMlTile = kMlBlock * kMlItems;   // data per tile: one per thread and chunk
+constexpr int kMlMaxBits = 8, kMlMaxBins = 1 << kMlMaxBits;
+constexpr int kMlScanItems = 16, kMlScanChunk = kMlBlock * kMlScanItems;    // entries of the tile histograms per scanning workgroup
+constexpr int kMlPartsBlock = 1024;
+size_t ml_tiles(size_t n) { return (n + kMlTile - 1) / kMlTile; }
+int ml_bits(uint32_t k) {   // bits of k - 1 (at least 1)
+    int b = 1;
+    while (b < 32 && (uint64_t(k - 1) >> b)) ++b;
+    return b;
+}
+// the lanes of this wave whose digit equals this lane's, among `valid`
+__device__ inline unsigned long long ml_peers(unsigned d, int bits, unsigned long long valid) {
+    unsigned long long m = valid;
+    for (int b = 0; b < bits; ++b) {
+        const unsigned long long x = __ballot((d >> b) & 1u);
+        m &= ((d >> b) & 1u) ? x : ~x;
+    }
+    return m;
+}
+// hist[d * n_tiles + t] = data of tile t with digit d (digit-major: ONE exclusive scan of the whole array gives every (digit, tile) its first output position)
+__global__ __launch_bounds__(kMlBlock) void k_ml_hist(const uint32_t *__restrict__ keys, size_t n, uint32_t kmax, uint32_t shift, int bits, uint32_t n_tiles,
+                                                      uint32_t *__restrict__ hist) {
+    __shared__ uint32_t cnt[kMlMaxBins];
+    const uint32_t R = 1u << bits, lane = threadIdx.x & 63;
+    for (uint32_t d = threadIdx.x; d < R; d += kMlBlock) cnt[d] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kMlTile;
+    for (int j = 0; j < kMlItems; ++j) {
+        const size_t i = base + (size_t)j * kMlBlock + threadIdx.x;
+        const bool ok = i < n;
+        const uint32_t d = ok ? (min(keys[i], kmax) >> shift) & (R - 1) : 0u;
+        const unsigned long long peers = ml_peers(d, bits, __ballot(ok));
+        if (ok && !(peers & ((1ull << lane) - 1))) atomicAdd(&cnt[d], (uint32_t)__popcll(peers));   // one add per digit and wave
+    }
+    __syncthreads();
+    for (uint32_t d = threadIdx.x; d < R; d += kMlBlock) hist[(size_t)d * n_tiles + blockIdx.x] = cnt[d];
+}
+// exclusive scan of hist[0 .. m): chunk sums, a scan of the sums (one workgroup), the chunks scanned from their sums
+__global__ __launch_bounds__(kMlBlock) void k_ml_chunk_sums(const uint32_t *__restrict__ hist, size_t m, uint32_t *__restrict__ parts) {
+    __shared__ uint32_t red[kMlBlock / 64];
+    const size_t base = (size_t)blockIdx.x * kMlScanChunk;
+    uint32_t sum = 0;
+    for (int q = 0; q < kMlScanItems; ++q) {
+        const size_t i = base + (size_t)q * kMlBlock + threadIdx.x;
+        if (i < m) sum += hist[i];
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) parts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(kMlPartsBlock) void k_ml_parts_scan(uint32_t *__restrict__ parts, uint32_t n_parts) {
+    __shared__ uint32_t part[kMlPartsBlock];
+    const uint32_t per = (n_parts + kMlPartsBlock - 1) / kMlPartsBlock, c0 = min(n_parts, threadIdx.x * per), c1 = min(n_parts, c0 + per);
+    uint32_t sum = 0;
+    for (uint32_t c = c0; c < c1; ++c) sum += parts[c];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < kMlPartsBlock; d <<= 1) {
+        const uint32_t x = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += x;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - sum;
+    for (uint32_t c = c0; c < c1; ++c) {
+        const uint32_t x = parts[c];
+        parts[c] = run;
+        run += x;
+    }
+}
+__global__ __launch_bounds__(kMlBlock) void k_ml_chunk_scan(uint32_t *__restrict__ hist, size_t m, const uint32_t *__restrict__ parts) {
+    __shared__ uint32_t part[kMlBlock];
+    const size_t base = (size_t)blockIdx.x * kMlScanChunk + (size_t)threadIdx.x * kMlScanItems;   // thread t: kMlScanItems consecutive entries
+    uint32_t x[kMlScanItems], sum = 0;
+#pragma unroll
+    for (int q = 0; q < kMlScanItems; ++q) {
+        x[q] = base + q < m ? hist[base + q] : 0u;
+        sum += x[q];
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < kMlBlock; d <<= 1) {
+        const uint32_t y = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += y;
+        __syncthreads();
+    }
+    uint32_t run = parts[blockIdx.x] + part[threadIdx.x] - sum;
+#pragma unroll
+    for (int q = 0; q < kMlScanItems; ++q) {
+        if (base + q < m) hist[base + q] = run;
+        run += x[q];
+    }
+}
+// the stable scatter of one pass: datum i of tile t goes to off[d * n_tiles + t] + (data of digit d before it in the tile); val_in NULL: the values are the indices
+__global__ __launch_bounds__(kMlBlock) void k_ml_scatter(const uint32_t *__restrict__ key_in, const uint32_t *__restrict__ val_in, size_t n, uint32_t kmax, uint32_t shift,
+                                                         int bits, uint32_t n_tiles, const uint32_t *__restrict__ off, uint32_t *__restrict__ key_out,
+                                                         uint32_t *__restrict__ val_out) {
+    __shared__ uint32_t run[kMlMaxBins];                    // next output position of each digit
+    __shared__ uint32_t wcnt[kMlBlock / 64][kMlMaxBins];    // this chunk's data of each digit, per wave
+    const uint32_t R = 1u << bits, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (uint32_t d = threadIdx.x; d < R; d += kMlBlock) {
+        run[d] = off[(size_t)d * n_tiles + blockIdx.x];
+        for (int v = 0; v < kMlBlock / 64; ++v) wcnt[v][d] = 0;
+    }
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kMlTile;
+    for (int j = 0; j < kMlItems; ++j) {
+        const size_t i = base + (size_t)j * kMlBlock + threadIdx.x;
+        const bool ok = i < n;
+        const uint32_t key = ok ? min(key_in[i], kmax) : 0u, val = ok ? (val_in ? val_in[i] : (uint32_t)i) : 0u;
+        const uint32_t d = (key >> shift) & (R - 1);
+        const unsigned long long peers = ml_peers(d, bits, __ballot(ok));
+        const uint32_t below = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
+        if (ok && !below) wcnt[w][d] = (uint32_t)__popcll(peers);
+        __syncthreads();
+        if (ok) {
+            uint32_t pos = run[d] + below;
+            for (uint32_t v = 0; v < w; ++v) pos += wcnt[v][d];
+            key_out[pos] = key;
+            val_out[pos] = val;
+        }
+        __syncthreads();
+        for (uint32_t d2 = threadIdx.x; d2 < R; d2 += kMlBlock) {
+            uint32_t add = 0;
+            for (int v = 0; v < kMlBlock / 64; ++v) {
+                add += wcnt[v][d2];
+                wcnt[v][d2] = 0;
+            }
+            run[d2] += add;
+        }
+        __syncthreads();
+    }
+}
+// start[c] = the first position whose sorted key is >= c (c = 0 .. k; start[k] = n since every key is clamped below k)
+__global__ __launch_bounds__(kMlBlock) void k_ml_starts(const uint32_t *__restrict__ sorted, size_t n, uint32_t k, uint32_t *__restrict__ start) {
+    for (size_t c = (size_t)blockIdx.x * kMlBlock + threadIdx.x; c <= k; c += (size_t)gridDim.x * kMlBlock) {
+        size_t lo = 0, hi = n;
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (sorted[mid] < c) lo = mid + 1;
+            else hi = mid;
+        }
+        start[c] = (uint32_t)lo;
+    }
+}
+size_t member_lists_radix_words(size_t n) {   // keys twice, values once (the other buffer is `members`), the tile histograms, the chunk sums
+    const size_t m = size_t(kMlMaxBins) * ml_tiles(n);
+    return 3 * n + m + (m + kMlScanChunk - 1) / kMlScanChunk + 1;
+}
+hipError_t launch_member_lists_radix(const uint32_t *keys, size_t n, uint32_t k, uint32_t *scratch, uint32_t *start, uint32_t *members, hipStream_t stream) {
+    if (k == 0 || n > 0xffffffffull) return hipErrorInvalidValue;
+    if (n == 0) return hipMemsetAsync(start, 0, (size_t(k) + 1) * 4, stream);
+    const int total_bits = ml_bits(k), passes = (total_bits + kMlMaxBits - 1) / kMlMaxBits;
+    const size_t n_tiles = ml_tiles(n);
+    uint32_t *key_buf[2] = {scratch, scratch + n}, *val_tmp = scratch + 2 * n, *hist = scratch + 3 * n;
+    uint32_t *parts = hist + size_t(kMlMaxBins) * n_tiles;
+    const uint32_t *key_in = keys, *val_in = nullptr;
+    uint32_t shift = 0;
+    for (int p = 0; p < passes; ++p) {
+        const int bits = (total_bits - int(shift) + (passes - p) - 1) / (passes - p);   // the bits left, spread over the passes left
+        const size_t m = (size_t(1) << bits) * n_tiles, n_parts = (m + kMlScanChunk - 1) / kMlScanChunk;
+        uint32_t *key_out = key_buf[p & 1], *val_out = ((passes - 1 - p) & 1) ? val_tmp : members;   // the last pass writes `members`
+        hipLaunchKernelGGL(k_ml_hist, dim3((unsigned)n_tiles), dim3(kMlBlock), 0, stream, key_in, n, k - 1, shift, bits, (uint32_t)n_tiles, hist);
+        hipLaunchKernelGGL(k_ml_chunk_sums, dim3((unsigned)n_parts), dim3(kMlBlock), 0, stream, (const uint32_t *)hist, m, parts);
+        hipLaunchKernelGGL(k_ml_parts_scan, dim3(1), dim3(kMlPartsBlock), 0, stream, parts, (uint32_t)n_parts);
+        hipLaunchKernelGGL(k_ml_chunk_scan, dim3((unsigned)n_parts), dim3(kMlBlock), 0, stream, hist, m, (const uint32_t *)parts);
+        hipLaunchKernelGGL(k_ml_scatter, dim3((unsigned)n_tiles), dim3(kMlBlock), 0, stream, key_in, val_in, n, k - 1, shift, bits, (uint32_t)n_tiles, (const uint32_t *)hist,
+                           key_out, val_out);
+        key_in = key_out;
+        val_in = val_out;
+        shift += uint32_t(bits);
+    }
+    hipLaunchKernelGGL(k_ml_starts, dim3((unsigned)std::min<size_t>((size_t(k) + kMlBlock) / kMlBlock, 8192)), dim3(kMlBlock), 0, stream, key_in, n, k, start);
+    return hipGetLastError();
+}
+size_t exclusive_scan_parts(size_t m) { return (m + kMlScanChunk - 1) / kMlScanChunk + 1; }
+hipError_t launch_exclusive_scan_u32(uint32_t *data, size_t m, uint32_t *parts, hipStream_t stream) {
+    if (m == 0) return hipSuccess;
+    const size_t n_parts = (m + kMlScanChunk - 1) / kMlScanChunk;
+    if (n_parts > 0xffffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ml_chunk_sums, dim3((unsigned)n_parts), dim3(kMlBlock), 0, stream, (const uint32_t *)data, m, parts);
+    hipLaunchKernelGGL(k_ml_parts_scan, dim3(1), dim3(kMlPartsBlock), 0, stream, parts, (uint32_t)n_parts);
+    hipLaunchKernelGGL(k_ml_chunk_scan, dim3((unsigned)n_parts), dim3(kMlBlock), 0, stream, data, m, (const uint32_t *)parts);
+    return hipGetLastError();
+}
+// the counting sort while its [tile][k] histogram is small: it scans that histogram once per cluster along the tiles, 0.71 ms at 4 M deals and 16 384 clusters against
+// 0.24 ms for the whole radix sort; at 64 K deals (2 M histogram entries) it is the faster one, 66 against 74 us (profiles/r06_float_deals.md)
+bool member_lists_counting(size_t n, uint32_t k) { return k <= kMemberListsLdsMax && member_list_tiles(n) * size_t(k) <= kMemberListsCountingMaxHist; }
+size_t member_lists_scratch_words(size_t n, uint32_t k) {
+    return member_lists_counting(n, k) ? (member_list_tiles(n) + 1) * size_t(k) : member_lists_radix_words(n);
+}
+size_t member_lists_scratch_words_upto(size_t n, uint32_t k) {   // enough for any n' <= n, whichever path it takes
+    size_t w = member_lists_radix_words(n);
+    if (k <= kMemberListsLdsMax) w = std::max(w, std::min((member_list_tiles(n) + 1) * size_t(k), kMemberListsCountingMaxHist + k));
+    return w;
+}
+hipError_t launch_member_lists(const uint32_t *keys, size_t n, uint32_t k, uint32_t *scratch, uint32_t *start, uint32_t *members, hipStream_t stream) {
+    if (k == 0) return hipErrorInvalidValue;
+    if (!member_lists_counting(n, k)) return launch_member_lists_radix(keys, n, k, scratch, start, members, stream);
+    if (n == 0) return hipMemsetAsync(start, 0, (size_t(k) + 1) * 4, stream);
+    return launch_member_lists_lds(keys, n, int(k), scratch, scratch + member_list_tiles(n) * size_t(k), start, members, stream);
 }
 
 // The ordered sums are a chain of dependent f32 additions per (cluster, bin); what need NOT be ordered are the loads.  So the members' histograms are first copied,
@@ -570,6 +781,20 @@ int rs_update_min_dists(rs_table *t, int dist, float *d_min_dists, const float *
         e = hipGetLastError();
     }
     RS_HIP(e, "k_update_min_dists");
+    return RS_OK;
+}
+
+// the member lists of the float deal apply (launch_member_lists), on caller-owned DEVICE buffers; allocates and frees its own scratch, synchronises
+int rs_member_lists(rs_table *t, const uint32_t *d_keys, size_t n, uint32_t k, uint32_t *d_start, uint32_t *d_members) {
+    if (!t || !d_start || (n && (!d_keys || !d_members))) return fail(RS_ERR_INVALID, "rs_member_lists: NULL argument");
+    if (k == 0 || n > 0xffffffffull) return fail(RS_ERR_INVALID, "rs_member_lists: k must be at least 1 and n below 2^32");
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    uint32_t *d_scratch = nullptr;
+    RS_HIP(hipMalloc((void **)&d_scratch, std::max<size_t>(member_lists_scratch_words(n, k), 1) * 4), "rs_member_lists: scratch");
+    hipError_t e = launch_member_lists(d_keys, n, k, d_scratch, d_start, d_members, t->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+    (void)hipFree(d_scratch);
+    RS_HIP(e, "rs_member_lists");
     return RS_OK;
 }
 

@@ -220,6 +220,21 @@ struct rs_solver {
     uint32_t item_cap = 0, items_world = 0;   // items_world: ranks d_items_all and d_item_count were sized for
     uint64_t dp_bytes_total = 0, dp_sweeps = 0;
     uint64_t dp_bytes_last = 0;         // bytes this rank handed to the collectives in its last sweep (all-reduce buffer + every rank's items)
+    // data-parallel deal sweeps on FLOAT tables (solver_exchange_float): per-deal delta vectors travel as items, every rank sums the union in global deal order
+    rs::FdpJob *d_fdp_jobs[2] = {nullptr, nullptr};   // per traverser, in the order of its plan's ApplyF32Jobs
+    uint32_t fdp_keys[2] = {0, 0};                // per traverser: sum of its nodes' clusters (the union sort's keys are below it)
+    uint32_t *d_fdp_scan = nullptr;               // [2][fdp_m + 1]: item flags, payload words, scanned in place
+    uint32_t *d_fdp_parts = nullptr;              // scan partial sums
+    uint32_t *d_fdp_count = nullptr;              // [2 + 2 * world]: this rank's (items, words), then every rank's
+    uint32_t *d_fdp_start = nullptr;              // [max fdp_keys + 2]
+    size_t fdp_m = 0;                             // max over traversers of n_jobs * n_deals
+    uint32_t fdp_world = 0;
+    // grown on demand (rank-invariant: from the gathered counts); fdp_cap_items == 0 after a failed grow, and every later sweep fails
+    uint32_t *d_fdp_key = nullptr, *d_fdp_off = nullptr, *d_fdp_key_all = nullptr, *d_fdp_off_all = nullptr, *d_fdp_members = nullptr, *d_fdp_scratch = nullptr;
+    float *d_fdp_pay = nullptr, *d_fdp_pay_all = nullptr;
+    uint32_t fdp_cap_items = 0;
+    size_t fdp_cap_words = 0, fdp_bytes = 0;
+    bool fdp_broken = false;
     int (*before_sweep)(void *ctx, int traverser) = nullptr;   // ... and is asked in front of every sweep whether the records are the live batch's (rs_iterate, rs_iterate_phase 0)
     void *before_sweep_ctx = nullptr;
     // delta rows (rs_kernel_forms.delta_rows): one buffer for both traversers' sweeps (they never overlap), [2A][batch pitch] i32 per traverser node of an eligible round

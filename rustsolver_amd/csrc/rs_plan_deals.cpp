@@ -467,18 +467,19 @@ int PlanBuilder::emit_apply() {
             for (size_t i = 0; i < t->nodes.size(); ++i)
                 if (t->nodes[i].round_idx == r && t->nodes[i].player == p && t->nodes[i].n_actions > 0) k = std::max(k, t->nodes[i].n_clusters);
             if (!k) continue;
-            if (size_t(k) * 4 > 64 * 1024) return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: f32 tables take at most 16 384 clusters per node (the member lists' LDS histogram)");
             hipError_t e = hipMalloc((void **)&plan.d_member_start[r], (size_t(k) + 1) * 4);
             if (e == hipSuccess) e = hipMalloc((void **)&plan.d_members[r], std::max<size_t>(n, 1) * 4);
             if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: member lists");
             plan.aux_bytes += (size_t(k) + 1) * 4 + size_t(n) * 4;
-            scratch = std::max(scratch, (member_list_tiles(n) + 1) * size_t(k));
+            scratch = std::max(scratch, member_lists_scratch_words(n, k));
         }
         if (hipMalloc((void **)&plan.d_member_scratch, std::max<size_t>(scratch, 1) * 4) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create_deals: member-list scratch");
         plan.aux_bytes += scratch * 4;
         for (size_t i = 0; i < t->nodes.size(); ++i) {
             const rs_node_desc &d = t->nodes[i];
             if (d.n_actions == 0 || d.player != p) continue;
+            if (uint64_t(d.n_clusters) * 2 * d.n_actions >= (uint64_t(1) << 32))   // k_apply_f32_rows counts a node's (row, cluster) cells in 32 bits
+                return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: a float-table node with 2^32 or more (row, cluster) cells");
             ApplyF32Job j{};
             j.reg = t->regrets_ptr(int(i));
             j.ssm = t->ssum_ptr(int(i));

@@ -20,6 +20,7 @@ int run_launch(rs_solver *s, const Plan &plan, const Launch &L, hipStream_t tree
     if (!tree_stream) tree_stream = t->stream;
     static const int prof_kind[] = {RS_K_REACH, RS_K_REACH, RS_K_CHANCE, RS_K_UPDATE, RS_K_NODE_UTIL, RS_K_CHANCE, RS_K_TREE, RS_K_CHANCE, RS_K_DISCOUNT};
     if (L.kind == L_APPLY && t->dtype != RS_I32 && s->deal_mode) {   // every cell's deltas summed in deal order: the traverser's deals listed per cluster, round by round, then the node jobs
+        if (s->comm) return RS_OK;   // data-parallel: solver_exchange_float has applied the union batch
         const int pl = &plan == &s->plan[1] ? 1 : 0;
         prof_begin(t, RS_K_DISCOUNT, L.bytes);
         hipError_t ef = hipSuccess;
@@ -28,8 +29,7 @@ int run_launch(rs_solver *s, const Plan &plan, const Launch &L, hipStream_t tree
             uint32_t k = 0;
             for (size_t i = 0; i < t->nodes.size(); ++i)
                 if (t->nodes[i].round_idx == r && t->nodes[i].player == pl && t->nodes[i].n_actions > 0) k = std::max(k, t->nodes[i].n_clusters);
-            ef = launch_member_lists(s->deals.d_cluster[r][pl], s->deals.n_deals, int(k), plan.d_member_scratch, plan.d_member_scratch + member_list_tiles(s->deals.n_deals) * size_t(k),
-                                     plan.d_member_start[r], plan.d_members[r], t->stream);
+            ef = launch_member_lists(s->deals.d_cluster[r][pl], s->deals.n_deals, k, plan.d_member_scratch, plan.d_member_start[r], plan.d_members[r], t->stream);
         }
         if (ef == hipSuccess) ef = launch_apply_f32_rows(plan.d_f32_jobs, plan.n_f32_jobs, plan.f32_max_clusters, uint32_t(s->pitch[0]), t->dtype, (s->params.mode & RS_UPD_RMPLUS) != 0, t->stream);
         prof_end(t);
@@ -342,6 +342,19 @@ int rs::solver_discount_primary(rs_solver *s, float d) {
     return RS_OK;
 }
 
+// the item buffers of data-parallel float deal sweeps (solver_exchange_float grows them)
+static void fdp_free_items(rs_solver *s) {
+    for (void *q : {(void *)s->d_fdp_key, (void *)s->d_fdp_off, (void *)s->d_fdp_key_all, (void *)s->d_fdp_off_all, (void *)s->d_fdp_members, (void *)s->d_fdp_scratch,
+                    (void *)s->d_fdp_pay, (void *)s->d_fdp_pay_all})
+        if (q) (void)hipFree(q);
+    s->d_fdp_key = s->d_fdp_off = s->d_fdp_key_all = s->d_fdp_off_all = s->d_fdp_members = s->d_fdp_scratch = nullptr;
+    s->d_fdp_pay = s->d_fdp_pay_all = nullptr;
+    s->other_bytes -= s->fdp_bytes;
+    s->fdp_bytes = 0;
+    s->fdp_cap_items = 0;
+    s->fdp_cap_words = 0;
+}
+
 void rs::solver_release_device(rs_solver *s) {
     if (!s || !s->table) return;   // already detached (its table was destroyed first)
     rs_table *t = s->table;
@@ -427,6 +440,11 @@ void rs::solver_release_device(rs_solver *s) {
     if (s->d_item_count) (void)hipFree(s->d_item_count);
     s->d_packed = nullptr;
     s->d_items = s->d_items_all = s->d_item_count = nullptr;
+    fdp_free_items(s);
+    for (void *q : {(void *)s->d_fdp_jobs[0], (void *)s->d_fdp_jobs[1], (void *)s->d_fdp_scan, (void *)s->d_fdp_parts, (void *)s->d_fdp_count, (void *)s->d_fdp_start})
+        if (q) (void)hipFree(q);
+    s->d_fdp_jobs[0] = s->d_fdp_jobs[1] = nullptr;
+    s->d_fdp_scan = s->d_fdp_parts = s->d_fdp_count = s->d_fdp_start = nullptr;
     s->d_arena = nullptr;
     s->d_seed_state = nullptr;
     t->solvers.erase(std::remove(t->solvers.begin(), t->solvers.end(), s), t->solvers.end());
@@ -1248,6 +1266,83 @@ static int solver_exchange_deltas(rs_solver *s, int p) {
     return RS_OK;
 }
 
+// Data-parallel deal sweeps on FLOAT tables.  f32 sums do not associate, so partial sums of the ranks cannot be combined: the per-deal delta vectors travel.  Every rank
+//  * compacts its traverser nodes' [2A] per-deal vectors that hold a non-zero value into items -- key = (node's first key) + cluster, an offset, 2A floats -- in (node, deal)
+//    order (k_fdp_flags, two exclusive scans, k_fdp_pack);
+//  * all-gathers the (items, words) counts, then keys, offsets and floats, `most` of each per rank (every rank computes the same `most` from the same gathered counts, so
+//    every rank grows its buffers, or not, alike and issues the same collectives);
+//  * sorts the union stably by key (launch_member_lists): rank-major, deal order inside a rank -- the order of the global batch, whose deal numbers are rank-major;
+//  * sums every traverser cell's items from 0.0 in that order and adds the sum to the cell (k_fdp_apply: k_apply_f32_rows' write-back, every cell touched).
+// N ranks x n deals = one GPU with N x n deals, bit for bit.
+static int solver_exchange_float(rs_solver *s, int p) {
+    rs_table *t = s->table;
+    Plan &plan = s->plan[p];
+    const int world = comm_world(s->comm);
+    s->dp_bytes_last = 0;
+    if (s->fdp_broken) return fail(RS_ERR_OOM, "rs_iterate: the float delta items could not be allocated in an earlier sweep");
+    if (!s->d_fdp_scan || !s->d_fdp_jobs[p] || int(s->fdp_world) < world) return fail(RS_ERR_INVALID, "rs_iterate: float delta buffers missing (rs_solver_attach_comm)");
+    const uint32_t n = s->deals.n_deals, pitch = uint32_t(s->pitch[0]);
+    const size_t m = size_t(plan.n_f32_jobs) * n;
+    uint32_t *flags = s->d_fdp_scan, *words = s->d_fdp_scan + s->fdp_m + 1;
+    RS_HIP(launch_fdp_flags(s->d_fdp_jobs[p], plan.n_f32_jobs, n, pitch, flags, words, t->stream), "k_fdp_flags");
+    RS_HIP(launch_exclusive_scan_u32(flags, m + 1, s->d_fdp_parts, t->stream), "float delta items: scan");
+    RS_HIP(launch_exclusive_scan_u32(words, m + 1, s->d_fdp_parts, t->stream), "float delta items: scan");
+    RS_HIP(hipMemcpyAsync(s->d_fdp_count, flags + m, 4, hipMemcpyDeviceToDevice, t->stream), "float delta items: counts");
+    RS_HIP(hipMemcpyAsync(s->d_fdp_count + 1, words + m, 4, hipMemcpyDeviceToDevice, t->stream), "float delta items: counts");
+    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_count, s->d_fdp_count + 2, 2)) return rc;
+    std::vector<uint32_t> counts(2 + 2 * size_t(world));
+    RS_HIP(hipMemcpyAsync(counts.data(), s->d_fdp_count, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream), "float delta items: counts");
+    RS_HIP(hipStreamSynchronize(t->stream), "float delta items: counts");
+    uint32_t most = 0;
+    size_t most_words = 0;
+    for (int r = 0; r < world; ++r) {
+        most = std::max(most, counts[2 + 2 * size_t(r)]);
+        most_words = std::max<size_t>(most_words, counts[3 + 2 * size_t(r)]);
+    }
+    const uint64_t union_items = uint64_t(most) * uint64_t(world);
+    if (union_items >= (uint64_t(1) << 32)) return fail(RS_ERR_UNSUPPORTED, "rs_iterate: 2^32 or more float delta items in one data-parallel sweep");
+    if (most > s->fdp_cap_items || most_words > s->fdp_cap_words || !s->d_fdp_key) {   // grow: a function of the gathered counts alone, hence the same on every rank
+        RS_HIP(hipStreamSynchronize(t->stream), "float delta items");
+        fdp_free_items(s);
+        const uint32_t cap = uint32_t(std::min<uint64_t>(uint64_t(most) + most / 8 + 1024, ((uint64_t(1) << 32) - 1) / uint64_t(world)));
+        const size_t cap_words = most_words + most_words / 8 + 1024 * 2 * RS_MAX_ACTIONS;
+        const size_t scratch = member_lists_scratch_words_upto(size_t(cap) * world, std::max(s->fdp_keys[0], s->fdp_keys[1]) + 1);
+        bool ok = hipMalloc((void **)&s->d_fdp_key, size_t(cap) * 4) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_off, size_t(cap) * 4) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_key_all, size_t(cap) * 4 * world) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_off_all, size_t(cap) * 4 * world) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_members, size_t(cap) * 4 * world) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_scratch, std::max<size_t>(scratch, 1) * 4) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_pay, cap_words * 4) == hipSuccess;
+        ok = ok && hipMalloc((void **)&s->d_fdp_pay_all, cap_words * 4 * world) == hipSuccess;
+        if (!ok) {   // nothing is launched on a missing buffer: this sweep and every later one fail
+            (void)hipGetLastError();
+            fdp_free_items(s);
+            s->fdp_broken = true;
+            return fail(RS_ERR_OOM, "rs_iterate: float delta items (data-parallel deal sweep)");
+        }
+        s->fdp_cap_items = cap;
+        s->fdp_cap_words = cap_words;
+        s->fdp_bytes = size_t(cap) * 4 * (2 + 3 * size_t(world)) + std::max<size_t>(scratch, 1) * 4 + cap_words * 4 * (1 + size_t(world));
+        s->other_bytes += s->fdp_bytes;
+    }
+    FdpClusters cl{};
+    for (int r = 0; r < s->n_rounds && r < RS_MAX_ROUNDS; ++r) cl.c[r] = s->deals.d_cluster[r][p];
+    RS_HIP(launch_fdp_pack(s->d_fdp_jobs[p], plan.n_f32_jobs, n, pitch, cl, flags, words, s->d_fdp_key, s->d_fdp_off, s->d_fdp_pay, t->stream), "k_fdp_pack");
+    const uint32_t own = counts[0];
+    if (most > own) RS_HIP(hipMemsetAsync(s->d_fdp_key + own, 0xff, size_t(most - own) * 4, t->stream), "float delta items: padding");   // beyond every key: the last list
+    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_key, s->d_fdp_key_all, most)) return rc;
+    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_off, s->d_fdp_off_all, most)) return rc;
+    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_pay, s->d_fdp_pay_all, most_words)) return rc;
+    const uint32_t k = s->fdp_keys[p] + 1;   // the padding's key is clamped to fdp_keys[p]: a list nobody reads
+    RS_HIP(launch_member_lists(s->d_fdp_key_all, size_t(union_items), k, s->d_fdp_scratch, s->d_fdp_start, s->d_fdp_members, t->stream), "float delta items: member lists");
+    RS_HIP(launch_fdp_apply(plan.d_f32_jobs, s->d_fdp_jobs[p], plan.n_f32_jobs, plan.f32_max_clusters, s->d_fdp_start, s->d_fdp_members, s->d_fdp_off_all, s->d_fdp_pay_all,
+                            most, most_words, t->dtype, (s->params.mode & RS_UPD_RMPLUS) != 0, t->stream),
+           "k_fdp_apply");
+    s->dp_bytes_last = 8 * uint64_t(world) + (uint64_t(most) * 8 + uint64_t(most_words) * 4) * uint64_t(world);
+    return RS_OK;
+}
+
 int rs_iterate(rs_solver *s, int traverser, float *d_root_util) {
     if (!s) return fail(RS_ERR_INVALID, "rs_iterate: solver is NULL");
     if (!s->table) return fail(RS_ERR_INVALID, "rs_iterate: the solver's table has been destroyed");
@@ -1262,15 +1357,13 @@ int rs_iterate(rs_solver *s, int traverser, float *d_root_util) {
         if (int rc = run_plan(s, traverser, 1)) return rc;
         return copy_root(s, traverser, d_root_util);
     }
-    if (s->deal_mode && s->comm && s->table->dtype != RS_I32)
-        return fail(RS_ERR_UNSUPPORTED, "rs_iterate: data-parallel deal batches all-reduce i32 deltas; a deal solver on a float table runs on one GPU");
     if (s->order_ahead && s->comm) return fail(RS_ERR_UNSUPPORTED, "rs_iterate: this solver's deal records are sorted ahead by its trainer, which runs on one GPU");
     if (s->before_sweep)
         if (int rc = s->before_sweep(s->before_sweep_ctx, traverser)) return rc;
     if (s->deal_mode && s->comm) {   // data-parallel deal batches: sweep, exchange the deltas of the ranks, apply the union
         if (s->d_item_count) RS_HIP(hipMemsetAsync(s->d_item_count, 0, sizeof(uint32_t), s->table->stream), "deal delta items");
         if (int rc = run_plan(s, traverser, 0)) return rc;
-        if (int rc = solver_exchange_deltas(s, traverser)) return rc;
+        if (int rc = s->table->dtype != RS_I32 ? solver_exchange_float(s, traverser) : solver_exchange_deltas(s, traverser)) return rc;
         s->dp_bytes_total += s->dp_bytes_last;
         s->dp_sweeps += 1;
         if (int rc = run_plan(s, traverser, 1)) return rc;
@@ -1289,6 +1382,9 @@ int rs_iterate_phase(rs_solver *s, int traverser, int phase, float *d_root_util)
             if (rows_round_direct(s, traverser, r))
                 return fail(RS_ERR_UNSUPPORTED, "rs_iterate_phase: this solver adds the delta rows of its large rounds straight into the table during the walks, so the delta tables "
                                                 "a host would exchange between the phases are incomplete: create it with rs_kernel_forms.direct_rows = RS_FORM_OFF");
+    if (s->deal_mode && s->comm && s->table->dtype != RS_I32)
+        return fail(RS_ERR_UNSUPPORTED, "rs_iterate_phase: a float-table deal solver under a communicator exchanges per-deal delta items and sums them in global deal order "
+                                        "inside rs_iterate; a host driving the phases has no delta tables to exchange (float sums do not associate): call rs_iterate");
     RS_HIP(hipSetDevice(s->table->device), "hipSetDevice");
     if (s->before_sweep && phase == 0)
         if (int rc = s->before_sweep(s->before_sweep_ctx, traverser)) return rc;
@@ -1326,6 +1422,55 @@ int rs_solver_attach_comm(rs_solver *s, rs_comm *comm) {
             RS_HIP(hipMalloc((void **)&s->d_items, size_t(s->item_cap) * 12), "rs_solver_attach_comm: delta items");
             RS_HIP(hipMalloc((void **)&s->d_items_all, size_t(s->item_cap) * 12 * size_t(s->items_world)), "rs_solver_attach_comm: delta items");
             s->other_bytes += size_t(s->item_cap) * 12 * (size_t(s->items_world) + 1);
+        }
+    }
+    if (comm && s->deal_mode && s->table && s->table->dtype != RS_I32) {   // the fixed buffers of solver_exchange_float; the item buffers grow with the first sweeps
+        rs_table *t = s->table;
+        RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+        const size_t world = size_t(comm_world(comm));
+        size_t m = 0;
+        uint64_t keys_max = 0;
+        for (int p = 0; p < 2; ++p) {
+            std::vector<FdpJob> jobs;
+            uint64_t keys = 0, words = 0;
+            for (size_t i = 0; i < t->nodes.size(); ++i) {   // the order of emit_apply's ApplyF32Jobs
+                const rs_node_desc &d = t->nodes[i];
+                if (d.n_actions == 0 || d.player != p) continue;
+                FdpJob j{};
+                j.rows = s->plan[p].d_frows + s->plan[p].frow_off[i];
+                j.n_actions = d.n_actions;
+                j.round = uint32_t(d.round_idx);
+                j.key_off = uint32_t(keys);
+                keys += d.n_clusters;
+                words += uint64_t(2) * d.n_actions * s->deals.n_deals;
+                jobs.push_back(j);
+            }
+            if (keys >= 0xffffffffull || words >= 0xffffffffull || uint64_t(jobs.size()) * s->deals.n_deals >= 0xffffffffull)
+                return fail(RS_ERR_UNSUPPORTED, "rs_solver_attach_comm: a float deal solver's items are counted in 32 bits (2^32 or more clusters, delta floats or (node, deal) pairs)");
+            if (int(jobs.size()) != s->plan[p].n_f32_jobs) return fail(RS_ERR_INVALID, "rs_solver_attach_comm: float apply jobs out of step");
+            s->fdp_keys[p] = uint32_t(keys);
+            keys_max = std::max(keys_max, keys);
+            m = std::max(m, jobs.size() * size_t(s->deals.n_deals));
+            if (!s->d_fdp_jobs[p] && !jobs.empty()) {
+                RS_HIP(hipMalloc((void **)&s->d_fdp_jobs[p], jobs.size() * sizeof(FdpJob)), "rs_solver_attach_comm: float item jobs");
+                RS_HIP(hipMemcpy(s->d_fdp_jobs[p], jobs.data(), jobs.size() * sizeof(FdpJob), hipMemcpyHostToDevice), "rs_solver_attach_comm: float item jobs");
+                s->other_bytes += jobs.size() * sizeof(FdpJob);
+            }
+        }
+        if (!s->d_fdp_scan) {
+            s->fdp_m = m;
+            RS_HIP(hipMalloc((void **)&s->d_fdp_scan, (m + 1) * 2 * 4), "rs_solver_attach_comm: float item scans");
+            RS_HIP(hipMalloc((void **)&s->d_fdp_parts, exclusive_scan_parts(m + 1) * 4), "rs_solver_attach_comm: float item scans");
+            RS_HIP(hipMalloc((void **)&s->d_fdp_start, (size_t(keys_max) + 2) * 4), "rs_solver_attach_comm: float member lists");
+            s->other_bytes += (m + 1) * 8 + exclusive_scan_parts(m + 1) * 4 + (size_t(keys_max) + 2) * 4;
+        }
+        if (world > s->fdp_world) {
+            if (s->d_fdp_count) (void)hipFree(s->d_fdp_count);
+            s->d_fdp_count = nullptr;
+            RS_HIP(hipStreamSynchronize(t->stream), "rs_solver_attach_comm");
+            fdp_free_items(s);   // sized for fewer ranks
+            RS_HIP(hipMalloc((void **)&s->d_fdp_count, (2 + 2 * world) * sizeof(uint32_t)), "rs_solver_attach_comm: float item counts");
+            s->fdp_world = uint32_t(world);
         }
     }
     s->comm = comm;

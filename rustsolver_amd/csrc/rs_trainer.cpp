@@ -155,8 +155,8 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
     }
     const int dtype = params->table_dtype;
     if (rc == RS_OK && dtype != RS_I32 && dtype != RS_F32 && dtype != RS_F16) rc = fail(RS_ERR_INVALID, "rs_deal_trainer_create: table_dtype is RS_I32, RS_F32 or RS_F16");
-    if (rc == RS_OK && dtype != RS_I32 && (params->prune_threshold != UINT64_MAX || tr->world > 1))
-        rc = fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_create: float tables (extension) take no pruning (prune_threshold = UINT64_MAX: cfr.rs:352 compares i32 regrets) and run on one GPU");
+    if (rc == RS_OK && dtype != RS_I32 && params->prune_threshold != UINT64_MAX)
+        rc = fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_create: float tables (extension) take no pruning (prune_threshold = UINT64_MAX: cfr.rs:352 compares i32 regrets)");
     if (rc == RS_OK) rc = rs_create_infosets(tr->tree, n_clusters, n_boards, dtype, device, &tr->table);   // cfr.rs:176
     const size_t pitch = round_up(params->deals_per_batch, kLanePad);
     const size_t n_hands[2] = {n_hands_p0, n_hands_p1};
