@@ -43,6 +43,11 @@ int rs_solver_exchange_bytes(const rs_solver *solver, uint64_t *bytes, uint64_t 
 /* ---- the member lists of the float deal apply: a stable sort of 0 .. n-1 by key.  d_members[d_start[c] .. d_start[c + 1]) = the indices whose key is c, ascending;
  * keys >= k count as k - 1.  DEVICE buffers: d_keys [n], d_start [k + 1], d_members [n]; k >= 1, n < 2^32.  Allocates its own scratch; synchronises. */
 int rs_member_lists(rs_table *table, const uint32_t *d_keys, size_t n, uint32_t k, uint32_t *d_start, uint32_t *d_members);
+/* ---- device memory the library holds: the bytes of every buffer its objects own right now (tables, solvers, trainers, card abstractions, best-response
+ * workspaces, scratch), process-wide.  What rs_dmalloc hands out belongs to the caller and is not counted. */
+size_t rs_device_held_bytes(void);
+/* test hook: grant the next n device allocations of the library, then refuse one with RS_ERR_OOM (nothing reaches the device) and disarm; n < 0 disarms */
+int rs_debug_fail_alloc(int64_t n);
 
 /* ---- checks of the generated (hipRTC) kernels without a GPU ---------------------------------------------------------------------- */
 /* generate + compile (no GPU needed) the tree-specialised kernels of every chance-free subtree, both traversers */

@@ -127,6 +127,8 @@ SYMBOLS = {
     "rs_table_fill_random": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "rs_fill_uniform_f32": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_float, C.c_float]),
     "rs_member_lists": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, _P]),
+    "rs_device_held_bytes": (C.c_size_t, []),
+    "rs_debug_fail_alloc": (C.c_int, [C.c_int64]),
     "rs_table_plant_saturating": (C.c_int, [_P, C.c_uint64, C.c_uint32]),
     "rs_fill_uniform_f32_at": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_float, C.c_float, C.c_uint64]),
     "rs_table_fill_random_logical": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),

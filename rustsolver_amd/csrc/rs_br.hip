@@ -289,21 +289,19 @@ int rs_calc_br(rs_table *t, const rs_tree *tree, float *out) {
     for (uint32_t n = 0; n < n_nodes; ++n) rows[n] = row_of(t, int(n));
     std::vector<float> prob(size_t(n_nodes) * RS_MAX_ACTIONS);
     if (n_nodes) {
-        BrNodeRow *d_rows = nullptr;
-        float *d_prob = nullptr;
-        RS_HIP(hipMalloc(&d_rows, rows.size() * sizeof(BrNodeRow)), "hipMalloc(calc_br rows)");
-        hipError_t e = hipMalloc(&d_prob, prob.size() * sizeof(float));
+        DevBuf<BrNodeRow> d_rows;
+        DevBuf<float> d_prob;
+        RS_HIP(d_rows.alloc(rows.size()), "calc_br rows");
+        hipError_t e = d_prob.alloc(prob.size());
         if (e == hipSuccess) e = hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(BrNodeRow), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-#define RS_B0(DT_) hipLaunchKernelGGL((k_bucket0_final_strategy<DT_>), dim3(grid1(n_nodes)), dim3(kBrBlock), 0, t->stream, t->d_ssum, d_rows, n_nodes, d_prob)
+#define RS_B0(DT_) hipLaunchKernelGGL((k_bucket0_final_strategy<DT_>), dim3(grid1(n_nodes)), dim3(kBrBlock), 0, t->stream, t->d_ssum.get(), d_rows.get(), n_nodes, d_prob.get())
             RS_BR_DT(t->dtype, RS_B0);
 #undef RS_B0
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(prob.data(), d_prob, prob.size() * sizeof(float), hipMemcpyDeviceToHost, t->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-        (void)hipFree(d_rows);
-        if (d_prob) (void)hipFree(d_prob);
         if (e != hipSuccess) return hip_fail(e, "rs_calc_br");
     }
     const AsCoded walk{tree->nodes, prob};
@@ -1090,6 +1088,7 @@ struct BrSide {
 };
 
 struct BrRun {
+    size_t dev_bytes = 0;                     // the ledger of its device buffers: dalloc's (the game-only half) and the walk's workspace (br_held_bytes)
     rs_table *t = nullptr;
     const rs_tree *tree = nullptr;
     int mode = RS_BR_MAX;
@@ -1098,21 +1097,16 @@ struct BrRun {
     uint32_t NB = 1;
     uint64_t *d_bmask = nullptr;
     BrSide side[2];
-    std::vector<void *> allocs;
+    std::vector<DevBuf<char>> allocs;
     std::vector<double *> q_level, v_level;   // per tree depth: [max actions][n_pad] children buffers
     double *d_root = nullptr;                 // [n_pad_max]: the root values of the traverser's lanes (depth-first walk)
     bool last_level_plan = false;             // what the last br_execute ran, and its launches (level plan)
     int last_launches = 0;
-    double *ws = nullptr;                     // the walk's workspace, allocated by the first br_execute and kept (a 60 GB hipMalloc takes seconds): level plan or depth-first
-    size_t ws_bytes = 0, game_bytes = 0;      // game_bytes: what dalloc handed out (the game-only half)
+    DevBuf<double> ws;                        // the walk's workspace, allocated by the first br_execute and kept (a 60 GB allocation takes seconds): level plan or depth-first
     bool ws_levels = false;
     void release_workspace() {
-        if (ws) {
-            (void)hipStreamSynchronize(t->stream);
-            (void)hipFree(ws);
-        }
-        ws = nullptr;
-        ws_bytes = 0;
+        if (ws) (void)hipStreamSynchronize(t->stream);
+        ws.reset();
         q_level.clear();
         v_level.clear();
         d_root = nullptr;
@@ -1121,22 +1115,16 @@ struct BrRun {
     hipError_t err = hipSuccess;
 
     template <typename T> T *dalloc(size_t n) {
-        void *ptr = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&ptr, (n ? n : 1) * sizeof(T));
-        if (err == hipSuccess) {
-            allocs.push_back(ptr);
-            game_bytes += (n ? n : 1) * sizeof(T);
-        }
-        return static_cast<T *>(ptr);
+        DevBuf<char> b;
+        if (err == hipSuccess) err = b.alloc(std::max<size_t>(n, 1) * sizeof(T), &dev_bytes);
+        T *ptr = reinterpret_cast<T *>(b.get());
+        if (ptr) allocs.push_back(std::move(b));
+        return ptr;
     }
     template <typename T> T *upload(const std::vector<T> &h) {
         T *d = dalloc<T>(h.size());
         if (err == hipSuccess && !h.empty()) err = hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);   // blocking: h may be a temporary
         return d;
-    }
-    ~BrRun() {
-        if (ws) (void)hipFree(ws);
-        for (void *ptr : allocs) (void)hipFree(ptr);
     }
 
     // ---- the level plan: every node gets buffers of its own (an action node: [A][n_pad] for its children's values, an opponent's node the same for their reach), so the
@@ -1268,8 +1256,8 @@ struct BrRun {
             o_sum.push_back(put(up_sum[size_t(d)]));
         }
         const size_t o_leaves = put(leaves);
-        BrJob *d_jobs = nullptr;
-        err = hipMalloc((void **)&d_jobs, std::max<size_t>(all.size(), 1) * sizeof(BrJob));
+        DevBuf<BrJob> d_jobs;
+        err = d_jobs.alloc(all.size());
         if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, all.data(), all.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(t->stream);   // `all` is a local
         n_launches = 0;
@@ -1381,8 +1369,7 @@ struct BrRun {
                 ++n_launches;
             }
         }
-        if (err == hipSuccess) err = hipStreamSynchronize(t->stream);   // d_jobs is freed below
-        if (d_jobs) (void)hipFree(d_jobs);
+        if (err == hipSuccess) err = hipStreamSynchronize(t->stream);   // d_jobs is freed on return
         return err == hipSuccess ? RS_OK : hip_fail(err, "rs_best_response (level plan)");
     }
     int n_launches = 0;
@@ -1802,7 +1789,7 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
 }
 
 void br_free(BrRun *run) { delete run; }
-size_t br_held_bytes(const BrRun *run) { return run ? run->game_bytes + run->ws_bytes : 0; }
+size_t br_held_bytes(const BrRun *run) { return run ? run->dev_bytes : 0; }
 void br_release_workspace(BrRun *run) {
     if (run) run->release_workspace();
 }
@@ -1818,7 +1805,7 @@ int br_execute(BrRun *prepared, int mode, double *out) {
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     run.mode = mode;
     run.err = hipSuccess;
-    // The level plan wants a buffer per tree edge (full 1 176-combo ranges from a flop on the 706-node tree: 59 GB, and a hipMalloc of that size takes seconds; 200 combos: 10 GB)
+    // The level plan wants a buffer per tree edge (full 1 176-combo ranges from a flop on the 706-node tree: 59 GB, and an allocation of that size takes seconds; 200 combos: 10 GB)
     // and buys launches, not kernel time (4 300 -> 66 per call; at full ranges both orders spend 0.24-0.27 s in their kernels): it is taken while it fits kBrLevelPlanBytes and half
     // of the free memory, else the depth-first walk runs with its two buffers per tree depth.  The workspace is allocated by the first call and KEPT with the object
     // (br_workspace_bytes / br_release_workspace: a trainer holds one object per showdown mode).
@@ -1827,21 +1814,14 @@ int br_execute(BrRun *prepared, int mode, double *out) {
         size_t free_b = 0, total_b = 0;
         const bool levels = !knobs_resolve(nullptr).br_depth_first && need <= kBrLevelPlanBytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
         (void)hipGetLastError();
-        if (levels && hipMalloc((void **)&run.ws, need) == hipSuccess) {
-            run.ws_bytes = need;
+        if (levels && run.ws.alloc(need / sizeof(double), &run.dev_bytes) == hipSuccess) {
             run.ws_levels = true;
         } else {
-            (void)hipGetLastError();
             int max_a = 1;
             for (const rs_tree_node &n : run.tree->nodes) max_a = std::max(max_a, n.n_children);
             const int depth = tree_depth(run.tree->nodes, 0);
             const size_t per = size_t(max_a) * run.n_pad_max;
-            run.ws_bytes = (size_t(2) * size_t(depth) * per + run.n_pad_max) * sizeof(double);
-            if (hipMalloc((void **)&run.ws, run.ws_bytes) != hipSuccess) {
-                run.ws = nullptr;
-                run.ws_bytes = 0;
-                return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
-            }
+            if (run.ws.alloc(size_t(2) * size_t(depth) * per + run.n_pad_max, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
             run.ws_levels = false;
             for (int l = 0; l < depth; ++l) {
                 run.q_level.push_back(run.ws + size_t(2 * l) * per);

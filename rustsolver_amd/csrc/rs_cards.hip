@@ -40,7 +40,7 @@ struct rs_hand_indexer {
     std::vector<uint64_t> perm_offset[kHiMaxRounds];
     struct Dev {
         int device;
-        void *blob;
+        DevBuf<char> blob;
         HandIndexView view;
     };
     std::vector<Dev> devs;                          // one mirror per device that used it
@@ -169,19 +169,16 @@ int device_view(rs_hand_indexer *ix, int device, hipStream_t stream, HandIndexVi
     std::vector<char> host(bytes, 0);
     std::memcpy(host.data(), ix->rank_rank.data(), ix->rank_rank.size() * sizeof(uint16_t));
     for (int r = 0; r < ix->rounds; ++r) std::memcpy(host.data() + off[r], ix->perm_offset[r].data(), ix->perm_offset[r].size() * sizeof(uint64_t));
-    void *blob = nullptr;
+    DevBuf<char> blob;
     RS_HIP(hipSetDevice(device), "hipSetDevice");
-    RS_HIP(hipMalloc(&blob, bytes), "rs_hand_indexer: device tables");
+    RS_HIP(blob.alloc(bytes), "rs_hand_indexer: device tables");
     hipError_t e = hipMemcpyAsync(blob, host.data(), bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);   // `host` dies at return
-    if (e != hipSuccess) {
-        (void)hipFree(blob);
-        return hip_fail(e, "rs_hand_indexer: table upload");
-    }
+    if (e != hipSuccess) return hip_fail(e, "rs_hand_indexer: table upload");
     HandIndexView v = ix->host_view();
-    v.rank_rank = reinterpret_cast<const uint16_t *>(blob);
-    for (int r = 0; r < kHiMaxRounds; ++r) v.perm_offset[r] = r < ix->rounds ? reinterpret_cast<const uint64_t *>((char *)blob + off[r]) : nullptr;
-    ix->devs.push_back({device, blob, v});
+    v.rank_rank = reinterpret_cast<const uint16_t *>(blob.get());
+    for (int r = 0; r < kHiMaxRounds; ++r) v.perm_offset[r] = r < ix->rounds ? reinterpret_cast<const uint64_t *>(blob + off[r]) : nullptr;
+    ix->devs.push_back({device, std::move(blob), v});
     *out = v;
     return RS_OK;
 }
@@ -489,55 +486,55 @@ struct rs_card_abs {
         uint16_t *pid;
         uint32_t xw;
     };
-    std::vector<Dev> devs;
+    struct Mirror {                             // the buffers a Dev points at
+        Dev view{};
+        DevBuf<uint32_t> cluster_arr, lut[2], err, xlut[2];
+        DevBuf<DenseSlot> slots[2];
+        DevBuf<uint16_t> pid;
+    };
+    std::vector<Mirror> devs;
     std::mutex mu;
 };
 
 namespace rs {
-hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Dev *d);   // below the kernels
+hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Mirror *m);   // below the kernels
 }
 namespace {
 int abs_device(rs_card_abs *a, rs_table *t, rs_card_abs::Dev *out) {
     std::lock_guard<std::mutex> lock(a->mu);
-    for (const auto &d : a->devs)
-        if (d.device == t->device) {
-            *out = d;
+    for (const auto &m : a->devs)
+        if (m.view.device == t->device) {
+            *out = m.view;
             return RS_OK;
         }
-    rs_card_abs::Dev d{};
+    rs_card_abs::Mirror m;
+    rs_card_abs::Dev &d = m.view;
     d.device = t->device;
     hipError_t e = hipSetDevice(t->device);
     if (e == hipSuccess && a->has_arr && !a->cluster_arr.empty()) {
-        e = hipMalloc(reinterpret_cast<void **>(&d.cluster_arr), a->cluster_arr.size() * sizeof(uint32_t));
+        e = m.cluster_arr.alloc(a->cluster_arr.size());
+        d.cluster_arr = m.cluster_arr;
         if (e == hipSuccess) e = hipMemcpyAsync(d.cluster_arr, a->cluster_arr.data(), a->cluster_arr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream);
     }
     for (int p = 0; e == hipSuccess && p < 2; ++p) {
-        e = hipMalloc(reinterpret_cast<void **>(&d.slots[p]), a->slots[p].size() * sizeof(DenseSlot));
+        e = m.slots[p].alloc(a->slots[p].size());
+        d.slots[p] = m.slots[p];
         if (e == hipSuccess) e = hipMemcpyAsync(d.slots[p], a->slots[p].data(), a->slots[p].size() * sizeof(DenseSlot), hipMemcpyHostToDevice, t->stream);
     }
     for (int p = 0; e == hipSuccess && p < 2; ++p) {
         if (a->lut[p].empty()) continue;
-        e = hipMalloc(reinterpret_cast<void **>(&d.lut[p]), a->lut[p].size() * sizeof(uint32_t));
+        e = m.lut[p].alloc(a->lut[p].size());
+        d.lut[p] = m.lut[p];
         if (e == hipSuccess) e = hipMemcpyAsync(d.lut[p], a->lut[p].data(), a->lut[p].size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream);
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d.err), sizeof(uint32_t));
+    if (e == hipSuccess) e = m.err.alloc(1);
+    d.err = m.err;
     if (e == hipSuccess) e = hipMemsetAsync(d.err, 0, sizeof(uint32_t), t->stream);
-    if (e == hipSuccess && a->cards_left > 0 && !a->pair_cards.empty()) e = build_xlut(a, t, &d);
+    if (e == hipSuccess && a->cards_left > 0 && !a->pair_cards.empty()) e = build_xlut(a, t, &m);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d.cluster_arr);
-        (void)hipFree(d.slots[0]);
-        (void)hipFree(d.slots[1]);
-        (void)hipFree(d.lut[0]);
-        (void)hipFree(d.lut[1]);
-        (void)hipFree(d.xlut[0]);
-        (void)hipFree(d.xlut[1]);
-        (void)hipFree(d.pid);
-        (void)hipFree(d.err);
-        return hip_fail(e, "rs_card_abs: device mirror");
-    }
-    a->devs.push_back(d);
+    if (e != hipSuccess) return hip_fail(e, "rs_card_abs: device mirror");
     *out = d;
+    a->devs.push_back(std::move(m));
     return RS_OK;
 }
 }  // namespace
@@ -584,10 +581,7 @@ int rs_hand_indexer_create(int rounds, const uint8_t *cards_per_round, rs_hand_i
 void rs_hand_indexer_destroy(rs_hand_indexer *ix) {
     if (!ix) return;
     for (auto &d : ix->devs)
-        if (hipSetDevice(d.device) == hipSuccess) {
-            (void)hipDeviceSynchronize();   // a launch may still read the tables
-            (void)hipFree(d.blob);
-        }
+        if (hipSetDevice(d.device) == hipSuccess) (void)hipDeviceSynchronize();   // a launch may still read the tables
     delete ix;
 }
 
@@ -737,19 +731,8 @@ static void dense_insert(std::vector<DenseSlot> &slots, std::vector<uint64_t> &k
 
 void rs_card_abs_destroy(rs_card_abs *a) {
     if (!a) return;
-    for (auto &d : a->devs)
-        if (hipSetDevice(d.device) == hipSuccess) {
-            (void)hipDeviceSynchronize();   // a launch may still read the mirror
-            (void)hipFree(d.cluster_arr);
-            (void)hipFree(d.slots[0]);
-            (void)hipFree(d.slots[1]);
-            (void)hipFree(d.lut[0]);
-            (void)hipFree(d.lut[1]);
-            (void)hipFree(d.xlut[0]);
-            (void)hipFree(d.xlut[1]);
-            (void)hipFree(d.pid);
-            (void)hipFree(d.err);
-        }
+    for (auto &m : a->devs)
+        if (hipSetDevice(m.view.device) == hipSuccess) (void)hipDeviceSynchronize();   // a launch may still read the mirror
     rs_hand_indexer_destroy(a->ix);
     delete a;
 }
@@ -897,19 +880,22 @@ namespace rs {
 // get_cluster tabulated over (hole pair, the one or two board cards beyond the initial board): 1 176 x 52 entries for a flop-start game's turn, 1 176 x 1 176 (5.5 MB) for its
 // river, per player.  The index path (hand index: ~1 000 vector instructions of 64-bit arithmetic, a 4-byte read from a bucket file of up to 492 MB, a hash probe) then runs
 // once per table entry instead of once per deal and sweep: 4 M deals, flop start, river: 219 -> ~20 us per call.
-hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Dev *d) {
+hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Mirror *m) {
+    rs_card_abs::Dev *d = &m->view;
     HandIndexView v;
     if (device_view(a->ix, t->device, t->stream, &v) != RS_OK) return hipErrorUnknown;
     const uint32_t n_pairs = uint32_t(a->pair_cards.size());
     d->xw = a->cards_left == 1 ? 52u : n_pairs;
-    uint16_t *d_pairs = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d->pid), a->pid.size() * sizeof(uint16_t));
+    DevBuf<uint16_t> d_pairs;
+    hipError_t e = m->pid.alloc(a->pid.size());
+    d->pid = m->pid;
     if (e == hipSuccess) e = hipMemcpyAsync(d->pid, a->pid.data(), a->pid.size() * sizeof(uint16_t), hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_pairs), n_pairs * sizeof(uint16_t));
+    if (e == hipSuccess) e = d_pairs.alloc(n_pairs);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pairs, a->pair_cards.data(), n_pairs * sizeof(uint16_t), hipMemcpyHostToDevice, t->stream);
     const size_t entries = size_t(n_pairs) * d->xw;
     for (int p = 0; e == hipSuccess && p < 2; ++p) {
-        e = hipMalloc(reinterpret_cast<void **>(&d->xlut[p]), entries * sizeof(uint32_t));
+        e = m->xlut[p].alloc(entries);
+        d->xlut[p] = m->xlut[p];
         if (e != hipSuccess) break;
         ClusterJob j;
         std::memset(&j, 0, sizeof(j));
@@ -923,11 +909,10 @@ hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Dev *d) {
         j.xw = d->xw;
         j.n_fixed = a->n_fixed;
         j.cards_left = a->cards_left;
-        hipLaunchKernelGGL(k_cluster_xlut, dim3(uint32_t(std::min<size_t>((entries + kBlock - 1) / kBlock, 8192))), dim3(kBlock), 0, t->stream, j, d_pairs, n_pairs, d->xlut[p]);
+        hipLaunchKernelGGL(k_cluster_xlut, dim3(uint32_t(std::min<size_t>((entries + kBlock - 1) / kBlock, 8192))), dim3(kBlock), 0, t->stream, j, d_pairs.get(), n_pairs, d->xlut[p]);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);   // d_pairs is freed below
-    (void)hipFree(d_pairs);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);   // d_pairs is freed on return
     return e;
 }
 // the same on a stream of the caller's choice (the trainer deals the NEXT batch beside the sweeps of the current one)
@@ -1036,7 +1021,7 @@ int deals_sample_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t fir
     if (n_board < 3 || n_board > 5) return fail(RS_ERR_INVALID, "invalid board mask");   // options.rs:41
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     if (!d_err) {
-        if (!t->d_err_sink) RS_HIP(hipMalloc(reinterpret_cast<void **>(&t->d_err_sink), sizeof(uint32_t)), "rs_deals_sample: error word");
+        if (!t->d_err_sink) RS_HIP(t->d_err_sink.alloc(1), "rs_deals_sample: error word");
         d_err = t->d_err_sink;   // nobody reads it
     }
     if (n_deals == 0) return RS_OK;

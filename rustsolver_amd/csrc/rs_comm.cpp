@@ -190,19 +190,15 @@ int rs_replicated_begin(rs_table *t, uint32_t round_mask) {
                 t->rep_off.push_back(t->rep_cells);
                 t->rep_cells += t->pitch[n] * t->nodes[n].n_actions;
             }
-        if (t->d_snap_regrets) (void)hipFree(t->d_snap_regrets);
-        if (t->d_snap_ssum) (void)hipFree(t->d_snap_ssum);
-        t->d_snap_regrets = t->d_snap_ssum = nullptr;
+        t->d_snap_regrets.reset();
+        t->d_snap_ssum.reset();
         if (t->rep_cells) {
-            if ((e = hipMalloc(&t->d_snap_regrets, t->rep_cells * 4)) != hipSuccess ||
-                (e = hipMalloc(&t->d_snap_ssum, t->rep_cells * 4)) != hipSuccess) {
-                if (t->d_snap_regrets) (void)hipFree(t->d_snap_regrets);
-                if (t->d_snap_ssum) (void)hipFree(t->d_snap_ssum);
-                t->d_snap_regrets = t->d_snap_ssum = nullptr;
+            if ((e = t->d_snap_regrets.alloc(t->rep_cells * 4)) != hipSuccess || (e = t->d_snap_ssum.alloc(t->rep_cells * 4)) != hipSuccess) {
+                t->d_snap_regrets.reset();
                 t->rep_nodes.clear();
                 t->rep_off.clear();
                 t->rep_cells = 0;
-                return hip_fail(e, "rs_replicated_begin: snapshot hipMalloc");
+                return hip_fail(e, "rs_replicated_begin: snapshot allocation");
             }
         }
         t->rep_mask = round_mask;

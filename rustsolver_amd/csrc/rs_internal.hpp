@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "rs_dev.hpp"
 #include "rustsolver_amd.h"
 #include "rustsolver_amd_diag.h"
 
@@ -395,13 +396,13 @@ inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 struct Profile {
     bool on = false;
     struct Pending {
-        hipEvent_t a, b;
+        DevEvent a, b;
         int kind;
         double bytes;
     };
     std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
-    std::vector<hipEvent_t> marks;     // rs_profile_mark: events on the table's stream, read (and recycled) by rs_profile_marks
+    std::vector<DevEvent> pool;
+    std::vector<DevEvent> marks;     // rs_profile_mark: events on the table's stream, read (and recycled) by rs_profile_marks
     rs_profile acc{};
 };
 
@@ -415,30 +416,29 @@ struct rs_tree {
 struct rs_table {
     int device = 0;
     int dtype = RS_I32;
-    hipStream_t stream = nullptr;
+    rs::DevStream stream;             // first: destroyed after every buffer
     std::vector<rs_node_desc> nodes;
     std::vector<size_t> pitch;        // per node, elements
     std::vector<size_t> tile;         // per node: lanes per tile of its block [pitch / tile][A][tile]; == pitch: the plain [A][pitch] block
     std::vector<size_t> cell_off;     // per node, element offset of its [A][pitch] block
     size_t n_cells = 0;
-    void *d_regrets = nullptr;        // n_cells elements
-    void *d_ssum = nullptr;
-    void *d_snap_regrets = nullptr;   // replicated-round snapshots (multi-GPU), lazily allocated, compact
-    void *d_snap_ssum = nullptr;
+    rs::DevBuf<char> d_regrets;       // n_cells elements
+    rs::DevBuf<char> d_ssum;
+    rs::DevBuf<char> d_snap_regrets;   // replicated-round snapshots (multi-GPU), lazily allocated, compact
+    rs::DevBuf<char> d_snap_ssum;
     uint32_t rep_mask = 0;            // rounds covered by the snapshot
     std::vector<int> rep_nodes;       // replicated node indices
     std::vector<size_t> rep_off;      // element offset of each of them inside the compact snapshot
     size_t rep_cells = 0;
-    void *d_dregrets = nullptr;       // deal batches: delta tables (same layout as the table), zero between sweeps
-    void *d_dssum = nullptr;
+    rs::DevBuf<char> d_dregrets;      // deal batches: delta tables (same layout as the table), zero between sweeps
+    rs::DevBuf<char> d_dssum;
     std::vector<struct rs_solver *> solvers;   // live solvers built on this table: released before the table goes away
     uint64_t epoch = 0;                        // counts the calls that wrote regrets / strategy sums (uploads, fills, sweeps, discounts, ...): a deal solver's KEPT shadow
                                                // records (rs_solver.cpp setup_table_shadow) are rebuilt when the table moved on without them
-    void *d_query = nullptr;          // scratch of the single-info-set strategy queries (rs_get_strategy)
-    uint32_t *d_err_sink = nullptr;   // error word for card kernels whose caller passed none (rs_deals_sample)
-    void *d_km_scratch = nullptr;     // staged k-means centers (rs_kmeans_predict), grow-only
-    size_t km_scratch_bytes = 0;
-    rs::NodeJob *d_job = nullptr;     // one device job slot for the per-node ABI calls (stream-ordered reuse)
+    rs::DevBuf<char> d_query;         // scratch of the single-info-set strategy queries (rs_get_strategy)
+    rs::DevBuf<uint32_t> d_err_sink;  // error word for card kernels whose caller passed none (rs_deals_sample)
+    rs::DevBuf<char> d_km_scratch;    // staged k-means centers (rs_kmeans_predict), grow-only
+    rs::DevBuf<rs::NodeJob> d_job;    // one device job slot for the per-node ABI calls (stream-ordered reuse)
     rs::Profile prof;
 
     bool tiled(int node) const { return tile[size_t(node)] != pitch[size_t(node)]; }
@@ -482,7 +482,7 @@ int comm_allreduce_i32(struct rs_comm *c, rs_table *t, void *d_buf, size_t n);
 int comm_allgather_u32(struct rs_comm *c, rs_table *t, const void *d_send, void *d_recv, size_t n);
 // ordered deal sweeps: the caller sorts the per-deal records of every batch itself, ahead of the sweep (true: accepted -- an ordered solver on one GPU that has not swept yet)
 bool solver_order_ahead(struct rs_solver *s, bool on, int (*before_sweep)(void *ctx, int traverser), void *ctx);
-int solver_order_on(struct rs_solver *s, int traverser, hipStream_t stream, const uint32_t *const cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS], const float *leaf, const uint8_t *prune);
+int solver_order_on(struct rs_solver *s, int traverser, hipStream_t stream, const DevBuf<uint32_t> (&cluster)[RS_MAX_ROUNDS][RS_MAX_PLAYERS], const float *leaf, const uint8_t *prune);
 int solver_discount_primary(struct rs_solver *s, float d);   // rs_discount while on: the kept records and the table WITHOUT their nodes
 // profiling hooks used around launches
 void prof_begin(rs_table *t, int kind, double bytes);

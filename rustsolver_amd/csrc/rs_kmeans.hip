@@ -631,21 +631,15 @@ int check_args(const char *who, const rs_table *t, int dist, const void *d_datas
 }
 
 // Centers are staged in a scratch buffer owned by the table.  It only ever grows, and it is rewritten only after the stream has drained, so a
-// sweep still in flight never sees the next call's centers.  (Stream-ordered pool allocations -- hipMallocAsync / hipFreeAsync per call -- were
+// sweep still in flight never sees the next call's centers.  (Stream-ordered pool allocations per call -- the asynchronous malloc / free pair -- were
 // tried first and produced sporadically wrong clusters: the staged centers were not reliably in place when the kernel ran.)
 int stage_centers(rs_table *t, const std::vector<float> &prepared, const std::vector<unsigned char> &zero, float **d_centers, unsigned char **d_zero) {
     const size_t c_bytes = round_up(prepared.size() * sizeof(float), 256), need = c_bytes + round_up(zero.size(), 256);
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
-    if (need > t->km_scratch_bytes) {
-        if (t->d_km_scratch) RS_HIP(hipFree(t->d_km_scratch), "hipFree(k-means scratch)");
-        t->d_km_scratch = nullptr;
-        t->km_scratch_bytes = 0;
-        RS_HIP(hipMalloc(&t->d_km_scratch, need), "hipMalloc(k-means scratch)");
-        t->km_scratch_bytes = need;
-    }
-    *d_centers = reinterpret_cast<float *>(t->d_km_scratch);
-    *d_zero = reinterpret_cast<unsigned char *>((char *)t->d_km_scratch + c_bytes);
+    if (need > t->d_km_scratch.bytes()) RS_HIP(t->d_km_scratch.alloc(need), "k-means scratch");
+    *d_centers = reinterpret_cast<float *>(t->d_km_scratch.get());
+    *d_zero = reinterpret_cast<unsigned char *>(t->d_km_scratch + c_bytes);
     RS_HIP(hipMemcpy(*d_centers, prepared.data(), prepared.size() * sizeof(float), hipMemcpyHostToDevice), "k-means centers upload");
     RS_HIP(hipMemcpy(*d_zero, zero.data(), zero.size(), hipMemcpyHostToDevice), "k-means centers upload");
     return RS_OK;
@@ -789,12 +783,10 @@ int rs_member_lists(rs_table *t, const uint32_t *d_keys, size_t n, uint32_t k, u
     if (!t || !d_start || (n && (!d_keys || !d_members))) return fail(RS_ERR_INVALID, "rs_member_lists: NULL argument");
     if (k == 0 || n > 0xffffffffull) return fail(RS_ERR_INVALID, "rs_member_lists: k must be at least 1 and n below 2^32");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    uint32_t *d_scratch = nullptr;
-    RS_HIP(hipMalloc((void **)&d_scratch, std::max<size_t>(member_lists_scratch_words(n, k), 1) * 4), "rs_member_lists: scratch");
-    hipError_t e = launch_member_lists(d_keys, n, k, d_scratch, d_start, d_members, t->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    (void)hipFree(d_scratch);
-    RS_HIP(e, "rs_member_lists");
+    DevBuf<uint32_t> d_scratch;
+    RS_HIP(d_scratch.alloc(member_lists_scratch_words(n, k)), "rs_member_lists: scratch");
+    RS_HIP(launch_member_lists(d_keys, n, k, d_scratch, d_start, d_members, t->stream), "rs_member_lists");
+    RS_HIP(hipStreamSynchronize(t->stream), "rs_member_lists");
     return RS_OK;
 }
 
@@ -804,32 +796,25 @@ int rs_member_lists(rs_table *t, const uint32_t *d_keys, size_t n, uint32_t k, u
 namespace {
 
 struct KmDevice {   // per-call device workspace of the training loops
-    float *raw = nullptr, *s = nullptr, *mv = nullptr, *sums = nullptr, *counts = nullptr, *sq = nullptr;
-    unsigned *members = nullptr, *tile_hist = nullptr, *total = nullptr, *start = nullptr;   // the member lists of a round (stable counting sort by cluster)
-    float *staged = nullptr;                                                                 // the members' histograms per cluster, bin-major
-    size_t n_tiles = 0, staged_floats = 0;
-    ~KmDevice() {
-        for (float *q : {raw, s, mv, sums, counts, sq})
-            if (q) (void)hipFree(q);
-        for (unsigned *q : {members, tile_hist, total, start})
-            if (q) (void)hipFree(q);
-        if (staged) (void)hipFree(staged);
-    }
+    DevBuf<float> raw, s, mv, sums, counts, sq;
+    DevBuf<unsigned> members, tile_hist, total, start;   // the member lists of a round (stable counting sort by cluster)
+    DevBuf<float> staged;                               // the members' histograms per cluster, bin-major
+    size_t n_tiles = 0;
     int alloc_lists(size_t n, int k) {
         n_tiles = (n + kKmTile - 1) / kKmTile;
-        hipError_t e = hipMalloc((void **)&members, std::max<size_t>(n, 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&tile_hist, std::max<size_t>(n_tiles * size_t(k), 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&total, size_t(k) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&start, (size_t(k) + 1) * 4);
+        hipError_t e = members.alloc(n);
+        if (e == hipSuccess) e = tile_hist.alloc(n_tiles * size_t(k));
+        if (e == hipSuccess) e = total.alloc(size_t(k));
+        if (e == hipSuccess) e = start.alloc(size_t(k) + 1);
         return e == hipSuccess ? RS_OK : hip_fail(e, "k-means member lists");
     }
     int alloc(int k, int n_bins) {
-        hipError_t e = hipMalloc((void **)&raw, size_t(k) * n_bins * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&s, size_t(k) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&mv, size_t(k) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&sums, size_t(k) * n_bins * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&counts, size_t(k) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&sq, size_t(k) * 4);
+        hipError_t e = raw.alloc(size_t(k) * n_bins);
+        if (e == hipSuccess) e = s.alloc(size_t(k));
+        if (e == hipSuccess) e = mv.alloc(size_t(k));
+        if (e == hipSuccess) e = sums.alloc(size_t(k) * n_bins);
+        if (e == hipSuccess) e = counts.alloc(size_t(k));
+        if (e == hipSuccess) e = sq.alloc(size_t(k));
         return e == hipSuccess ? RS_OK : hip_fail(e, "k-means workspace");
     }
 };
@@ -879,7 +864,7 @@ int reassign_device(rs_table *t, int dist, const float *d_dataset, const uint32_
                     float *d_bounds) {
     // the centers were staged by init_s_device just before (same stream, same scratch): reuse them
     const int nb = padded_bins(n_bins);
-    float *d_centers = reinterpret_cast<float *>(t->d_km_scratch);
+    float *d_centers = reinterpret_cast<float *>(t->d_km_scratch.get());
     unsigned char *d_zero = reinterpret_cast<unsigned char *>((char *)t->d_km_scratch + round_up(size_t(k) * nb * sizeof(float), 256));
     if (n == 0) return RS_OK;
     const dim3 grid = km_grid(n), block(kKmBlock);
@@ -932,12 +917,7 @@ int update_step(rs_table *t, int dist, const float *d_dataset, const uint32_t *d
     RS_HIP(hipGetLastError(), "k-means member lists");
     const int rows = n_bins + (growbatch ? 1 : 0);
     if (rows > 64) return fail(RS_ERR_UNSUPPORTED, "k-means training loops: at most 63 bins (one lane of a wave per bin)");
-    if (w.staged_floats < n * size_t(rows) + 4) {
-        if (w.staged) (void)hipFree(w.staged);
-        w.staged = nullptr;
-        w.staged_floats = n * size_t(rows) + 4;
-        RS_HIP(hipMalloc((void **)&w.staged, w.staged_floats * 4), "k-means staging buffer");
-    }
+    if (w.staged.bytes() < (n * size_t(rows) + 4) * 4) RS_HIP(w.staged.alloc(n * size_t(rows) + 4), "k-means staging buffer");
     hipLaunchKernelGGL(k_kmeans_stage, km_grid(n), dim3(kKmBlock), 0, t->stream, d_dataset, (const unsigned *)d_order, (const unsigned *)d_clusters, (const unsigned *)w.members,
                        (const unsigned *)w.start, (const float *)d_bounds, n, n_bins, k, rows, w.staged);
     hipLaunchKernelGGL(k_kmeans_center_sums, dim3((unsigned)k), dim3(64), 0, t->stream, (const float *)w.staged, (const unsigned *)w.start, n_bins, rows, w.sums, w.counts,
@@ -1045,12 +1025,11 @@ int rs_kmeans_reassign(rs_table *t, int dist, const float *d_dataset, const uint
     float *d_centers = nullptr;
     unsigned char *d_zero = nullptr;
     if (int rc = stage_for(t, dist, centers, n_centers, n_bins, nb, &d_centers, &d_zero)) return rc;
-    float *d_s = nullptr;
-    RS_HIP(hipMalloc((void **)&d_s, size_t(n_centers) * 4), "hipMalloc(s)");
+    DevBuf<float> d_s;
+    RS_HIP(d_s.alloc(size_t(n_centers)), "s");
     hipError_t e = hipMemcpy(d_s, s, size_t(n_centers) * 4, hipMemcpyHostToDevice);
     int rc = e == hipSuccess ? reassign_device(t, dist, d_dataset, d_order, n, n_centers, n_bins, d_s, d_clusters, d_bounds) : hip_fail(e, "s upload");
     if (rc == RS_OK && (e = hipStreamSynchronize(t->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-    (void)hipFree(d_s);
     return rc;
 }
 
@@ -1064,9 +1043,9 @@ int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t 
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     KmDevice w;
     if (int rc = w.alloc(n_centers, n_bins)) return rc;
-    float *own_bounds = nullptr;
+    DevBuf<float> own_bounds;
     if (!d_bounds) {
-        RS_HIP(hipMalloc((void **)&own_bounds, n * 8), "hipMalloc(bounds)");
+        RS_HIP(own_bounds.alloc(n * 2), "bounds");
         d_bounds = own_bounds;
     }
     std::vector<float> c(centers, centers + size_t(n_centers) * n_bins), mv, counts, sq;
@@ -1089,7 +1068,6 @@ int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t 
         *inertia = sum / float(n);
     }
     if (rc == RS_OK) std::memcpy(centers, c.data(), c.size() * 4);
-    if (own_bounds) (void)hipFree(own_bounds);
     return rc;
 }
 

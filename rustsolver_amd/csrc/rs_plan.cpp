@@ -614,7 +614,7 @@ int PlanBuilder::add_jit_job(int id, bool down, const std::vector<int> &sparse_s
                     rj.tpitch = tpn;
                     rj.n_clusters = ncl;
                     const int32_t *src = s->d_drows + plan.drow_off[size_t(an.index)] + size_t(arr) * A * bp;
-                    int32_t *dst = static_cast<int32_t *>(arr == 0 ? t->d_dregrets : t->d_dssum) + t->cell_off[an.index];
+                    int32_t *dst = reinterpret_cast<int32_t *>((arr == 0 ? t->d_dregrets : t->d_dssum).get()) + t->cell_off[an.index];
                     if (ncl > kRowSumMaxCells) {   // no LDS tile holds a row: its deltas go straight into the table (k_row_apply)
                         rj.rows = src;
                         rj.dst = static_cast<int32_t *>(arr == 0 ? t->regrets_ptr(an.index) : t->ssum_ptr(an.index));
@@ -706,10 +706,9 @@ int PlanBuilder::emit() {
             plan.frow_off[i] = floats;
             floats += size_t(2) * d.n_actions * s->pitch[0];
         }
-        hipError_t ef = hipMalloc((void **)&plan.d_frows, std::max<size_t>(floats, 64) * sizeof(float));
-        if (ef == hipSuccess) ef = hipMemsetAsync(plan.d_frows, 0, std::max<size_t>(floats, 64) * sizeof(float), t->stream);
+        hipError_t ef = plan.d_frows.alloc(std::max<size_t>(floats, 64), &s->dev_bytes);
+        if (ef == hipSuccess) ef = hipMemsetAsync(plan.d_frows, 0, plan.d_frows.bytes(), t->stream);
         if (ef != hipSuccess) return hip_fail(ef, "rs_solver_create_deals: per-deal delta rows");
-        plan.aux_bytes += floats * sizeof(float);
     }
     if (s->rows) {   // delta rows: one buffer for both traversers' sweeps, offsets per traverser node of an eligible round
         plan.drow_off.assign(t->nodes.size(), SIZE_MAX);
@@ -722,9 +721,8 @@ int PlanBuilder::emit() {
         }
         if (!s->d_drows) {
             const size_t need = std::max<size_t>(std::max(drows_ints(s, 0), drows_ints(s, 1)), 64);
-            hipError_t ed = hipMalloc((void **)&s->d_drows, need * sizeof(int32_t));
+            hipError_t ed = s->d_drows.alloc(need, &s->dev_bytes);
             if (ed != hipSuccess) return hip_fail(ed, "rs_solver_create_deals: delta rows");
-            s->other_bytes += need * sizeof(int32_t);
         }
     }
     const bool prune = (s->params.mode & RS_UPD_PRUNE) != 0;

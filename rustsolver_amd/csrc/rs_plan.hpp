@@ -60,7 +60,7 @@ struct JitLaunch {
     size_t stride = 0;
     int n_jobs = 0;
     uint32_t max_n_vec = 0;
-    unsigned char *d_blob = nullptr;
+    DevBuf<unsigned char> d_blob;
     double bytes = 0.0;
     int threads = 256;
     size_t lds_bytes = 0;
@@ -69,63 +69,104 @@ struct JitLaunch {
     bool rows = false;                  // delta rows: no LDS, no barrier, 256-thread workgroups, many per CU
     bool staged = false;                // staged rows: lds_bytes is the waves' staging area, not delta tiles (grid as for the forms without LDS)
     bool worklist = false;              // list-walking kernels with LDS tiles: a 1-D grid of resident workgroups pulls (job, trip) items; k_worklist runs right before
-    uint32_t *d_wl = nullptr;           // [2 + n_jobs + 1]
+    DevBuf<uint32_t> d_wl;              // [2 + n_jobs + 1]
     uint32_t off_count = 0, deals_per_trip = 0;
 };
 
+// every device buffer of a plan is charged to its solver's ledger (rs_solver.dev_bytes)
 struct Plan {
     std::vector<ChanceJob> chance_jobs;   // L_EXPAND / L_REDUCE launches index into this (first_job, n_jobs)
-    ChanceJob *d_chance_jobs = nullptr;
+    DevBuf<ChanceJob> d_chance_jobs;
     std::vector<JitLaunch> jit;
     std::vector<NodeJob> jobs;
-    NodeJob *d_jobs = nullptr;
+    DevBuf<NodeJob> d_jobs;
     std::vector<Launch> launches;
     // sparse deal sweeps: per subtree root the list of live deals (reach not NaN), rebuilt by k_compact_live after the top-down pass
-    uint32_t *d_lists = nullptr;        // [n_compact][pitch]
-    float *d_rlists = nullptr;          // position-indexed rows: the reach of every list entry, same shape as d_lists
-    uint32_t *d_plists = nullptr;       // position-indexed rows: where the parent subtree reads every list entry's utility, same shape as d_lists
-    float *d_hrows = nullptr;           // hand-off rows of the round subtrees with a reach-down kernel: [opponent nodes handed + 1][batch pitch + stagger] floats per root
-    uint32_t *d_klists = nullptr;       // delta rows: the traverser's cluster of every list entry (the key row of k_row_sums), same shape as d_lists
+    DevBuf<uint32_t> d_lists;           // [n_compact][pitch]
+    DevBuf<float> d_rlists;             // position-indexed rows: the reach of every list entry, same shape as d_lists
+    DevBuf<uint32_t> d_plists;          // position-indexed rows: where the parent subtree reads every list entry's utility, same shape as d_lists
+    DevBuf<float> d_hrows;              // hand-off rows of the round subtrees with a reach-down kernel: [opponent nodes handed + 1][batch pitch + stagger] floats per root
+    DevBuf<uint32_t> d_klists;          // delta rows: the traverser's cluster of every list entry (the key row of k_row_sums), same shape as d_lists
     std::vector<size_t> drow_off;       // delta rows: per table node the int offset of its [2A][batch pitch] rows inside the solver's d_drows (SIZE_MAX: none)
     std::vector<RowSumJob> row_jobs;
-    RowSumJob *d_row_jobs = nullptr;
+    DevBuf<RowSumJob> d_row_jobs;
     uint32_t row_max_cells = 0;
-    ApplyJob *d_apply_jobs = nullptr;   // deal sweeps: the cell ranges of the traverser's own nodes (where its deltas are)
+    DevBuf<ApplyJob> d_apply_jobs;      // deal sweeps: the cell ranges of the traverser's own nodes (where its deltas are)
     // deal sweeps on f32 tables: per-deal delta rows of every traverser node, the traverser's deals listed per cluster and round (rebuilt every sweep), the ordered apply
-    float *d_frows = nullptr;
+    DevBuf<float> d_frows;
     std::vector<size_t> frow_off;       // per table node: float offset of its [2A][pitch] rows inside d_frows (SIZE_MAX: not this traverser's)
-    ApplyF32Job *d_f32_jobs = nullptr;
+    DevBuf<ApplyF32Job> d_f32_jobs;
     int n_f32_jobs = 0;
     uint32_t f32_max_clusters = 0;
-    uint32_t *d_member_start[RS_MAX_ROUNDS] = {nullptr, nullptr, nullptr}, *d_members[RS_MAX_ROUNDS] = {nullptr, nullptr, nullptr};
-    uint32_t *d_member_scratch = nullptr;   // tile histograms, then totals
+    DevBuf<uint32_t> d_member_start[RS_MAX_ROUNDS], d_members[RS_MAX_ROUNDS];
+    DevBuf<uint32_t> d_member_scratch;   // tile histograms, then totals
     int n_apply_jobs = 0;
     size_t apply_max_vec = 0;
     bool apply_whole = false;           // the apply pass runs over the whole table (cell ranges that are no multiple of four: never with 64-lane padded pitches)
-    size_t *d_pack_off = nullptr;       // data-parallel sweeps: where every apply job's cells start in the packed buffer the ranks sum (vectors of 4 cells)
+    DevBuf<size_t> d_pack_off;          // data-parallel sweeps: where every apply job's cells start in the packed buffer the ranks sum (vectors of 4 cells)
     size_t pack_vec = 0;                // ... and its length per array
-    size_t aux_bytes = 0;               // device memory of this plan beside the arena: live-deal lists and the reach rows of the round subtrees
     size_t n_count_words = 0;           // u32 words of d_counts (all counters, kCountStride apart)
     bool counts_zeroed_by_shadow = false;   // the sweep opens with a k_build_shadow launch, which zeroes d_counts too (else: a memset in front of every compaction)
-    uint32_t *d_counts = nullptr;       // [n_compact]
-    CompactJob *d_compact_jobs = nullptr;
+    DevBuf<uint32_t> d_counts;          // [n_compact]
+    DevBuf<CompactJob> d_compact_jobs;
     std::vector<CompactJob> compact_jobs;
     std::vector<size_t> count_off;      // per compact job: index of its first counter (a job has one per cluster range)
     std::vector<int> compact_round;     // per compact job: betting round of its root
     std::vector<rs::CompactGroup> compact_groups;   // runs of sibling jobs (same source, no cluster ranges), in job order
-    rs::CompactGroup *d_compact_groups = nullptr;
+    DevBuf<rs::CompactGroup> d_compact_groups;
     int dense_roots[RS_MAX_ROUNDS] = {0, 0, 0};   // round subtrees that walk the whole batch, per round
     uint32_t compact_max_lanes = 0;
-    uint32_t *d_bmask = nullptr;        // liveness masks of the round subtrees' reach-down kernels (CompactJob.mask), one row per parent root
-    float *d_reach_nan = nullptr;       // round subtrees: reach buffers of every root but the first, all NaN at the start of a sweep
+    DevBuf<uint32_t> d_bmask;           // liveness masks of the round subtrees' reach-down kernels (CompactJob.mask), one row per parent root
+    DevBuf<float> d_reach_nan;          // round subtrees: reach buffers of every root but the first, all NaN at the start of a sweep
     size_t reach_nan_bytes = 0;
     size_t split = 0;                   // sharded sweeps: launches [0, split) = phase 0, [split, end) = phase 1
     int n_boundary = 0;                 // chance nodes entering the sharded round
     size_t arena_bytes = 0;
     const float *root_util = nullptr;   // inside the arena
     size_t root_lanes = 0;
-    hipGraphExec_t graph_exec = nullptr;
-    hipGraph_t graph = nullptr;
+    DevGraph graph;                     // last: destroyed before the buffers it launches on, the executable first
+    DevGraphExec graph_exec;
+};
+
+// The device buffers, streams and events of a solver beside its plans (rs_solver derives from it: solver_release_device drops them all in one assignment).
+// Owners only: the pointers that alias them (rs_solver.d_arec, d_attr) stay plain pointers.
+struct SolverDevice {
+    static constexpr int kAux = 3;      // auxiliary streams of the round subtrees (why three: rs_solver)
+    DevStream aux[kAux];
+    DevEvent ev_fork, ev_join[kAux];
+    DevBuf<char> d_arena;
+    DevBuf<float> d_exchange;           // sharded sweeps: [world][n_boundary][slot_lanes]
+    DevBuf<uint64_t> d_seed_state;      // RS_OPP_SAMPLE: {base seed, call index, seed of the current sweep}
+    // the AoS shadow of the table a deal sweep gathers from, its kept records and their jobs (rs_solver.cpp setup_table_shadow)
+    DevBuf<int32_t> d_shadow;
+    DevBuf<ShadowJob> d_shadow_jobs;    // the jobs of traverser 0's sweep, then those of traverser 1's (the same nodes, different record widths)
+    DevBuf<ShadowJob> d_kept_jobs;
+    DevBuf<uint32_t> d_kept_primary;    // device flag k_row_apply reads: the kept records alone take the additions (solver_kept_primary)
+    DevBuf<DiscountJob> d_disc_jobs;    // the table without the kept nodes, as stretches of consecutive nodes
+    // per-deal records (rs_solver.cpp setup_deal_records): packed per round, or sorted per traverser
+    DevBuf<char> d_attr_buf[RS_MAX_ROUNDS];
+    DevBuf<PackJob> d_pack_jobs;
+    DevBuf<char> d_arec_p[2];           // one set of records per traverser (round 5): traverser 1's can be sorted while traverser 0's sweep still reads its own
+    DevBuf<uint32_t> d_order_tot;       // [2 traversers][2][n_bins]: counts and cursors of the counting sorts
+    DevBuf<int32_t> d_drows;            // delta rows (rs_solver.rows)
+    // data-parallel deal sweeps on i32 tables (solver_exchange_deltas)
+    DevBuf<int32_t> d_packed;           // [2][max pack_vec * 4] the traverser's delta cells of the rounds that sum through the delta tables, one ncclInt32 all-reduce
+    DevBuf<uint32_t> d_item_count;      // [1 + world]: this rank's cursor, then every rank's count
+    DevBuf<uint32_t> d_items;           // [3 * item_cap] this rank's (job, row, cluster, delta) items of the rounds whose rows go straight into the table
+    DevBuf<uint32_t> d_items_all;       // [world][3 * item_cap]
+    // data-parallel deal sweeps on float tables (solver_exchange_float): fixed at rs_solver_attach_comm ...
+    DevBuf<FdpJob> d_fdp_jobs[2];       // per traverser, in the order of its plan's ApplyF32Jobs
+    DevBuf<uint32_t> d_fdp_scan;        // [2][fdp_m + 1]: item flags, payload words, scanned in place
+    DevBuf<uint32_t> d_fdp_parts;       // scan partial sums
+    DevBuf<uint32_t> d_fdp_count;       // [2 + 2 * world]: this rank's (items, words), then every rank's
+    DevBuf<uint32_t> d_fdp_start;       // [max fdp_keys + 2]
+    // ... and grown on demand (rank-invariant: from the gathered counts), all together
+    struct FdpItems {
+        DevBuf<uint32_t> key, off, key_all, off_all, members, scratch;
+        DevBuf<float> pay, pay_all;
+        uint32_t cap_items = 0;         // what they hold (0: nothing)
+        size_t cap_words = 0;
+    } fdp;
 };
 
 
@@ -138,7 +179,9 @@ using rs::RowSumJob;
 using rs::Plan;
 using rs::ShadowJob;
 
-struct rs_solver {
+// Its device state lives in the SolverDevice base, charged to dev_bytes; solver_release_device empties it before the object is deleted.
+struct rs_solver : rs::SolverDevice {
+    size_t dev_bytes = 0;               // the ledger of every device allocation of the solver and its plans (rs_solver_workspace_bytes)
     rs_table *table = nullptr;
     rs_tree tree;
     rs_solver_params params{};
@@ -146,9 +189,7 @@ struct rs_solver {
     int lds_limit = 64 * 1024;          // LDS bytes the device gives ONE workgroup (MI355X: 160 KiB), queried at creation
     std::vector<rs_leaf_desc> leaves[2];
     Plan plan[2];
-    char *d_arena = nullptr;
     size_t arena_bytes = 0;
-    size_t other_bytes = 0;             // every other device allocation of the solver: table shadow, packed / ordered per-deal records, job blobs, work lists, counters, exchange buffer
     uint32_t n_boards[RS_MAX_ROUNDS] = {0, 0, 0};
     uint32_t n_clusters = 0;
     size_t pitch[RS_MAX_ROUNDS] = {0, 0, 0};
@@ -157,7 +198,6 @@ struct rs_solver {
     bool sharded = false;
     uint32_t shard_lo[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // first global board of every rank at shard_round, then the total
     size_t slot_lanes = 0;              // floats per (rank, boundary node) in the exchange buffer
-    float *d_exchange = nullptr;        // [world][n_boundary][slot_lanes]
     size_t exchange_floats_per_rank = 0;
     rs_comm *comm = nullptr;
     int n_cus = 256;                    // multiprocessors of the device (grid of the persistent deal kernels)
@@ -165,12 +205,8 @@ struct rs_solver {
     // Three: with the table's own stream that makes four, one per hardware queue of the device (GPU_MAX_HW_QUEUES defaults to 4) -- a fifth stream shares a queue with another
     // and which two collide differs from process to process: with four auxiliary streams a 64 K-deal batch took 0.81 or 0.97 ms depending on the run, with three 0.76-0.77 in
     // every run (16 K deals 0.95 -> 0.82, 256 K 1.40 -> 1.30, the 2 GB lossless table 1.43 -> 1.36; 1 M and 4 M deals unchanged).  (8: 4 M deals 6.95 -> 7.24 ms, 64 K 0.91 -> 1.10)
-    static constexpr int kAux = 3;
-    hipStream_t aux[kAux] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[kAux] = {};
-    // deal sweeps through tree-specialised kernels read the table from an AoS shadow rebuilt at the start of every sweep
-    int32_t *d_shadow = nullptr;
-    ShadowJob *d_shadow_jobs = nullptr;   // the jobs of traverser 0's sweep, then those of traverser 1's (the same nodes, different record widths)
+    // (SolverDevice::kAux, aux, ev_fork, ev_join)
+    // deal sweeps through tree-specialised kernels read the table from an AoS shadow rebuilt at the start of every sweep (d_shadow, d_shadow_jobs)
     int n_shadow_jobs = 0;                // per traverser
     std::vector<size_t> shadow_off_p[2];  // per traverser and table node, in ints (SIZE_MAX: no shadow): where cluster 0's record of the node starts
     std::vector<uint32_t> shadow_stride_p[2];   // ints between two clusters' records of the node: the ROW of its round subtree and role (rs_solver.cpp setup_table_shadow)
@@ -186,19 +222,15 @@ struct rs_solver {
     // strategy sums}, no strategies) at the front of d_shadow, shared by both traversers' sweeps, built when the table has moved on without them (rs_table.epoch), and taking
     // every addition k_row_apply makes to the table and every discount sweep (solver_table_discounted)
     size_t kept_ints = 0;                 // d_shadow[0 .. kept_ints)
-    ShadowJob *d_kept_jobs = nullptr;
     int n_kept_jobs = 0;
     uint32_t kept_max_clusters = 0;
     uint64_t kept_epoch = ~uint64_t(0);   // the table epoch the kept records are in step with
     std::vector<char> kept_node;          // per table node
-    uint32_t *d_kept_primary = nullptr;   // device flag k_row_apply reads: the kept records alone take the additions (solver_kept_primary)
-    bool primary = false;
-    rs::DiscountJob *d_disc_jobs = nullptr;   // the table without the kept nodes, as stretches of consecutive nodes
+    bool primary = false;                 // d_kept_primary is set
     int n_disc_jobs = 0;
     size_t disc_max_vec = 0;
     // sparse deal sweeps fetch the per-deal inputs of a round (both cluster ids, leaf value, prune flag) as ONE packed 16-byte record per live deal
-    void *d_attr[RS_MAX_ROUNDS] = {nullptr, nullptr, nullptr};
-    PackJob *d_pack_jobs = nullptr;
+    void *d_attr[RS_MAX_ROUNDS] = {nullptr, nullptr, nullptr};   // d_attr_buf[r], or d_arec
     int n_pack_jobs = 0;
     unsigned attr_used = 0;             // bit r: some generated kernel reads the packed records of round r (only the list-walking forms do)
     // ordered sweeps (rs_kernel_forms.deal_order): traverser p's sweep walks the batch sorted by p's cluster id on the last round; d_arec holds the 32-byte per-deal
@@ -206,45 +238,27 @@ struct rs_solver {
     bool ordered = false;
     int order_round = 0;                // the last betting round of the tree
     void *d_arec = nullptr;             // == d_arec_p[0]
-    void *d_arec_p[2] = {nullptr, nullptr};   // one set of records per traverser (round 5): traverser 1's can be sorted while traverser 0's sweep still reads its own
-    uint32_t *d_order_tot = nullptr;    // [2 traversers][2][n_bins]: counts and cursors of the counting sorts
     OrderJob order_job[2];              // per traverser
     // The records depend on the deals alone, not on the table: a caller that knows the next batch early (rs_deal_trainer deals ahead on a second stream) sorts them itself,
     // beside the sweeps (solver_order_on), and the plans' own L_ORDER launches do nothing.  Set before the first sweep (a captured graph keeps what it was captured with).
     bool order_ahead = false;
     // data-parallel deal sweeps (a communicator attached): what the ranks exchange between sweep and apply (solver_exchange_deltas)
-    int32_t *d_packed = nullptr;        // [2][max pack_vec * 4] the traverser's delta cells of the rounds that sum through the delta tables, one ncclInt32 all-reduce
-    uint32_t *d_items = nullptr;        // [3 * item_cap] this rank's (job, row, cluster, delta) items of the rounds whose rows go straight into the table
-    uint32_t *d_items_all = nullptr;    // [world][3 * item_cap]
-    uint32_t *d_item_count = nullptr;   // [1 + world]: this rank's cursor, then every rank's count
-    uint32_t item_cap = 0, items_world = 0;   // items_world: ranks d_items_all and d_item_count were sized for
+    // (d_packed, d_item_count, d_items, d_items_all)
+    uint32_t item_cap = 0, items_world = 0;   // items_world: ranks d_items_all and d_item_count were sized for; both raised once every buffer they size exists
     uint64_t dp_bytes_total = 0, dp_sweeps = 0;
     uint64_t dp_bytes_last = 0;         // bytes this rank handed to the collectives in its last sweep (all-reduce buffer + every rank's items)
     // data-parallel deal sweeps on FLOAT tables (solver_exchange_float): per-deal delta vectors travel as items, every rank sums the union in global deal order
-    rs::FdpJob *d_fdp_jobs[2] = {nullptr, nullptr};   // per traverser, in the order of its plan's ApplyF32Jobs
     uint32_t fdp_keys[2] = {0, 0};                // per traverser: sum of its nodes' clusters (the union sort's keys are below it)
-    uint32_t *d_fdp_scan = nullptr;               // [2][fdp_m + 1]: item flags, payload words, scanned in place
-    uint32_t *d_fdp_parts = nullptr;              // scan partial sums
-    uint32_t *d_fdp_count = nullptr;              // [2 + 2 * world]: this rank's (items, words), then every rank's
-    uint32_t *d_fdp_start = nullptr;              // [max fdp_keys + 2]
     size_t fdp_m = 0;                             // max over traversers of n_jobs * n_deals
-    uint32_t fdp_world = 0;
-    // grown on demand (rank-invariant: from the gathered counts); fdp_cap_items == 0 after a failed grow, and every later sweep fails
-    uint32_t *d_fdp_key = nullptr, *d_fdp_off = nullptr, *d_fdp_key_all = nullptr, *d_fdp_off_all = nullptr, *d_fdp_members = nullptr, *d_fdp_scratch = nullptr;
-    float *d_fdp_pay = nullptr, *d_fdp_pay_all = nullptr;
-    uint32_t fdp_cap_items = 0;
-    size_t fdp_cap_words = 0, fdp_bytes = 0;
-    bool fdp_broken = false;
+    uint32_t fdp_world = 0;                       // ranks d_fdp_count and the item buffers were sized for
     int (*before_sweep)(void *ctx, int traverser) = nullptr;   // ... and is asked in front of every sweep whether the records are the live batch's (rs_iterate, rs_iterate_phase 0)
     void *before_sweep_ctx = nullptr;
     // delta rows (rs_kernel_forms.delta_rows): one buffer for both traversers' sweeps (they never overlap), [2A][batch pitch] i32 per traverser node of an eligible round
     bool rows = false;
     bool direct_rows = false;           // rounds whose traverser nodes outgrow the summing pass's LDS tile store delta rows too, added straight into the table (k_row_apply)
     int first_round = 0;                // betting round of the first action node: its subtree walks the whole batch and keeps its tiles unless RS_JIT_ROWS = 2
-    int32_t *d_drows = nullptr;
     bool deal_mode = false;             // lanes are deals (rs_solver_create_deals)
     rs_deal_batch deals{};
-    uint64_t *d_seed_state = nullptr;   // RS_OPP_SAMPLE: {base seed, call index, seed of the current sweep}
     const uint64_t *d_seed() const { return d_seed_state ? d_seed_state + 2 : nullptr; }
 };
 

@@ -150,19 +150,19 @@ int PlanBuilder::emit_deal_lists() {
             list_elems += size_t(pr.first) * s->pitch[lane_round[ids[k]]] + kRowStagger;
             n_counts += pr.first;
         }
-        hipError_t ea = hipMalloc((void **)&plan.d_lists, list_elems * sizeof(uint32_t));
-        if (ea == hipSuccess && pos_rows) ea = hipMalloc((void **)&plan.d_rlists, list_elems * sizeof(float));
-        if (ea == hipSuccess && pos_rows) ea = hipMalloc((void **)&plan.d_plists, list_elems * sizeof(uint32_t));
+        size_t *led = &s->dev_bytes;
+        hipError_t ea = plan.d_lists.alloc(list_elems, led);
+        if (ea == hipSuccess && pos_rows) ea = plan.d_rlists.alloc(list_elems, led);
+        if (ea == hipSuccess && pos_rows) ea = plan.d_plists.alloc(list_elems, led);
         bool any_rows = false;
         for (int id : ids) any_rows = any_rows || rows_root(id);
-        if (ea == hipSuccess && any_rows) ea = hipMalloc((void **)&plan.d_klists, list_elems * sizeof(uint32_t));
-        plan.aux_bytes += list_elems * sizeof(uint32_t) * (1 + (pos_rows ? 2 : 0) + (any_rows ? 1 : 0));
+        if (ea == hipSuccess && any_rows) ea = plan.d_klists.alloc(list_elems, led);
         plan.n_count_words = n_counts * kCountStride;
-        if (ea == hipSuccess) ea = hipMalloc((void **)&plan.d_counts, n_counts * kCountStride * sizeof(uint32_t));
+        if (ea == hipSuccess) ea = plan.d_counts.alloc(n_counts * kCountStride, led);
         if (ea == hipSuccess) ea = hipMemsetAsync(plan.d_counts, 0, n_counts * kCountStride * sizeof(uint32_t), t->stream);
         for (const Launch &L0 : plan.launches) plan.counts_zeroed_by_shadow = plan.counts_zeroed_by_shadow || L0.kind == L_SHADOW;   // pushed before any compaction (rs_plan.cpp)
         plan.counts_zeroed_by_shadow = plan.counts_zeroed_by_shadow && plan.n_count_words < (size_t(1) << 32);
-        if (ea == hipSuccess) ea = hipMalloc((void **)&plan.d_compact_jobs, n_sparse * sizeof(CompactJob));
+        if (ea == hipSuccess) ea = plan.d_compact_jobs.alloc(n_sparse, led);
         if (ea != hipSuccess) return hip_fail(ea, "rs_solver_create: live-deal lists");
         plan.compact_jobs.resize(n_sparse);
         plan.count_off.assign(n_sparse + 1, 0);
@@ -184,7 +184,7 @@ int PlanBuilder::emit_deal_lists() {
             cj.key = n_parts[k] > 1 ? s->deals.d_cluster[nodes[id].round_idx][p] : nullptr;   // the traverser's cluster on this round
             cj.key_stride = 1;
             if (cj.key && s->ordered) {   // list entries are ranks: the key sits in the rank's record
-                cj.key = static_cast<const uint32_t *>(s->d_arec_p[p]) + 2 * nodes[id].round_idx + p;
+                cj.key = reinterpret_cast<const uint32_t *>(s->d_arec_p[p].get()) + 2 * nodes[id].round_idx + p;
                 cj.key_stride = 8;
             }
             plan.count_off[k] = cat;
@@ -242,9 +242,8 @@ int PlanBuilder::emit_deal_lists() {
                 words += (par_listed ? size_t(plan.compact_jobs[size_t(sparse_slot[size_t(par)])].list_stride) : s->pitch[lane_round[size_t(par)]]) + kRowStagger;
             }
             if (words) {
-                if (hipMalloc((void **)&plan.d_bmask, words * sizeof(uint32_t)) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create: liveness masks of the round subtrees");
+                if (plan.d_bmask.alloc(words, &s->dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create: liveness masks of the round subtrees");
                 if (hipMemsetAsync(plan.d_bmask, 0, words * sizeof(uint32_t), t->stream) != hipSuccess) return fail(RS_ERR_HIP, "rs_solver_create: liveness masks of the round subtrees");
-                plan.aux_bytes += words * sizeof(uint32_t);
                 for (auto &pr : rows) {
                     mask_of_root[size_t(pr.first)] = plan.d_bmask + pr.second;
                     int bit = 0;
@@ -330,8 +329,7 @@ int PlanBuilder::emit_deal_lists() {
                     floats += (std::min<size_t>(opp, 10) + 1) * hp;
                 }
             if (floats) {
-                if (hipMalloc((void **)&plan.d_hrows, floats * sizeof(float)) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create: hand-off rows of the round subtrees");
-                plan.aux_bytes += floats * sizeof(float);
+                if (plan.d_hrows.alloc(floats, &s->dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create: hand-off rows of the round subtrees");
             } else hrow_off.clear();
         }
         nan_off.assign(size_t(n_nan) + 1, 0);
@@ -343,8 +341,7 @@ int PlanBuilder::emit_deal_lists() {
         for (size_t k = 0; k < size_t(n_nan); ++k) nan_off[k + 1] += nan_off[k];
         if (n_nan) {
             plan.reach_nan_bytes = nan_off[size_t(n_nan)] * sizeof(float);
-            plan.aux_bytes += plan.reach_nan_bytes;
-            hipError_t en = hipMalloc((void **)&plan.d_reach_nan, plan.reach_nan_bytes);
+            hipError_t en = plan.d_reach_nan.alloc(nan_off[size_t(n_nan)], &s->dev_bytes);
             if (en == hipSuccess) en = hipMemsetAsync(plan.d_reach_nan, 0xff, plan.reach_nan_bytes, t->stream);
             if (en != hipSuccess) return hip_fail(en, "rs_solver_create: reach buffers of the round subtrees");
             // dense sweeps read every lane of a root's row: lanes nobody handed a reach to must hold NaN.  List sweeps only ever read what the parent's reach-down
@@ -393,10 +390,9 @@ int PlanBuilder::emit_deal_lists() {
         push_compact(0, int(listed.size()));
     }
     if (!plan.compact_groups.empty()) {
-        hipError_t eg = hipMalloc((void **)&plan.d_compact_groups, plan.compact_groups.size() * sizeof(CompactGroup));
+        hipError_t eg = plan.d_compact_groups.alloc(plan.compact_groups.size(), &s->dev_bytes);
         if (eg == hipSuccess) eg = hipMemcpy(plan.d_compact_groups, plan.compact_groups.data(), plan.compact_groups.size() * sizeof(CompactGroup), hipMemcpyHostToDevice);
         if (eg != hipSuccess) return hip_fail(eg, "rs_solver_create: sibling groups of the live-deal lists");
-        plan.aux_bytes += plan.compact_groups.size() * sizeof(CompactGroup);
     }
     return RS_OK;
 }
@@ -449,10 +445,9 @@ int PlanBuilder::emit_round_walks() {   // ---- round subtrees, bottom-up: last 
 
 int PlanBuilder::emit_row_sums() {   // delta rows: the job descriptors of the summing launches emit_round_walks placed
     if (plan.row_jobs.empty()) return RS_OK;
-    hipError_t e = hipMalloc((void **)&plan.d_row_jobs, plan.row_jobs.size() * sizeof(RowSumJob));
+    hipError_t e = plan.d_row_jobs.alloc(plan.row_jobs.size(), &s->dev_bytes);
     if (e == hipSuccess) e = hipMemcpy(plan.d_row_jobs, plan.row_jobs.data(), plan.row_jobs.size() * sizeof(RowSumJob), hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: row-sum jobs");
-    plan.aux_bytes += plan.row_jobs.size() * sizeof(RowSumJob);
     return RS_OK;
 }
 
@@ -467,14 +462,12 @@ int PlanBuilder::emit_apply() {
             for (size_t i = 0; i < t->nodes.size(); ++i)
                 if (t->nodes[i].round_idx == r && t->nodes[i].player == p && t->nodes[i].n_actions > 0) k = std::max(k, t->nodes[i].n_clusters);
             if (!k) continue;
-            hipError_t e = hipMalloc((void **)&plan.d_member_start[r], (size_t(k) + 1) * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&plan.d_members[r], std::max<size_t>(n, 1) * 4);
+            hipError_t e = plan.d_member_start[r].alloc(size_t(k) + 1, &s->dev_bytes);
+            if (e == hipSuccess) e = plan.d_members[r].alloc(n, &s->dev_bytes);
             if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: member lists");
-            plan.aux_bytes += (size_t(k) + 1) * 4 + size_t(n) * 4;
             scratch = std::max(scratch, member_lists_scratch_words(n, k));
         }
-        if (hipMalloc((void **)&plan.d_member_scratch, std::max<size_t>(scratch, 1) * 4) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create_deals: member-list scratch");
-        plan.aux_bytes += scratch * 4;
+        if (plan.d_member_scratch.alloc(scratch, &s->dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_solver_create_deals: member-list scratch");
         for (size_t i = 0; i < t->nodes.size(); ++i) {
             const rs_node_desc &d = t->nodes[i];
             if (d.n_actions == 0 || d.player != p) continue;
@@ -493,7 +486,7 @@ int PlanBuilder::emit_apply() {
             plan.f32_max_clusters = std::max(plan.f32_max_clusters, d.n_clusters);
         }
         if (!jobs.empty()) {
-            hipError_t e = hipMalloc((void **)&plan.d_f32_jobs, jobs.size() * sizeof(ApplyF32Job));
+            hipError_t e = plan.d_f32_jobs.alloc(jobs.size(), &s->dev_bytes);
             if (e == hipSuccess) e = hipMemcpy(plan.d_f32_jobs, jobs.data(), jobs.size() * sizeof(ApplyF32Job), hipMemcpyHostToDevice);
             if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: f32 apply jobs");
             plan.n_f32_jobs = int(jobs.size());
@@ -518,7 +511,7 @@ int PlanBuilder::emit_apply() {
             cells += double(nc);
         }
         if (!aj.empty()) {
-            hipError_t ea = hipMalloc((void **)&plan.d_apply_jobs, aj.size() * sizeof(ApplyJob));
+            hipError_t ea = plan.d_apply_jobs.alloc(aj.size(), &s->dev_bytes);
             if (ea == hipSuccess) ea = hipMemcpy(plan.d_apply_jobs, aj.data(), aj.size() * sizeof(ApplyJob), hipMemcpyHostToDevice);
             if (ea != hipSuccess) return hip_fail(ea, "rs_solver_create: apply jobs");
             plan.n_apply_jobs = int(aj.size());
@@ -529,7 +522,7 @@ int PlanBuilder::emit_apply() {
                 at += aj[k].n_vec;
             }
             plan.pack_vec = at;
-            ea = hipMalloc((void **)&plan.d_pack_off, aj.size() * sizeof(size_t));
+            ea = plan.d_pack_off.alloc(aj.size(), &s->dev_bytes);
             if (ea == hipSuccess) ea = hipMemcpy(plan.d_pack_off, off.data(), aj.size() * sizeof(size_t), hipMemcpyHostToDevice);
             if (ea != hipSuccess) return hip_fail(ea, "rs_solver_create: apply jobs");
         }

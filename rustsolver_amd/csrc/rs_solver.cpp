@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 
 #include "rs_plan.hpp"
@@ -227,10 +228,10 @@ static int run_plan_inner(rs_solver *s, int p, int phase) {
         if (!plan.graph_exec) {
             RS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
             const int rc = run_range(s, plan, 0, plan.launches.size());
-            hipError_t e = hipStreamEndCapture(t->stream, &plan.graph);
+            hipError_t e = hipStreamEndCapture(t->stream, plan.graph.put());
             if (rc != RS_OK) return rc;
             RS_HIP(e, "hipStreamEndCapture");
-            RS_HIP(hipGraphInstantiate(&plan.graph_exec, plan.graph, nullptr, nullptr, 0), "hipGraphInstantiate");
+            RS_HIP(hipGraphInstantiate(plan.graph_exec.put(), plan.graph, nullptr, nullptr, 0), "hipGraphInstantiate");
         }
         RS_HIP(hipGraphLaunch(plan.graph_exec, t->stream), "hipGraphLaunch");
         return RS_OK;
@@ -267,8 +268,8 @@ int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_b
     if (table && (!table->d_dregrets || !table->d_dssum)) {
         hipError_t e = hipSetDevice(table->device);
         const size_t bytes = table->n_cells * 4;
-        if (e == hipSuccess && !table->d_dregrets) e = hipMalloc(&table->d_dregrets, bytes);
-        if (e == hipSuccess && !table->d_dssum) e = hipMalloc(&table->d_dssum, bytes);
+        if (e == hipSuccess && !table->d_dregrets) e = table->d_dregrets.alloc(bytes);
+        if (e == hipSuccess && !table->d_dssum) e = table->d_dssum.alloc(bytes);
         if (e == hipSuccess) e = hipMemsetAsync(table->d_dregrets, 0, bytes, table->stream);
         if (e == hipSuccess) e = hipMemsetAsync(table->d_dssum, 0, bytes, table->stream);
         if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: delta tables");
@@ -296,7 +297,7 @@ bool rs::solver_order_ahead(rs_solver *s, bool on, int (*before_sweep)(void *ctx
     return true;
 }
 // traverser p's records from the given per-deal arrays (the layout of rs_deal_batch: cluster[round][player], one leaf row, prune flags or null), on `stream`
-int rs::solver_order_on(rs_solver *s, int p, hipStream_t stream, const uint32_t *const cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS], const float *leaf, const uint8_t *prune) {
+int rs::solver_order_on(rs_solver *s, int p, hipStream_t stream, const DevBuf<uint32_t> (&cluster)[RS_MAX_ROUNDS][RS_MAX_PLAYERS], const float *leaf, const uint8_t *prune) {
     if (!s || !s->table || !s->ordered || p < 0 || p > 1) return fail(RS_ERR_INVALID, "solver_order_on: not an ordered deal solver");
     OrderJob oj = s->order_job[p];
     oj.key = cluster[s->order_round][p];
@@ -342,19 +343,6 @@ int rs::solver_discount_primary(rs_solver *s, float d) {
     return RS_OK;
 }
 
-// the item buffers of data-parallel float deal sweeps (solver_exchange_float grows them)
-static void fdp_free_items(rs_solver *s) {
-    for (void *q : {(void *)s->d_fdp_key, (void *)s->d_fdp_off, (void *)s->d_fdp_key_all, (void *)s->d_fdp_off_all, (void *)s->d_fdp_members, (void *)s->d_fdp_scratch,
-                    (void *)s->d_fdp_pay, (void *)s->d_fdp_pay_all})
-        if (q) (void)hipFree(q);
-    s->d_fdp_key = s->d_fdp_off = s->d_fdp_key_all = s->d_fdp_off_all = s->d_fdp_members = s->d_fdp_scratch = nullptr;
-    s->d_fdp_pay = s->d_fdp_pay_all = nullptr;
-    s->other_bytes -= s->fdp_bytes;
-    s->fdp_bytes = 0;
-    s->fdp_cap_items = 0;
-    s->fdp_cap_words = 0;
-}
-
 void rs::solver_release_device(rs_solver *s) {
     if (!s || !s->table) return;   // already detached (its table was destroyed first)
     rs_table *t = s->table;
@@ -364,89 +352,16 @@ void rs::solver_release_device(rs_solver *s) {
         (void)solver_kept_primary(s, false);
         (void)hipStreamSynchronize(t->stream);
     }
-    for (int p = 0; p < 2; ++p) {
-        Plan &pl = s->plan[p];
-        if (pl.graph_exec) (void)hipGraphExecDestroy(pl.graph_exec);
-        if (pl.graph) (void)hipGraphDestroy(pl.graph);
-        if (pl.d_jobs) (void)hipFree(pl.d_jobs);
-        if (pl.d_chance_jobs) (void)hipFree(pl.d_chance_jobs);
-        if (pl.d_reach_nan) (void)hipFree(pl.d_reach_nan);
-        if (pl.d_bmask) (void)hipFree(pl.d_bmask);
-        if (pl.d_lists) (void)hipFree(pl.d_lists);
-        if (pl.d_rlists) (void)hipFree(pl.d_rlists);
-        if (pl.d_plists) (void)hipFree(pl.d_plists);
-        if (pl.d_klists) (void)hipFree(pl.d_klists);
-        if (pl.d_hrows) (void)hipFree(pl.d_hrows);
-        if (pl.d_compact_groups) (void)hipFree(pl.d_compact_groups);
-        if (pl.d_row_jobs) (void)hipFree(pl.d_row_jobs);
-        if (pl.d_apply_jobs) (void)hipFree(pl.d_apply_jobs);
-        if (pl.d_pack_off) (void)hipFree(pl.d_pack_off);
-        if (pl.d_frows) (void)hipFree(pl.d_frows);
-        if (pl.d_f32_jobs) (void)hipFree(pl.d_f32_jobs);
-        if (pl.d_member_scratch) (void)hipFree(pl.d_member_scratch);
-        for (int r = 0; r < RS_MAX_ROUNDS; ++r) {
-            if (pl.d_member_start[r]) (void)hipFree(pl.d_member_start[r]);
-            if (pl.d_members[r]) (void)hipFree(pl.d_members[r]);
-        }
-        if (pl.d_counts) (void)hipFree(pl.d_counts);
-        if (pl.d_compact_jobs) (void)hipFree(pl.d_compact_jobs);
-        for (JitLaunch &JL : pl.jit) {
-            if (JL.d_blob) (void)hipFree(JL.d_blob);
-            if (JL.d_wl) (void)hipFree(JL.d_wl);
-        }
+    for (Plan &pl : s->plan) {   // the graphs before the buffers they launch on
+        pl.graph_exec.reset();
+        pl.graph.reset();
         pl = Plan{};
     }
-    if (s->d_arena) (void)hipFree(s->d_arena);
-    for (int k = 0; k < rs_solver::kAux; ++k) {
-        if (s->aux[k]) (void)hipStreamDestroy(s->aux[k]);
-        if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]);
-        s->aux[k] = nullptr;
-        s->ev_join[k] = nullptr;
-    }
-    if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-    s->ev_fork = nullptr;
-    if (s->d_shadow) (void)hipFree(s->d_shadow);
-    if (s->d_shadow_jobs) (void)hipFree(s->d_shadow_jobs);
-    if (s->d_kept_jobs) (void)hipFree(s->d_kept_jobs);
-    if (s->d_kept_primary) (void)hipFree(s->d_kept_primary);
-    if (s->d_disc_jobs) (void)hipFree(s->d_disc_jobs);
-    s->d_kept_jobs = nullptr;
-    s->d_kept_primary = nullptr;
-    s->d_disc_jobs = nullptr;
-    s->n_kept_jobs = 0;
-    for (int r = 0; r < RS_MAX_ROUNDS; ++r) {
-        if (s->d_attr[r] && s->d_attr[r] != s->d_arec) (void)hipFree(s->d_attr[r]);
-        s->d_attr[r] = nullptr;
-    }
-    for (int tp = 0; tp < 2; ++tp) {
-        if (s->d_arec_p[tp]) (void)hipFree(s->d_arec_p[tp]);
-        s->d_arec_p[tp] = nullptr;
-    }
-    if (s->d_drows) (void)hipFree(s->d_drows);
-    if (s->d_order_tot) (void)hipFree(s->d_order_tot);
+    static_cast<SolverDevice &>(*s) = SolverDevice{};
     s->d_arec = nullptr;
-    s->d_order_tot = nullptr;
-    if (s->d_pack_jobs) (void)hipFree(s->d_pack_jobs);
-    s->d_pack_jobs = nullptr;
+    for (void *&a : s->d_attr) a = nullptr;
+    s->n_kept_jobs = 0;
     s->n_pack_jobs = 0;
-    s->d_shadow = nullptr;
-    s->d_shadow_jobs = nullptr;
-    if (s->d_seed_state) (void)hipFree(s->d_seed_state);
-    if (s->d_exchange) (void)hipFree(s->d_exchange);
-    s->d_exchange = nullptr;
-    if (s->d_packed) (void)hipFree(s->d_packed);
-    if (s->d_items) (void)hipFree(s->d_items);
-    if (s->d_items_all) (void)hipFree(s->d_items_all);
-    if (s->d_item_count) (void)hipFree(s->d_item_count);
-    s->d_packed = nullptr;
-    s->d_items = s->d_items_all = s->d_item_count = nullptr;
-    fdp_free_items(s);
-    for (void *q : {(void *)s->d_fdp_jobs[0], (void *)s->d_fdp_jobs[1], (void *)s->d_fdp_scan, (void *)s->d_fdp_parts, (void *)s->d_fdp_count, (void *)s->d_fdp_start})
-        if (q) (void)hipFree(q);
-    s->d_fdp_jobs[0] = s->d_fdp_jobs[1] = nullptr;
-    s->d_fdp_scan = s->d_fdp_parts = s->d_fdp_count = s->d_fdp_start = nullptr;
-    s->d_arena = nullptr;
-    s->d_seed_state = nullptr;
     t->solvers.erase(std::remove(t->solvers.begin(), t->solvers.end(), s), t->solvers.end());
     s->table = nullptr;
 }
@@ -654,16 +569,15 @@ static int setup_table_shadow(rs_solver *s) {
             }
             if (tp == 0) s->n_shadow_jobs = int(jobs.size());
         }
-        s->other_bytes += std::max<size_t>(ints * 4, 256) + std::max<size_t>(jobs.size() * sizeof(ShadowJob), 256) + kept_jobs.size() * sizeof(ShadowJob);
-        e = hipMalloc((void **)&s->d_shadow, std::max<size_t>(ints * 4, 256));
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_shadow, 0, std::max<size_t>(ints * 4, 256), table->stream);
+        e = s->d_shadow.alloc(std::max<size_t>(ints, 64), &s->dev_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(s->d_shadow, 0, s->d_shadow.bytes(), table->stream);
         for (ShadowJob &j : jobs) j.dst = s->d_shadow + reinterpret_cast<size_t>(j.dst);
         for (ShadowJob &j : kept_jobs) j.dst = s->d_shadow + reinterpret_cast<size_t>(j.dst);
-        if (e == hipSuccess && !kept_jobs.empty()) e = hipMalloc((void **)&s->d_kept_jobs, kept_jobs.size() * sizeof(ShadowJob));
+        if (e == hipSuccess && !kept_jobs.empty()) e = s->d_kept_jobs.alloc(kept_jobs.size(), &s->dev_bytes);
         if (e == hipSuccess && !kept_jobs.empty()) e = hipMemcpy(s->d_kept_jobs, kept_jobs.data(), kept_jobs.size() * sizeof(ShadowJob), hipMemcpyHostToDevice);
         s->kept_epoch = ~uint64_t(0);
         if (e == hipSuccess && !kept_jobs.empty()) {   // the flag k_row_apply reads, and the table without the kept nodes as stretches of consecutive nodes (solver_discount_primary)
-            e = hipMalloc((void **)&s->d_kept_primary, 256);
+            e = s->d_kept_primary.alloc(64, &s->dev_bytes);
             if (e == hipSuccess) e = hipMemsetAsync(s->d_kept_primary, 0, 256, table->stream);
             std::vector<DiscountJob> runs;
             const size_t es = 4;   // kept records exist on RS_I32 tables only
@@ -682,11 +596,11 @@ static int setup_table_shadow(rs_solver *s) {
                 i = j;
             }
             s->n_disc_jobs = int(runs.size());
-            if (e == hipSuccess && !runs.empty()) e = hipMalloc((void **)&s->d_disc_jobs, runs.size() * sizeof(DiscountJob));
+            if (e == hipSuccess && !runs.empty()) e = s->d_disc_jobs.alloc(runs.size(), &s->dev_bytes);
             if (e == hipSuccess && !runs.empty()) e = hipMemcpy(s->d_disc_jobs, runs.data(), runs.size() * sizeof(DiscountJob), hipMemcpyHostToDevice);
         }
         if (jobs.size() != size_t(2) * size_t(s->n_shadow_jobs)) return fail(RS_ERR_INVALID, "rs_solver_create: the two sweeps' shadows hold different node sets");
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_shadow_jobs, std::max<size_t>(jobs.size() * sizeof(ShadowJob), 256));
+        if (e == hipSuccess) e = s->d_shadow_jobs.alloc(std::max<size_t>(jobs.size(), (256 + sizeof(ShadowJob) - 1) / sizeof(ShadowJob)), &s->dev_bytes);
         if (e == hipSuccess && !jobs.empty()) e = hipMemcpy(s->d_shadow_jobs, jobs.data(), jobs.size() * sizeof(ShadowJob), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             return hip_fail(e, "rs_solver_create: table shadow");
@@ -763,13 +677,12 @@ static int setup_deal_records(rs_solver *s) {
                 const uint32_t n_chunks = uint32_t(std::min<size_t>(size_t(s->n_cus) * 2, (size_t(n) + kOrderThreads - 1) / kOrderThreads));
                 const uint32_t chunk = uint32_t(round_up((size_t(n) + n_chunks - 1) / n_chunks, kOrderThreads));
                 const uint32_t max_bins = std::max(bins[0], bins[1]);
-                s->other_bytes += 2 * pitch * 32 + size_t(4) * max_bins * sizeof(uint32_t);
                 for (int tp = 0; tp < 2 && e == hipSuccess; ++tp) {
-                    e = hipMalloc(&s->d_arec_p[tp], pitch * 32);
+                    e = s->d_arec_p[tp].alloc(pitch * 32, &s->dev_bytes);
                     if (e == hipSuccess) e = hipMemsetAsync(s->d_arec_p[tp], 0, pitch * 32, table->stream);
                 }
                 s->d_arec = s->d_arec_p[0];
-                if (e == hipSuccess) e = hipMalloc((void **)&s->d_order_tot, size_t(4) * max_bins * sizeof(uint32_t));
+                if (e == hipSuccess) e = s->d_order_tot.alloc(size_t(4) * max_bins, &s->dev_bytes);
                 if (e != hipSuccess) {
                     return hip_fail(e, "rs_solver_create: ordered deal records");
                 }
@@ -796,8 +709,8 @@ static int setup_deal_records(rs_solver *s) {
             std::vector<PackJob> jobs;
             const size_t pitch = round_up(s->deals.n_deals, kLanePad);
             for (int r = 0; r < s->n_rounds && e == hipSuccess; ++r) {
-                s->other_bytes += pitch * 16;
-                e = hipMalloc(&s->d_attr[r], pitch * 16);
+                e = s->d_attr_buf[r].alloc(pitch * 16, &s->dev_bytes);
+                s->d_attr[r] = s->d_attr_buf[r];
                 if (e == hipSuccess) e = hipMemsetAsync(s->d_attr[r], 0, pitch * 16, table->stream);
                 PackJob j{};
                 j.cid0 = s->deals.d_cluster[r][0];
@@ -808,7 +721,7 @@ static int setup_deal_records(rs_solver *s) {
                 j.n = s->deals.n_deals;
                 jobs.push_back(j);
             }
-            if (e == hipSuccess) e = hipMalloc((void **)&s->d_pack_jobs, std::max<size_t>(jobs.size() * sizeof(PackJob), 256));
+            if (e == hipSuccess) e = s->d_pack_jobs.alloc(std::max<size_t>(jobs.size(), (256 + sizeof(PackJob) - 1) / sizeof(PackJob)), &s->dev_bytes);
             if (e == hipSuccess && !jobs.empty()) e = hipMemcpy(s->d_pack_jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice);
             if (e != hipSuccess) {
                 return hip_fail(e, "rs_solver_create: packed deal inputs");
@@ -919,9 +832,8 @@ static int trim_packed_records(rs_solver *s) {
                 j.n = s->deals.n_deals;
                 keep.push_back(j);
             } else {
-                (void)hipFree(s->d_attr[r]);
+                s->d_attr_buf[r].reset();
                 s->d_attr[r] = nullptr;
-                s->other_bytes -= round_up(s->deals.n_deals, kLanePad) * 16;
             }
         }
         if (int(keep.size()) != s->n_pack_jobs) {
@@ -980,7 +892,8 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
                 return fail(RS_ERR_INVALID, "rs_solver_create: action node " + std::to_string(nd.index) +
                                                 " has no valid action; mccfr would panic in WeightedIndex::new(&[]).unwrap() (cfr.rs:471)");
 
-    rs_solver *s = new (std::nothrow) rs_solver();
+    std::unique_ptr<rs_solver, void (*)(rs_solver *)> guard(new (std::nothrow) rs_solver(), rs_solver_destroy);   // destroys the solver on every way out but success
+    rs_solver *s = guard.get();
     if (!s) return fail(RS_ERR_OOM, "rs_solver_create: out of host memory");
     s->table = table;
     table->solvers.push_back(s);
@@ -1005,101 +918,52 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
                                               " is a showdown / all-in and needs an RS_LEAF_SIGN or RS_LEAF_UTIL buffer");
         }
     }
-    if (rc != RS_OK) {
-        rs_solver_destroy(s);
-        return rc;
-    }
+    if (rc != RS_OK) return rc;
     hipError_t e = hipSetDevice(table->device);
-    if (e != hipSuccess) {
-        rs_solver_destroy(s);
-        return hip_fail(e, "hipSetDevice");
-    }
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (params->opp_mode == RS_OPP_SAMPLE) {
         const uint64_t init[3] = {params->sample_seed, 0, 0};
-        if ((e = hipMalloc((void **)&s->d_seed_state, sizeof(init))) != hipSuccess ||
-            (e = hipMemcpy(s->d_seed_state, init, sizeof(init), hipMemcpyHostToDevice)) != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: seed state");
-            rs_solver_destroy(s);
-            return rc;
-        }
+        if ((e = s->d_seed_state.alloc(3, &s->dev_bytes)) != hipSuccess ||
+            (e = hipMemcpy(s->d_seed_state, init, sizeof(init), hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "rs_solver_create: seed state");
     }
     // streams for the independent round subtrees of a deal sweep
     if (hipDeviceGetAttribute(&s->lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, table->device) != hipSuccess || s->lds_limit < 1024) s->lds_limit = 64 * 1024;
     if (hipDeviceGetAttribute(&s->n_cus, hipDeviceAttributeMultiprocessorCount, table->device) != hipSuccess || s->n_cus < 1) s->n_cus = 256;
     if (s->deal_mode && !s->knobs.no_overlap && s->params.fuse_subtrees) {
-        e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(s->ev_fork.put(), hipEventDisableTiming);
         for (int k = 0; e == hipSuccess && k < rs_solver::kAux; ++k) {
-            e = hipStreamCreateWithFlags(&s->aux[k], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming);
+            e = hipStreamCreateWithFlags(s->aux[k].put(), hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(s->ev_join[k].put(), hipEventDisableTiming);
         }
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: auxiliary streams");
-            rs_solver_destroy(s);
-            return rc;
-        }
+        if (e != hipSuccess) return hip_fail(e, "rs_solver_create: auxiliary streams");
     }
     choose_delta_rows(s);
-    if (int rc2 = setup_deal_records(s)) {
-        rs_solver_destroy(s);
-        return rc2;
-    }
-    if (int rc2 = setup_table_shadow(s)) {   // after the two above: which nodes KEEP their records depends on where the delta rows go
-        rs_solver_destroy(s);
-        return rc2;
-    }
-    struct Builders {   // one plan builder per traverser; freed on every way out
-        PlanBuilder *b[2] = {nullptr, nullptr};
-        ~Builders() {
-            plan_builder_free(b[0]);
-            plan_builder_free(b[1]);
-        }
-    } pb;
-    pb.b[0] = plan_builder_new(s, 0);
-    pb.b[1] = plan_builder_new(s, 1);
-    if ((rc = plan_builder_layout(pb.b[0])) != RS_OK || (rc = plan_builder_layout(pb.b[1])) != RS_OK) {
-        rs_solver_destroy(s);
-        return rc;
-    }
-    if (int rc2 = trim_packed_records(s)) {
-        rs_solver_destroy(s);
-        return rc2;
-    }
+    if (int rc2 = setup_deal_records(s)) return rc2;
+    if (int rc2 = setup_table_shadow(s)) return rc2;   // after the two above: which nodes KEEP their records depends on where the delta rows go
+    using Builder = std::unique_ptr<PlanBuilder, void (*)(PlanBuilder *)>;   // one plan builder per traverser
+    const Builder pb[2] = {Builder(plan_builder_new(s, 0), plan_builder_free), Builder(plan_builder_new(s, 1), plan_builder_free)};
+    if ((rc = plan_builder_layout(pb[0].get())) != RS_OK || (rc = plan_builder_layout(pb[1].get())) != RS_OK) return rc;
+    if (int rc2 = trim_packed_records(s)) return rc2;
     s->arena_bytes = std::max(s->plan[0].arena_bytes, s->plan[1].arena_bytes);
-    if ((e = hipMalloc((void **)&s->d_arena, std::max<size_t>(s->arena_bytes, 256))) != hipSuccess) {
-        rc = hip_fail(e, "rs_solver_create: workspace hipMalloc");
-        rs_solver_destroy(s);
-        return rc;
-    }
+    if ((e = s->d_arena.alloc(std::max<size_t>(s->arena_bytes, 256), &s->dev_bytes)) != hipSuccess) return hip_fail(e, "rs_solver_create: workspace");
     // padding lanes are read by the vector kernels: keep them finite
-    (void)hipMemsetAsync(s->d_arena, 0, std::max<size_t>(s->arena_bytes, 256), table->stream);
+    (void)hipMemsetAsync(s->d_arena, 0, s->d_arena.bytes(), table->stream);
     if (s->sharded) {
         const size_t nb = size_t(std::max(s->plan[0].n_boundary, s->plan[1].n_boundary));
         s->exchange_floats_per_rank = nb * s->slot_lanes;
-        const size_t bytes = std::max<size_t>(size_t(s->params.shard_world) * s->exchange_floats_per_rank * sizeof(float), 256);
-        s->other_bytes += bytes;
-        if ((e = hipMalloc((void **)&s->d_exchange, bytes)) != hipSuccess || (e = hipMemsetAsync(s->d_exchange, 0, bytes, table->stream)) != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: exchange buffer");
-            rs_solver_destroy(s);
-            return rc;
-        }
+        const size_t floats = std::max<size_t>(size_t(s->params.shard_world) * s->exchange_floats_per_rank, 64);
+        if ((e = s->d_exchange.alloc(floats, &s->dev_bytes)) != hipSuccess || (e = hipMemsetAsync(s->d_exchange, 0, s->d_exchange.bytes(), table->stream)) != hipSuccess)
+            return hip_fail(e, "rs_solver_create: exchange buffer");
     }
-    if ((rc = plan_builder_emit(pb.b[0])) != RS_OK || (rc = plan_builder_emit(pb.b[1])) != RS_OK) {
-        rs_solver_destroy(s);
-        return rc;
-    }
-    if ((rc = merge_small_groups(s)) != RS_OK) {
-        rs_solver_destroy(s);
-        return rc;
-    }
+    if ((rc = plan_builder_emit(pb[0].get())) != RS_OK || (rc = plan_builder_emit(pb[1].get())) != RS_OK) return rc;
+    if ((rc = merge_small_groups(s)) != RS_OK) return rc;
     {   // the generated kernels of both plans: compiled together (concurrently where no cache has them), then bound to their launches
         std::vector<JitRequest> reqs;
         for (int p = 0; p < 2; ++p)
             for (JitLaunch &JL : s->plan[p].jit)
                 if (!JL.absorbed) reqs.push_back(JitRequest{&JL.source, &JL.entry, nullptr});
-        if (!reqs.empty() && (rc = jit_get_kernels(reqs, table->device, s->knobs.dump != 0)) != RS_OK) {
-            rs_solver_destroy(s);
-            return rc;
-        }
+        if (!reqs.empty() && (rc = jit_get_kernels(reqs, table->device, s->knobs.dump != 0)) != RS_OK) return rc;
         size_t k = 0;
         for (int p = 0; p < 2; ++p)
             for (JitLaunch &JL : s->plan[p].jit) {
@@ -1109,35 +973,17 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
     }
     for (int p = 0; p < 2; ++p) {
         Plan &pl = s->plan[p];
-        const size_t bytes = std::max<size_t>(pl.jobs.size(), 1) * sizeof(NodeJob);
-        s->other_bytes += bytes + std::max<size_t>(pl.chance_jobs.size(), 1) * sizeof(ChanceJob) + pl.n_count_words * sizeof(uint32_t) + pl.compact_jobs.size() * sizeof(CompactJob) +
-                          size_t(pl.n_apply_jobs) * sizeof(ApplyJob);
-        for (const JitLaunch &JL : pl.jit) s->other_bytes += JL.blob.size() + (JL.worklist ? (size_t(JL.n_jobs) + 3) * sizeof(uint32_t) : 0);
-        if ((e = hipMalloc((void **)&pl.d_jobs, bytes)) != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: job allocation");
-            rs_solver_destroy(s);
-            return rc;
-        }
-        if ((e = hipMalloc((void **)&pl.d_chance_jobs, std::max<size_t>(pl.chance_jobs.size(), 1) * sizeof(ChanceJob))) != hipSuccess ||
+        if ((e = pl.d_jobs.alloc(pl.jobs.size(), &s->dev_bytes)) != hipSuccess) return hip_fail(e, "rs_solver_create: job allocation");
+        if ((e = pl.d_chance_jobs.alloc(pl.chance_jobs.size(), &s->dev_bytes)) != hipSuccess ||
             (e = hipMemcpyAsync(pl.d_chance_jobs, pl.chance_jobs.data(), pl.chance_jobs.size() * sizeof(ChanceJob),
-                                hipMemcpyHostToDevice, table->stream)) != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: chance job upload");
-            rs_solver_destroy(s);
-            return rc;
-        }
+                                hipMemcpyHostToDevice, table->stream)) != hipSuccess)
+            return hip_fail(e, "rs_solver_create: chance job upload");
         for (JitLaunch &JL : pl.jit) {
-            if (JL.worklist && (e = hipMalloc((void **)&JL.d_wl, (size_t(JL.n_jobs) + 3) * sizeof(uint32_t))) != hipSuccess) {
-                rc = hip_fail(e, "rs_solver_create: work list");
-                rs_solver_destroy(s);
-                return rc;
-            }
+            if (JL.worklist && (e = JL.d_wl.alloc(size_t(JL.n_jobs) + 3, &s->dev_bytes)) != hipSuccess) return hip_fail(e, "rs_solver_create: work list");
             if (JL.blob.empty()) continue;   // a merged launch: its members hold the blobs
-            if ((e = hipMalloc((void **)&JL.d_blob, JL.blob.size())) != hipSuccess ||
-                (e = hipMemcpyAsync(JL.d_blob, JL.blob.data(), JL.blob.size(), hipMemcpyHostToDevice, table->stream)) != hipSuccess) {
-                rc = hip_fail(e, "rs_solver_create: tree-kernel argument upload");
-                rs_solver_destroy(s);
-                return rc;
-            }
+            if ((e = JL.d_blob.alloc(JL.blob.size(), &s->dev_bytes)) != hipSuccess ||
+                (e = hipMemcpyAsync(JL.d_blob, JL.blob.data(), JL.blob.size(), hipMemcpyHostToDevice, table->stream)) != hipSuccess)
+                return hip_fail(e, "rs_solver_create: tree-kernel argument upload");
         }
         for (JitLaunch &JL : pl.jit) {   // merged launches: where every member's jobs start on the grid's y axis, and its blob
             unsigned at = 0;
@@ -1169,18 +1015,11 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
             }
         }
         if ((e = hipMemcpyAsync(pl.d_jobs, pl.jobs.data(), pl.jobs.size() * sizeof(NodeJob), hipMemcpyHostToDevice,
-                                table->stream)) != hipSuccess) {
-            rc = hip_fail(e, "rs_solver_create: job upload");
-            rs_solver_destroy(s);
-            return rc;
-        }
+                                table->stream)) != hipSuccess)
+            return hip_fail(e, "rs_solver_create: job upload");
     }
-    if ((e = hipStreamSynchronize(table->stream)) != hipSuccess) {
-        rc = hip_fail(e, "rs_solver_create: sync");
-        rs_solver_destroy(s);
-        return rc;
-    }
-    *out = s;
+    if ((e = hipStreamSynchronize(table->stream)) != hipSuccess) return hip_fail(e, "rs_solver_create: sync");
+    *out = guard.release();
     return RS_OK;
 }
 
@@ -1201,6 +1040,17 @@ static int copy_root(rs_solver *s, int traverser, float *d_root_util) {
         RS_HIP(hipMemcpyAsync(d_root_util, s->plan[traverser].root_util, s->plan[traverser].root_lanes * sizeof(float),
                               hipMemcpyDeviceToDevice, s->table->stream),
                "rs_iterate: root util copy");
+    return RS_OK;
+}
+
+// The buffers of the direct rows' items, all or nothing: fresh ones, moved in (and item_cap raised) once both exist.  A failure keeps what was there.
+static int grow_items(rs_solver *s, uint32_t cap, size_t world, const char *what) {
+    DevBuf<uint32_t> items, items_all;
+    RS_HIP(items.alloc(size_t(cap) * 3, &s->dev_bytes), what);
+    RS_HIP(items_all.alloc(size_t(cap) * 3 * world, &s->dev_bytes), what);
+    s->d_items = std::move(items);
+    s->d_items_all = std::move(items_all);
+    s->item_cap = cap;
     return RS_OK;
 }
 
@@ -1241,16 +1091,9 @@ static int solver_exchange_deltas(rs_solver *s, int p) {
         if (most <= s->item_cap) break;
         if (attempt) return fail(RS_ERR_HIP, "deal delta items: the count changed between two passes over the same rows");
         // some rank's rows hold more items than the buffers: every rank grows (the counts are everybody's) and writes its items again -- the rows are still there
-        (void)hipFree(s->d_items);
-        (void)hipFree(s->d_items_all);
-        s->d_items = s->d_items_all = nullptr;
-        const size_t sized = std::max<size_t>(size_t(world), s->items_world);
-        s->other_bytes -= size_t(s->item_cap) * 12 * (sized + 1);
-        s->item_cap = uint32_t(std::min<uint64_t>(uint64_t(most) + most / 8 + 1024, 0xfffffff0ull / 3));
-        if (most > s->item_cap) return fail(RS_ERR_OOM, "deal delta items: more than 2^32 / 3 items in one sweep");
-        RS_HIP(hipMalloc((void **)&s->d_items, size_t(s->item_cap) * 12), "deal delta items");
-        RS_HIP(hipMalloc((void **)&s->d_items_all, size_t(s->item_cap) * 12 * sized), "deal delta items");
-        s->other_bytes += size_t(s->item_cap) * 12 * (sized + 1);
+        const uint32_t cap = uint32_t(std::min<uint64_t>(uint64_t(most) + most / 8 + 1024, 0xfffffff0ull / 3));
+        if (most > cap) return fail(RS_ERR_OOM, "deal delta items: more than 2^32 / 3 items in one sweep");
+        if (int rc = grow_items(s, cap, std::max<size_t>(size_t(world), s->items_world), "deal delta items")) return rc;
         RS_HIP(hipMemsetAsync(s->d_item_count, 0, sizeof(uint32_t), t->stream), "deal delta items");
         for (const Launch &L : plan.launches)
             if (L.kind == L_ROWSUM && L.n_actions)
@@ -1279,7 +1122,6 @@ static int solver_exchange_float(rs_solver *s, int p) {
     Plan &plan = s->plan[p];
     const int world = comm_world(s->comm);
     s->dp_bytes_last = 0;
-    if (s->fdp_broken) return fail(RS_ERR_OOM, "rs_iterate: the float delta items could not be allocated in an earlier sweep");
     if (!s->d_fdp_scan || !s->d_fdp_jobs[p] || int(s->fdp_world) < world) return fail(RS_ERR_INVALID, "rs_iterate: float delta buffers missing (rs_solver_attach_comm)");
     const uint32_t n = s->deals.n_deals, pitch = uint32_t(s->pitch[0]);
     const size_t m = size_t(plan.n_f32_jobs) * n;
@@ -1301,42 +1143,34 @@ static int solver_exchange_float(rs_solver *s, int p) {
     }
     const uint64_t union_items = uint64_t(most) * uint64_t(world);
     if (union_items >= (uint64_t(1) << 32)) return fail(RS_ERR_UNSUPPORTED, "rs_iterate: 2^32 or more float delta items in one data-parallel sweep");
-    if (most > s->fdp_cap_items || most_words > s->fdp_cap_words || !s->d_fdp_key) {   // grow: a function of the gathered counts alone, hence the same on every rank
+    if (most > s->fdp.cap_items || most_words > s->fdp.cap_words || !s->fdp.key) {   // grow: a function of the gathered counts alone, hence the same on every rank
         RS_HIP(hipStreamSynchronize(t->stream), "float delta items");
-        fdp_free_items(s);
+        s->fdp = SolverDevice::FdpItems{};   // first: the old and the new items never take memory at the same time
+        // all or nothing: fresh buffers, moved in (and the caps raised) once every one exists; nothing is launched on a missing buffer, and a later sweep tries again
+        SolverDevice::FdpItems f;
         const uint32_t cap = uint32_t(std::min<uint64_t>(uint64_t(most) + most / 8 + 1024, ((uint64_t(1) << 32) - 1) / uint64_t(world)));
         const size_t cap_words = most_words + most_words / 8 + 1024 * 2 * RS_MAX_ACTIONS;
         const size_t scratch = member_lists_scratch_words_upto(size_t(cap) * world, std::max(s->fdp_keys[0], s->fdp_keys[1]) + 1);
-        bool ok = hipMalloc((void **)&s->d_fdp_key, size_t(cap) * 4) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_off, size_t(cap) * 4) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_key_all, size_t(cap) * 4 * world) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_off_all, size_t(cap) * 4 * world) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_members, size_t(cap) * 4 * world) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_scratch, std::max<size_t>(scratch, 1) * 4) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_pay, cap_words * 4) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->d_fdp_pay_all, cap_words * 4 * world) == hipSuccess;
-        if (!ok) {   // nothing is launched on a missing buffer: this sweep and every later one fail
-            (void)hipGetLastError();
-            fdp_free_items(s);
-            s->fdp_broken = true;
-            return fail(RS_ERR_OOM, "rs_iterate: float delta items (data-parallel deal sweep)");
-        }
-        s->fdp_cap_items = cap;
-        s->fdp_cap_words = cap_words;
-        s->fdp_bytes = size_t(cap) * 4 * (2 + 3 * size_t(world)) + std::max<size_t>(scratch, 1) * 4 + cap_words * 4 * (1 + size_t(world));
-        s->other_bytes += s->fdp_bytes;
+        size_t *led = &s->dev_bytes;
+        const bool ok = f.key.alloc(cap, led) == hipSuccess && f.off.alloc(cap, led) == hipSuccess && f.key_all.alloc(size_t(cap) * world, led) == hipSuccess &&
+                        f.off_all.alloc(size_t(cap) * world, led) == hipSuccess && f.members.alloc(size_t(cap) * world, led) == hipSuccess &&
+                        f.scratch.alloc(scratch, led) == hipSuccess && f.pay.alloc(cap_words, led) == hipSuccess && f.pay_all.alloc(cap_words * world, led) == hipSuccess;
+        if (!ok) return fail(RS_ERR_OOM, "rs_iterate: float delta items (data-parallel deal sweep)");
+        f.cap_items = cap;
+        f.cap_words = cap_words;
+        s->fdp = std::move(f);
     }
     FdpClusters cl{};
     for (int r = 0; r < s->n_rounds && r < RS_MAX_ROUNDS; ++r) cl.c[r] = s->deals.d_cluster[r][p];
-    RS_HIP(launch_fdp_pack(s->d_fdp_jobs[p], plan.n_f32_jobs, n, pitch, cl, flags, words, s->d_fdp_key, s->d_fdp_off, s->d_fdp_pay, t->stream), "k_fdp_pack");
+    RS_HIP(launch_fdp_pack(s->d_fdp_jobs[p], plan.n_f32_jobs, n, pitch, cl, flags, words, s->fdp.key, s->fdp.off, s->fdp.pay, t->stream), "k_fdp_pack");
     const uint32_t own = counts[0];
-    if (most > own) RS_HIP(hipMemsetAsync(s->d_fdp_key + own, 0xff, size_t(most - own) * 4, t->stream), "float delta items: padding");   // beyond every key: the last list
-    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_key, s->d_fdp_key_all, most)) return rc;
-    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_off, s->d_fdp_off_all, most)) return rc;
-    if (int rc = comm_allgather_u32(s->comm, t, s->d_fdp_pay, s->d_fdp_pay_all, most_words)) return rc;
+    if (most > own) RS_HIP(hipMemsetAsync(s->fdp.key + own, 0xff, size_t(most - own) * 4, t->stream), "float delta items: padding");   // beyond every key: the last list
+    if (int rc = comm_allgather_u32(s->comm, t, s->fdp.key, s->fdp.key_all, most)) return rc;
+    if (int rc = comm_allgather_u32(s->comm, t, s->fdp.off, s->fdp.off_all, most)) return rc;
+    if (int rc = comm_allgather_u32(s->comm, t, s->fdp.pay, s->fdp.pay_all, most_words)) return rc;
     const uint32_t k = s->fdp_keys[p] + 1;   // the padding's key is clamped to fdp_keys[p]: a list nobody reads
-    RS_HIP(launch_member_lists(s->d_fdp_key_all, size_t(union_items), k, s->d_fdp_scratch, s->d_fdp_start, s->d_fdp_members, t->stream), "float delta items: member lists");
-    RS_HIP(launch_fdp_apply(plan.d_f32_jobs, s->d_fdp_jobs[p], plan.n_f32_jobs, plan.f32_max_clusters, s->d_fdp_start, s->d_fdp_members, s->d_fdp_off_all, s->d_fdp_pay_all,
+    RS_HIP(launch_member_lists(s->fdp.key_all, size_t(union_items), k, s->fdp.scratch, s->d_fdp_start, s->fdp.members, t->stream), "float delta items: member lists");
+    RS_HIP(launch_fdp_apply(plan.d_f32_jobs, s->d_fdp_jobs[p], plan.n_f32_jobs, plan.f32_max_clusters, s->d_fdp_start, s->fdp.members, s->fdp.off_all, s->fdp.pay_all,
                             most, most_words, t->dtype, (s->params.mode & RS_UPD_RMPLUS) != 0, t->stream),
            "k_fdp_apply");
     s->dp_bytes_last = 8 * uint64_t(world) + (uint64_t(most) * 8 + uint64_t(most_words) * 4) * uint64_t(world);
@@ -1399,29 +1233,19 @@ int rs_solver_attach_comm(rs_solver *s, rs_comm *comm) {
         rs_table *t = s->table;
         RS_HIP(hipSetDevice(t->device), "hipSetDevice");
         const size_t pack_vec = std::max(s->plan[0].pack_vec, s->plan[1].pack_vec);
-        if (pack_vec && !s->d_packed) {
-            RS_HIP(hipMalloc((void **)&s->d_packed, pack_vec * 32), "rs_solver_attach_comm: packed delta cells");
-            s->other_bytes += pack_vec * 32;
-        }
+        if (pack_vec && !s->d_packed) RS_HIP(s->d_packed.alloc(pack_vec * 8, &s->dev_bytes), "rs_solver_attach_comm: packed delta cells");
         bool direct = false;
         for (int p = 0; p < 2; ++p)
             for (const Launch &L : s->plan[p].launches) direct = direct || (L.kind == L_ROWSUM && L.n_actions);
         const size_t world = size_t(comm_world(comm));
-        if (direct && s->items_world && world > s->items_world) {   // a communicator of more ranks than the buffers were sized for: again, bigger
+        if (direct && (!s->d_items || world > s->items_world)) {   // first, or a communicator of more ranks than the buffers were sized for: again, bigger
             RS_HIP(hipStreamSynchronize(t->stream), "rs_solver_attach_comm");
-            (void)hipFree(s->d_item_count);
-            (void)hipFree(s->d_items);
-            (void)hipFree(s->d_items_all);
-            s->other_bytes -= size_t(s->item_cap) * 12 * (size_t(s->items_world) + 1);
-            s->d_item_count = s->d_items = s->d_items_all = nullptr;
-        }
-        if (direct && !s->d_item_count) RS_HIP(hipMalloc((void **)&s->d_item_count, (world + 1) * sizeof(uint32_t) + 256), "rs_solver_attach_comm: item counts");
-        if (direct) s->items_world = uint32_t(std::max<size_t>(world, s->items_world));
-        if (direct && !s->d_items) {
-            s->item_cap = uint32_t(std::min<uint64_t>(uint64_t(s->deals.n_deals) * 16 + 4096, 0xfffffff0ull / 3));   // grown when a sweep writes more (solver_exchange_deltas)
-            RS_HIP(hipMalloc((void **)&s->d_items, size_t(s->item_cap) * 12), "rs_solver_attach_comm: delta items");
-            RS_HIP(hipMalloc((void **)&s->d_items_all, size_t(s->item_cap) * 12 * size_t(s->items_world)), "rs_solver_attach_comm: delta items");
-            s->other_bytes += size_t(s->item_cap) * 12 * (size_t(s->items_world) + 1);
+            DevBuf<uint32_t> count;
+            RS_HIP(count.alloc(world + 1 + 64, &s->dev_bytes), "rs_solver_attach_comm: item counts");
+            const uint32_t cap = uint32_t(std::min<uint64_t>(uint64_t(s->deals.n_deals) * 16 + 4096, 0xfffffff0ull / 3));   // grown when a sweep writes more (solver_exchange_deltas)
+            if (int rc = grow_items(s, cap, world, "rs_solver_attach_comm: delta items")) return rc;
+            s->d_item_count = std::move(count);
+            s->items_world = uint32_t(world);
         }
     }
     if (comm && s->deal_mode && s->table && s->table->dtype != RS_I32) {   // the fixed buffers of solver_exchange_float; the item buffers grow with the first sweeps
@@ -1451,25 +1275,29 @@ int rs_solver_attach_comm(rs_solver *s, rs_comm *comm) {
             s->fdp_keys[p] = uint32_t(keys);
             keys_max = std::max(keys_max, keys);
             m = std::max(m, jobs.size() * size_t(s->deals.n_deals));
-            if (!s->d_fdp_jobs[p] && !jobs.empty()) {
-                RS_HIP(hipMalloc((void **)&s->d_fdp_jobs[p], jobs.size() * sizeof(FdpJob)), "rs_solver_attach_comm: float item jobs");
-                RS_HIP(hipMemcpy(s->d_fdp_jobs[p], jobs.data(), jobs.size() * sizeof(FdpJob), hipMemcpyHostToDevice), "rs_solver_attach_comm: float item jobs");
-                s->other_bytes += jobs.size() * sizeof(FdpJob);
+            if (!s->d_fdp_jobs[p] && !jobs.empty()) {   // each group below is moved in once all of it exists: a failed attach leaves nothing half built
+                DevBuf<FdpJob> dj;
+                RS_HIP(dj.alloc(jobs.size(), &s->dev_bytes), "rs_solver_attach_comm: float item jobs");
+                RS_HIP(hipMemcpy(dj, jobs.data(), jobs.size() * sizeof(FdpJob), hipMemcpyHostToDevice), "rs_solver_attach_comm: float item jobs");
+                s->d_fdp_jobs[p] = std::move(dj);
             }
         }
         if (!s->d_fdp_scan) {
+            DevBuf<uint32_t> scan, parts, start;
+            RS_HIP(scan.alloc((m + 1) * 2, &s->dev_bytes), "rs_solver_attach_comm: float item scans");
+            RS_HIP(parts.alloc(exclusive_scan_parts(m + 1), &s->dev_bytes), "rs_solver_attach_comm: float item scans");
+            RS_HIP(start.alloc(size_t(keys_max) + 2, &s->dev_bytes), "rs_solver_attach_comm: float member lists");
+            s->d_fdp_scan = std::move(scan);
+            s->d_fdp_parts = std::move(parts);
+            s->d_fdp_start = std::move(start);
             s->fdp_m = m;
-            RS_HIP(hipMalloc((void **)&s->d_fdp_scan, (m + 1) * 2 * 4), "rs_solver_attach_comm: float item scans");
-            RS_HIP(hipMalloc((void **)&s->d_fdp_parts, exclusive_scan_parts(m + 1) * 4), "rs_solver_attach_comm: float item scans");
-            RS_HIP(hipMalloc((void **)&s->d_fdp_start, (size_t(keys_max) + 2) * 4), "rs_solver_attach_comm: float member lists");
-            s->other_bytes += (m + 1) * 8 + exclusive_scan_parts(m + 1) * 4 + (size_t(keys_max) + 2) * 4;
         }
         if (world > s->fdp_world) {
-            if (s->d_fdp_count) (void)hipFree(s->d_fdp_count);
-            s->d_fdp_count = nullptr;
             RS_HIP(hipStreamSynchronize(t->stream), "rs_solver_attach_comm");
-            fdp_free_items(s);   // sized for fewer ranks
-            RS_HIP(hipMalloc((void **)&s->d_fdp_count, (2 + 2 * world) * sizeof(uint32_t)), "rs_solver_attach_comm: float item counts");
+            DevBuf<uint32_t> count;
+            RS_HIP(count.alloc(2 + 2 * world, &s->dev_bytes), "rs_solver_attach_comm: float item counts");
+            s->d_fdp_count = std::move(count);
+            s->fdp = SolverDevice::FdpItems{};   // sized for fewer ranks
             s->fdp_world = uint32_t(world);
         }
     }
@@ -1514,7 +1342,7 @@ int rs_train(rs_solver *s, uint64_t iterations, uint64_t discount_interval, uint
     return rc != RS_OK ? rc : rc_off;
 }
 
-size_t rs_solver_workspace_bytes(const rs_solver *s) { return s ? s->arena_bytes + s->plan[0].aux_bytes + s->plan[1].aux_bytes + s->other_bytes : 0; }
+size_t rs_solver_workspace_bytes(const rs_solver *s) { return s ? s->dev_bytes : 0; }
 
 int rs_solver_exchange_bytes(const rs_solver *s, uint64_t *bytes, uint64_t *sweeps) {
     if (!s || !bytes || !sweeps) return fail(RS_ERR_INVALID, "rs_solver_exchange_bytes: NULL argument");

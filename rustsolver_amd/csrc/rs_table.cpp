@@ -28,21 +28,21 @@ int hip_fail(hipError_t e, const char *what) {
     } while (0)
 
 // ---- profiling ------------------------------------------------------------------------------------
-static hipEvent_t prof_event(rs_table *t) {
+static DevEvent prof_event(rs_table *t) {
+    DevEvent e;
     if (!t->prof.pool.empty()) {
-        hipEvent_t e = t->prof.pool.back();
+        e = std::move(t->prof.pool.back());
         t->prof.pool.pop_back();
         return e;
     }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
+    (void)hipEventCreate(e.put());
     return e;
 }
 void prof_begin(rs_table *t, int kind, double bytes) {
     if (!t->prof.on) return;
     Profile::Pending p{prof_event(t), prof_event(t), kind, bytes};
     (void)hipEventRecord(p.a, t->stream);
-    t->prof.pending.push_back(p);
+    t->prof.pending.push_back(std::move(p));
 }
 void prof_end(rs_table *t) {
     if (!t->prof.on) return;
@@ -56,8 +56,8 @@ static void prof_collect(rs_table *t) {
             t->prof.acc.ms[p.kind] += ms;
             t->prof.acc.algo_bytes[p.kind] += p.bytes;
         }
-        t->prof.pool.push_back(p.a);
-        t->prof.pool.push_back(p.b);
+        t->prof.pool.push_back(std::move(p.a));
+        t->prof.pool.push_back(std::move(p.b));
     }
     t->prof.pending.clear();
 }
@@ -227,8 +227,8 @@ int rs_table_create_with(const rs_node_desc *nodes, int n_nodes, int dtype, int 
     t->n_cells = off;
     const size_t bytes = off * elem_size(dtype);
     hipError_t er;
-    if ((er = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (er = hipMalloc(&t->d_regrets, bytes)) != hipSuccess || (er = hipMalloc(&t->d_ssum, bytes)) != hipSuccess ||
+    if ((er = hipStreamCreateWithFlags(t->stream.put(), hipStreamNonBlocking)) != hipSuccess ||
+        (er = t->d_regrets.alloc(bytes)) != hipSuccess || (er = t->d_ssum.alloc(bytes)) != hipSuccess ||
         (er = hipMemsetAsync(t->d_regrets, 0, bytes, t->stream)) != hipSuccess ||   // Infoset::init zero fill
         (er = hipMemsetAsync(t->d_ssum, 0, bytes, t->stream)) != hipSuccess ||
         (er = hipStreamSynchronize(t->stream)) != hipSuccess) {
@@ -263,23 +263,6 @@ void rs_table_destroy(rs_table *t) {
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     while (!t->solvers.empty()) solver_release_device(t->solvers.back());   // they stay valid handles, but inert
-    for (Profile::Pending &p : t->prof.pending) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (hipEvent_t e : t->prof.pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : t->prof.marks) (void)hipEventDestroy(e);
-    if (t->d_regrets) (void)hipFree(t->d_regrets);
-    if (t->d_ssum) (void)hipFree(t->d_ssum);
-    if (t->d_snap_regrets) (void)hipFree(t->d_snap_regrets);
-    if (t->d_snap_ssum) (void)hipFree(t->d_snap_ssum);
-    if (t->d_job) (void)hipFree(t->d_job);
-    if (t->d_query) (void)hipFree(t->d_query);
-    if (t->d_err_sink) (void)hipFree(t->d_err_sink);
-    if (t->d_km_scratch) (void)hipFree(t->d_km_scratch);
-    if (t->d_dregrets) (void)hipFree(t->d_dregrets);
-    if (t->d_dssum) (void)hipFree(t->d_dssum);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
 }
 
@@ -383,10 +366,10 @@ int rs_get_infosets(rs_table *t, int node, const uint32_t *lanes, size_t n, void
             return fail(RS_ERR_OOB, "rs_get_infosets: index out of bounds: the len is " + std::to_string(n_lanes) + " but the index is " + std::to_string(lanes[k]));
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     const size_t es = elem_size(t->dtype), A = nd.n_actions;
-    uint32_t *d_lanes = nullptr;
-    void *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_lanes, n * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_out, A * n * es);
+    DevBuf<uint32_t> d_lanes;
+    DevBuf<char> d_out;
+    hipError_t e = d_lanes.alloc(n);
+    if (e == hipSuccess) e = d_out.alloc(A * n * es);
     if (e == hipSuccess) e = hipMemcpyAsync(d_lanes, lanes, n * 4, hipMemcpyHostToDevice, t->stream);
     std::vector<uint16_t> tmp(t->dtype == RS_F16 ? A * n : 0);
     for (int which = 0; which < 2 && e == hipSuccess; ++which) {
@@ -399,8 +382,6 @@ int rs_get_infosets(rs_table *t, int node, const uint32_t *lanes, size_t n, void
             for (size_t i = 0; i < A * n; ++i) ((float *)host)[i] = f16_bits_to_f32(tmp[i]);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (d_lanes) (void)hipFree(d_lanes);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return hip_fail(e, "rs_get_infosets");
     return RS_OK;
 }
@@ -410,14 +391,13 @@ int rs_get_infosets(rs_table *t, int node, const uint32_t *lanes, size_t n, void
 int rs_selftest_division(rs_table *t, size_t n, uint64_t seed, uint64_t *mismatches, float *first_bad) {
     if (!t || !mismatches) return fail(RS_ERR_INVALID, "rs_selftest_division: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    char *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, 16);
+    DevBuf<char> d;
+    hipError_t e = d.alloc(16);
     if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16, t->stream);
-    if (e == hipSuccess) e = launch_selftest_division(n, seed, (unsigned long long *)d, (float *)(d + 8), t->stream);
+    if (e == hipSuccess) e = launch_selftest_division(n, seed, (unsigned long long *)d.get(), (float *)(d + 8), t->stream);
     char host[16] = {0};
     if (e == hipSuccess) e = hipMemcpyAsync(host, d, 16, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (d) (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, "rs_selftest_division");
     std::memcpy(mismatches, host, 8);
     if (first_bad) std::memcpy(first_bad, host + 8, 8);
@@ -428,8 +408,8 @@ int rs_table_checksum(rs_table *t, uint64_t *out) {
     if (!t || !out) return fail(RS_ERR_INVALID, "rs_table_checksum: NULL argument");
     if (int rc = table_settle(t)) return rc;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    unsigned long long *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, 16);
+    DevBuf<unsigned long long> d;
+    hipError_t e = d.alloc(2);
     if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16, t->stream);
     for (int n = 0; n < int(t->nodes.size()) && e == hipSuccess; ++n) {
         const rs_node_desc &nd = t->nodes[size_t(n)];
@@ -440,7 +420,6 @@ int rs_table_checksum(rs_table *t, uint64_t *out) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, 16, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (d) (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, "rs_table_checksum");
     return RS_OK;
 }
@@ -460,7 +439,7 @@ static int single_strategy(rs_table *t, int node, int board, int cluster, float 
     const size_t g0 = lane / kLanePad * kLanePad;  // 64-lane aligned group
     const size_t es = elem_size(t->dtype);
     // gather the group's A rows into a compact [A][64] block (cached per-table scratch), run the kernel with pitch 64
-    if (!t->d_query) RS_HIP(hipMalloc(&t->d_query, RS_MAX_ACTIONS * kLanePad * (4 + sizeof(float))), "hipMalloc(query scratch)");
+    if (!t->d_query) RS_HIP(t->d_query.alloc(RS_MAX_ACTIONS * kLanePad * (4 + sizeof(float))), "query scratch");
     void *d_in = t->d_query;
     float *d_out = reinterpret_cast<float *>((char *)t->d_query + RS_MAX_ACTIONS * kLanePad * 4);
     // the 64-lane group never straddles a tile (tiles are multiples of 64 lanes): rows are tile[node] elements apart from its first element on
@@ -524,10 +503,10 @@ static int logical_sweep(rs_table *t, const uint64_t *lane_off, int op, uint64_t
     if (!t || !lane_off) return fail(RS_ERR_INVALID, std::string(fn) + ": NULL argument");
     if (op == 0 && t->dtype == RS_F32) return fail(RS_ERR_UNSUPPORTED, std::string(fn) + ": i32 and binary16 tables");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    unsigned long long *d = nullptr;
+    DevBuf<unsigned long long> d;
     hipError_t e = hipSuccess;
     if (op == 1) {
-        e = hipMalloc((void **)&d, RS_MAX_ROUNDS * 2 * sizeof(unsigned long long));
+        e = d.alloc(RS_MAX_ROUNDS * 2);
         if (e == hipSuccess) e = hipMemsetAsync(d, 0, RS_MAX_ROUNDS * 2 * sizeof(unsigned long long), t->stream);
     }
     for (int n = 0; n < int(t->nodes.size()) && e == hipSuccess; ++n) {
@@ -543,7 +522,6 @@ static int logical_sweep(rs_table *t, const uint64_t *lane_off, int op, uint64_t
     }
     if (op == 1 && e == hipSuccess) e = hipMemcpyAsync(out, d, RS_MAX_ROUNDS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream);
     if (op == 1 && e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (d) (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, fn);
     return RS_OK;
 }
@@ -579,11 +557,16 @@ int rs_dfree(rs_table *t, void *d_ptr) {
     RS_HIP(hipFree(d_ptr), "hipFree");
     return RS_OK;
 }
+size_t rs_device_held_bytes(void) { return g_dev_held.load(); }
+int rs_debug_fail_alloc(int64_t n) {
+    g_dev_fail_after.store(n < 0 ? -1 : (long long)n);
+    return RS_OK;
+}
 int rs_table_deltas(rs_table *t, int32_t **d_dregrets, int32_t **d_dssum) {
     if (!t || !d_dregrets || !d_dssum) return fail(RS_ERR_INVALID, "rs_table_deltas: NULL argument");
     if (!t->d_dregrets || !t->d_dssum) return fail(RS_ERR_INVALID, "rs_table_deltas: the table has no delta tables (rs_solver_create_deals makes them)");
-    *d_dregrets = static_cast<int32_t *>(t->d_dregrets);
-    *d_dssum = static_cast<int32_t *>(t->d_dssum);
+    *d_dregrets = reinterpret_cast<int32_t *>(t->d_dregrets.get());
+    *d_dssum = reinterpret_cast<int32_t *>(t->d_dssum.get());
     return RS_OK;
 }
 int rs_h2d(rs_table *t, void *d_dst, const void *src, size_t bytes) {
@@ -615,7 +598,7 @@ int rs_sync(rs_table *t) {
 
 // ---- bulk kernels on one node -------------------------------------------------------------------------------------------
 static int stage_job(rs_table *t, const NodeJob &job) {
-    if (!t->d_job) RS_HIP(hipMalloc((void **)&t->d_job, sizeof(NodeJob)), "hipMalloc(job slot)");
+    if (!t->d_job) RS_HIP(t->d_job.alloc(1), "job slot");
     // stream-ordered: the previous kernel that read the slot has finished before this copy runs
     RS_HIP(hipMemcpyAsync(t->d_job, &job, sizeof(NodeJob), hipMemcpyHostToDevice, t->stream), "hipMemcpyAsync(job)");
     return RS_OK;
@@ -797,14 +780,14 @@ int rs_stream_probe(rs_table *t, size_t bytes, int reps, double *gbps) {
     if (bytes < (1u << 20) || reps < 1) return fail(RS_ERR_INVALID, "rs_stream_probe: at least 1 MiB and one repetition");
     bytes &= ~size_t(4095);
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    void *in = nullptr, *out = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipMalloc(&in, bytes);
-    if (e == hipSuccess) e = hipMalloc(&out, bytes);
+    DevBuf<char> in, out;
+    DevEvent a, b;
+    hipError_t e = in.alloc(bytes);
+    if (e == hipSuccess) e = out.alloc(bytes);
     if (e == hipSuccess) e = hipMemsetAsync(in, 1, bytes, t->stream);
     if (e == hipSuccess) e = hipMemsetAsync(out, 0, bytes, t->stream);
-    if (e == hipSuccess) e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventCreate(a.put());
+    if (e == hipSuccess) e = hipEventCreate(b.put());
     double best = 0.0;
     for (unsigned blocks : {1024u, 4096u, 16384u}) {
         if (e == hipSuccess) e = launch_probe_copy(in, out, bytes, blocks, t->stream);   // warm-up
@@ -816,10 +799,6 @@ int rs_stream_probe(rs_table *t, size_t bytes, int reps, double *gbps) {
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
         if (e == hipSuccess && ms > 0.0f) best = std::max(best, 2.0 * double(bytes) * reps / (double(ms) * 1e-3) / 1e9);
     }
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    if (in) (void)hipFree(in);
-    if (out) (void)hipFree(out);
     if (e != hipSuccess) return hip_fail(e, "rs_stream_probe");
     *gbps = best;
     return RS_OK;
@@ -828,10 +807,10 @@ int rs_stream_probe(rs_table *t, size_t bytes, int reps, double *gbps) {
 int rs_profile_mark(rs_table *t) {
     if (!t) return fail(RS_ERR_INVALID, "rs_profile_mark: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    hipEvent_t e = prof_event(t);
+    DevEvent e = prof_event(t);
     if (!e) return fail(RS_ERR_HIP, "rs_profile_mark: hipEventCreate failed");
     RS_HIP(hipEventRecord(e, t->stream), "hipEventRecord");
-    t->prof.marks.push_back(e);
+    t->prof.marks.push_back(std::move(e));
     return RS_OK;
 }
 int rs_profile_marks(rs_table *t, float *ms_out, size_t cap, size_t *n_out) {
@@ -842,7 +821,7 @@ int rs_profile_marks(rs_table *t, float *ms_out, size_t cap, size_t *n_out) {
     *n_out = n;
     hipError_t e = hipSuccess;
     for (size_t i = 0; i < n && i < cap && e == hipSuccess; ++i) e = hipEventElapsedTime(&ms_out[i], t->prof.marks[i], t->prof.marks[i + 1]);
-    for (hipEvent_t ev : t->prof.marks) t->prof.pool.push_back(ev);
+    for (DevEvent &ev : t->prof.marks) t->prof.pool.push_back(std::move(ev));
     t->prof.marks.clear();
     if (e != hipSuccess) return hip_fail(e, "rs_profile_marks");
     return RS_OK;

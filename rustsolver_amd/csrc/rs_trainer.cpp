@@ -21,11 +21,12 @@ struct rs_deal_trainer {
     int n_rounds = 0;
     rs_deal_trainer_params params{};
     uint32_t n_hands[2] = {0, 0};
-    uint8_t *d_hands[2] = {nullptr, nullptr};   // trainer.hand_ranges
-    uint8_t *d_cards = nullptr;                 // [9][pitch]
-    uint32_t *d_cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS] = {};
-    float *d_sign = nullptr;
-    uint32_t *d_err = nullptr;
+    // the device buffers, events and dealing stream below go with the object (rs_deal_trainer_destroy deletes it before the table)
+    DevBuf<uint8_t> d_hands[2];                 // trainer.hand_ranges
+    DevBuf<uint8_t> d_cards;                    // [9][pitch]
+    DevBuf<uint32_t> d_cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS];
+    DevBuf<float> d_sign;
+    DevBuf<uint32_t> d_err;
     uint64_t t = 0;                // iterations done (deals), the shared counter of cfr.rs:200
     uint64_t threshold = 0;        // next discount tick (cfr.rs:203)
     uint64_t batches = 0;
@@ -35,7 +36,7 @@ struct rs_deal_trainer {
     rs::BrRun *br_prepared[2] = {nullptr, nullptr};       // [pair loop, rank-order showdowns]: the game-only half of rs_best_response_rounds, kept between calls
     // train()'s prune schedule (cfr.rs:213-221): with a finite prune_threshold the solver runs in RS_UPD_PRUNE mode from the start and every
     // traverser visit honours the deal's flag byte -- all zero (= unpruned, bit for bit) until a batch reaches beyond the threshold
-    uint8_t *d_prune = nullptr;        // [pitch] flags of the live batch
+    DevBuf<uint8_t> d_prune;           // [pitch] flags of the live batch
     bool live_prune = false;           // the live batch has deals beyond the threshold
     uint64_t live_first = 0, staged_first = 0;   // global number of deal 0 of the live / staged batch
     int tick_br = 0;                   // calc_br at every discount tick (cfr.rs:244-246)
@@ -45,11 +46,11 @@ struct rs_deal_trainer {
     uint32_t world = 1, rank = 0;  // data-parallel training: this rank's share of every global batch
     // The NEXT batch is dealt (sample -> clusters -> showdown) into staging buffers on a second stream while the current one is swept -- the
     // sweep kernels leave most wave slots of a CU idle -- and swapped in with device-to-device copies.  Same deal numbers, same results.
-    hipStream_t deal_stream = nullptr;
-    hipEvent_t ev_dealt = nullptr, ev_taken = nullptr;
-    uint8_t *s_cards = nullptr;
-    uint32_t *s_cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS] = {};
-    float *s_sign = nullptr;
+    DevStream deal_stream;
+    DevEvent ev_dealt, ev_taken;
+    DevBuf<uint8_t> s_cards;
+    DevBuf<uint32_t> s_cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS];
+    DevBuf<float> s_sign;
     bool staged = false;           // the staging buffers hold the next batch (or will, once ev_dealt fires)
     bool taken_recorded = false;
     // Ordered sweeps walk 32-byte per-deal records sorted by the traverser's last-round cluster (rs_solver.cpp).  The records depend on the deals alone, so with a batch dealt
@@ -57,8 +58,8 @@ struct rs_deal_trainer {
     // sweeps that follow -- two sorts (0.43 + 0.06 ms per 4 M-deal batch) and the hand-over copies (0.09 ms; nothing in such a sweep reads the live arrays, they are filled on the
     // dealing stream for the accessors) leave the batch's critical path.  The solver asks before every sweep (before_sweep) whether its records are the live batch's.
     bool ahead = false;
-    uint8_t *s_prune = nullptr;        // prune flags of the staged batch
-    hipEvent_t ev_free[2] = {nullptr, nullptr}, ev_sorted[2] = {nullptr, nullptr}, ev_main = nullptr;
+    DevBuf<uint8_t> s_prune;           // prune flags of the staged batch
+    DevEvent ev_free[2], ev_sorted[2], ev_main;
     uint64_t arec_first[2] = {~uint64_t(0), ~uint64_t(0)};   // deal 0 of the batch whose records traverser p's buffer holds (or will, once ev_sorted[p] fires)
     bool wait_sorted[2] = {false, false};                    // the table's stream has not waited for ev_sorted[p] yet
 };
@@ -73,35 +74,12 @@ void rs_deal_trainer_destroy(rs_deal_trainer *tr) {
         if (tr->br_prepared[k]) rs::br_free(tr->br_prepared[k]);
     if (tr->deal_stream) (void)hipStreamSynchronize(tr->deal_stream);   // a sort dealt ahead may still be writing the solver's records
     if (tr->solver) rs_solver_destroy(tr->solver);
-    if (tr->table) {
-        if (tr->d_prune) rs_dfree(tr->table, tr->d_prune);
-        for (int p = 0; p < 2; ++p)
-            if (tr->d_hands[p]) rs_dfree(tr->table, tr->d_hands[p]);
-        if (tr->d_cards) rs_dfree(tr->table, tr->d_cards);
-        if (tr->d_sign) rs_dfree(tr->table, tr->d_sign);
-        if (tr->d_err) rs_dfree(tr->table, tr->d_err);
-        if (tr->deal_stream) (void)hipStreamSynchronize(tr->deal_stream);
-        if (tr->s_cards) rs_dfree(tr->table, tr->s_cards);
-        if (tr->s_sign) rs_dfree(tr->table, tr->s_sign);
-        if (tr->s_prune) rs_dfree(tr->table, tr->s_prune);
-        for (int p = 0; p < 2; ++p) {
-            if (tr->ev_free[p]) (void)hipEventDestroy(tr->ev_free[p]);
-            if (tr->ev_sorted[p]) (void)hipEventDestroy(tr->ev_sorted[p]);
-        }
-        if (tr->ev_main) (void)hipEventDestroy(tr->ev_main);
-        for (int r = 0; r < RS_MAX_ROUNDS; ++r)
-            for (int p = 0; p < RS_MAX_PLAYERS; ++p)
-                if (tr->s_cluster[r][p]) rs_dfree(tr->table, tr->s_cluster[r][p]);
-        if (tr->deal_stream) (void)hipStreamDestroy(tr->deal_stream);
-        if (tr->ev_dealt) (void)hipEventDestroy(tr->ev_dealt);
-        if (tr->ev_taken) (void)hipEventDestroy(tr->ev_taken);
-        for (int r = 0; r < RS_MAX_ROUNDS; ++r)
-            for (int p = 0; p < RS_MAX_PLAYERS; ++p)
-                if (tr->d_cluster[r][p]) rs_dfree(tr->table, tr->d_cluster[r][p]);
-        rs_table_destroy(tr->table);
-    }
-    if (tr->tree) rs_tree_destroy(tr->tree);
-    delete tr;
+    if (tr->table) (void)rs_sync(tr->table);   // nothing on the table's stream uses the trainer's buffers any more
+    rs_table *table = tr->table;
+    rs_tree *tree = tr->tree;
+    delete tr;   // its buffers, events and dealing stream, before the table they were made for
+    if (table) rs_table_destroy(table);
+    if (tree) rs_tree_destroy(tree);
 }
 
 int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, int n_rounds, const uint8_t *hands_p0, size_t n_hands_p0,
@@ -159,6 +137,11 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
         rc = fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_create: float tables (extension) take no pruning (prune_threshold = UINT64_MAX: cfr.rs:352 compares i32 regrets)");
     if (rc == RS_OK) rc = rs_create_infosets(tr->tree, n_clusters, n_boards, dtype, device, &tr->table);   // cfr.rs:176
     const size_t pitch = round_up(params->deals_per_batch, kLanePad);
+    auto dalloc = [device](auto &buf, size_t n) {   // n elements on the trainer's device
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = buf.alloc(n);
+        return e == hipSuccess ? RS_OK : hip_fail(e, "rs_deal_trainer_create: device buffers");
+    };
     const size_t n_hands[2] = {n_hands_p0, n_hands_p1};
     const uint8_t *hands[2] = {hands_p0, hands_p1};
     for (int p = 0; rc == RS_OK && p < 2; ++p) {
@@ -170,14 +153,14 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
             else if ((1ull << a | 1ull << b) & params->board_mask)
                 rc = fail(RS_ERR_INVALID, "rs_deal_trainer_create: a range combo uses a board card (remove_invalid_combos first, cfr.rs:163)");
         }
-        if (rc == RS_OK) rc = rs_dmalloc(tr->table, n_hands[p] * 2, reinterpret_cast<void **>(&tr->d_hands[p]));
+        if (rc == RS_OK) rc = dalloc(tr->d_hands[p], n_hands[p] * 2);
         if (rc == RS_OK) rc = rs_h2d(tr->table, tr->d_hands[p], hands[p], n_hands[p] * 2);
     }
-    if (rc == RS_OK) rc = rs_dmalloc(tr->table, 9 * pitch, reinterpret_cast<void **>(&tr->d_cards));
+    if (rc == RS_OK) rc = dalloc(tr->d_cards, 9 * pitch);
     if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_cards, 0, 9 * pitch);
-    if (rc == RS_OK) rc = rs_dmalloc(tr->table, pitch * sizeof(float), reinterpret_cast<void **>(&tr->d_sign));
+    if (rc == RS_OK) rc = dalloc(tr->d_sign, pitch);
     if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_sign, 0, pitch * sizeof(float));
-    if (rc == RS_OK) rc = rs_dmalloc(tr->table, 256, reinterpret_cast<void **>(&tr->d_err));
+    if (rc == RS_OK) rc = dalloc(tr->d_err, 64);
     if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_err, 0, 256);
     // staging for the batch dealt ahead; small batches are bound by the NUMBER of launches on the table's stream (about 5 us each), and swapping a
     // staged batch in costs more of them (four copies + the flags) than dealing in place (two kernels): no staging up to 256 K deals
@@ -187,43 +170,43 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
     // pays beyond 256 K deals (the river game as coded at 64 K deals: 0.10 against 0.12 s for 1 024 batches).
     const bool prefetch = params->prefetch == RS_FORM_ON || (params->prefetch != RS_FORM_OFF && params->deals_per_batch >= (n_rounds > 1 ? (1u << 16) : (1u << 18) + 1u));
     if (rc == RS_OK && prefetch) {
-        rc = rs_dmalloc(tr->table, 9 * pitch, reinterpret_cast<void **>(&tr->s_cards));
+        rc = dalloc(tr->s_cards, 9 * pitch);
         if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->s_cards, 0, 9 * pitch);
-        if (rc == RS_OK) rc = rs_dmalloc(tr->table, pitch * sizeof(float), reinterpret_cast<void **>(&tr->s_sign));
+        if (rc == RS_OK) rc = dalloc(tr->s_sign, pitch);
         if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->s_sign, 0, pitch * sizeof(float));
         for (int r = 0; rc == RS_OK && r < n_rounds; ++r)
             for (int p = 0; rc == RS_OK && p < 2; ++p) {
-                rc = rs_dmalloc(tr->table, pitch * sizeof(uint32_t), reinterpret_cast<void **>(&tr->s_cluster[r][p]));
+                rc = dalloc(tr->s_cluster[r][p], pitch);
                 if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->s_cluster[r][p], 0, pitch * sizeof(uint32_t));
             }
         if (rc == RS_OK) {
             hipError_t e = hipSetDevice(device);
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&tr->deal_stream, hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_dealt, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_taken, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipStreamCreateWithFlags(tr->deal_stream.put(), hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(tr->ev_dealt.put(), hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(tr->ev_taken.put(), hipEventDisableTiming);
             if (e != hipSuccess) rc = hip_fail(e, "rs_deal_trainer_create: dealing stream");
         }
-        if (rc == RS_OK) rc = rs_dmalloc(tr->table, pitch, reinterpret_cast<void **>(&tr->s_prune));
+        if (rc == RS_OK) rc = dalloc(tr->s_prune, pitch);
         if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->s_prune, 0, pitch);
         if (rc == RS_OK) {
             hipError_t e = hipSuccess;
             for (int p = 0; p < 2 && e == hipSuccess; ++p) {
-                e = hipEventCreateWithFlags(&tr->ev_free[p], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_sorted[p], hipEventDisableTiming);
+                e = hipEventCreateWithFlags(tr->ev_free[p].put(), hipEventDisableTiming);
+                if (e == hipSuccess) e = hipEventCreateWithFlags(tr->ev_sorted[p].put(), hipEventDisableTiming);
             }
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_main, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(tr->ev_main.put(), hipEventDisableTiming);
             if (e != hipSuccess) rc = hip_fail(e, "rs_deal_trainer_create: dealing stream events");
         }
         if (rc == RS_OK) rc = rs_sync(tr->table);   // the memsets above ran on the table's stream
     }
-    if (rc == RS_OK) rc = rs_dmalloc(tr->table, pitch, reinterpret_cast<void **>(&tr->d_prune));
+    if (rc == RS_OK) rc = dalloc(tr->d_prune, pitch);
     if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_prune, 0, pitch);
     rs_deal_batch batch{};
     batch.n_deals = params->deals_per_batch;
     batch.d_prune = tr->d_prune;
     for (int r = 0; rc == RS_OK && r < n_rounds; ++r)
         for (int p = 0; rc == RS_OK && p < 2; ++p) {
-            rc = rs_dmalloc(tr->table, pitch * sizeof(uint32_t), reinterpret_cast<void **>(&tr->d_cluster[r][p]));
+            rc = dalloc(tr->d_cluster[r][p], pitch);
             if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_cluster[r][p], 0, pitch * sizeof(uint32_t));
             batch.d_cluster[r][p] = tr->d_cluster[r][p];
         }
@@ -244,8 +227,7 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
         if (rc == RS_OK && tr->deal_stream && !tr->ahead && params->prefetch != RS_FORM_ON && params->deals_per_batch <= (1u << 18)) {
             // dealt ahead from 64 K deals on BECAUSE the records can be sorted ahead with it; sweeps that are not ordered (more last-round clusters than the sort has bins: the
             // lossless abstractions; a communicator) would swap every staged batch in with eight copies on the table's stream: up to 256 K deals they deal in place
-            (void)hipStreamDestroy(tr->deal_stream);
-            tr->deal_stream = nullptr;
+            tr->deal_stream.reset();
         }
     }
     if (rc != RS_OK) {
@@ -302,7 +284,7 @@ static int before_sweep(void *ctx, int p) {
 }
 
 // sample -> clusters -> showdown of batch number `tr->batches` into (cards, cluster, sign) on `stream`
-static int deal_into(rs_deal_trainer *tr, hipStream_t stream, uint8_t *cards, uint32_t *cluster[RS_MAX_ROUNDS][RS_MAX_PLAYERS], float *sign, uint64_t *first) {
+static int deal_into(rs_deal_trainer *tr, hipStream_t stream, uint8_t *cards, const DevBuf<uint32_t> (&cluster)[RS_MAX_ROUNDS][RS_MAX_PLAYERS], float *sign, uint64_t *first) {
     const uint32_t n = tr->params.deals_per_batch;
     const uint64_t first_deal = (tr->batches * tr->world + tr->rank) * uint64_t(n);   // global batch b = deals [b*world*n, (b+1)*world*n)
     *first = first_deal;
