@@ -596,15 +596,20 @@ void orc_discount_f32(float *regrets, float *ssum, int n, float d, int storage) 
     }
 }
 
-/* i32 tables, clamp arithmetic of cfr.rs:445-461, with the regret floored at 0 on write (RM+) */
-float orc_update_infoset_rmplus(int32_t *regrets, int32_t *ssum, int n, const float *utils, float cfr_reach,
-                                float scale) {
+/* i32 tables, clamp arithmetic of cfr.rs:445-461, with the regret floored at 0 on write (RM+).  Under prune only the explored actions
+ * (regret > -10M) enter util and are written, as in cfr.rs:379-386 / :415-441; the floor does not revive a pruned cell. */
+static float update_rmplus(int32_t *regrets, int32_t *ssum, int n, const float *utils, float cfr_reach, float scale, int prune) {
     float strategy[ORC_MAX_ACTIONS];
+    int explored[ORC_MAX_ACTIONS];
     float util = 0.0f;
     int i;
     orc_get_strategy(regrets, n, strategy);
-    for (i = 0; i < n; i++) util += utils[i] * strategy[i];
     for (i = 0; i < n; i++) {
+        explored[i] = !prune || regrets[i] > ORC_PRUNE_THRESHOLD;
+        if (explored[i]) util += utils[i] * strategy[i];
+    }
+    for (i = 0; i < n; i++) {
+        if (!explored[i]) continue;
         int64_t nr = wrapping_add_i64((int64_t)regrets[i], orc_f32_as_i64(scale * cfr_reach * (utils[i] - util)));
         int64_t ns = wrapping_add_i64((int64_t)ssum[i], orc_f32_as_i64(scale * cfr_reach * strategy[i]));
         nr = clamp_i64_to_i32(nr);
@@ -613,6 +618,11 @@ float orc_update_infoset_rmplus(int32_t *regrets, int32_t *ssum, int n, const fl
         ssum[i] = (int32_t)clamp_i64_to_i32(ns);
     }
     return util;
+}
+
+float orc_update_infoset_rmplus(int32_t *regrets, int32_t *ssum, int n, const float *utils, float cfr_reach,
+                                float scale) {
+    return update_rmplus(regrets, ssum, n, utils, cfr_reach, scale, 0);
 }
 
 /* ======================================================================================
@@ -741,8 +751,8 @@ float orc_traverse(const orc_ctx *ctx, int node_id, int player, uint32_t b, uint
                 utils[i] = orc_traverse(ctx, nd->children[i], player, b, c, cfr_reach); /* cfr.rs:578-581 */
             }
             if (is_int) {
-                if (ctx->rmplus) util = orc_update_infoset_rmplus(infoset->regrets, infoset->strategy_sum, n_actions,
-                                                                  utils, cfr_reach, ctx->scale);
+                if (ctx->rmplus) util = update_rmplus(infoset->regrets, infoset->strategy_sum, n_actions, utils, cfr_reach,
+                                                      ctx->scale, ctx->prune);
                 else util = orc_update_infoset(infoset->regrets, infoset->strategy_sum, n_actions, utils, cfr_reach,
                                                ctx->scale, ctx->mode, ctx->prune);
             } else {
@@ -824,7 +834,7 @@ float orc_traverse_deal(const orc_deal_ctx *dc, int node_id, int player, size_t 
             }
             memcpy(r, infoset->regrets, (size_t)n_actions * sizeof(int32_t));
             memcpy(s, infoset->strategy_sum, (size_t)n_actions * sizeof(int32_t));
-            if (ctx->rmplus) util = orc_update_infoset_rmplus(r, s, n_actions, utils, cfr_reach, ctx->scale);
+            if (ctx->rmplus) util = update_rmplus(r, s, n_actions, utils, cfr_reach, ctx->scale, prune);
             else util = orc_update_infoset(r, s, n_actions, utils, cfr_reach, ctx->scale, ctx->mode, prune);
             for (i = 0; i < n_actions; i++) { /* delta against the snapshot value, accumulated with wrapping adds */
                 dinfo->regrets[i] = wrapping_add_i32(dinfo->regrets[i], (int32_t)((uint32_t)r[i] - (uint32_t)infoset->regrets[i]));
