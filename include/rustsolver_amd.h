@@ -300,7 +300,10 @@ typedef struct rs_kernel_forms {
                                    one pass per round adds them straight into the TABLE once the round's walks are done (atomic adds at the key row's clusters) -- no delta-table
                                    entries, no share of the apply pass for those nodes.  Default: on; data-parallel deal batches exchange the delta TABLES between sweep and apply
                                    and must switch it off (rs_solver_attach_comm refuses a solver that has it on; rs_deal_trainer does so for world > 1) */
-    int32_t reserved[1];        /* zero */
+    int32_t pair_sweeps;        /* RS_FORM_*: lane solvers whose traverser plans are one chance-free subtree kernel each (fused river trees, PASS chance, one rank) walk BOTH
+                                   traversers per lane in one launch, every node's regrets carried in registers from the first walk to the second: 612 instead of 776 bytes per
+                                   lane and iteration on the 14-node river tree.  rs_iterate(.., 0, ..) then holds its sweep until rs_iterate(.., 1, ..) (see there).  Default: on.
+                                   (ABI 6 had `reserved` in this slot: a zeroed struct means what it meant.) */
 } rs_kernel_forms;
 
 typedef struct rs_solver_params {
@@ -360,7 +363,11 @@ int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_b
                            const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out);
 void rs_solver_destroy(rs_solver *solver);
 /* one traverser sweep over every lane: `self.cfr(0, player, hand, 1f32, ..)` (cfr.rs:217) for all lanes.
- * d_root_util[pitch of the root round] (NULL = discard) receives the value returned at node 0. */
+ * d_root_util[pitch of the root round] (NULL = discard) receives the value returned at node 0.
+ * Paired solvers (rs_solver_forms bit 2, rs_kernel_forms.pair_sweeps): rs_iterate(s, 0, u0) HOLDS the sweep and only records it, u0 included; the next
+ * rs_iterate(s, 1, u1) runs both sweeps as one launch and writes u0 and u1.  Any other entry point that takes the solver, its table or a trainer over it (rs_sync and
+ * rs_stream included, and every solver's rs_iterate on the same table) first issues a held sweep on its own, so results are those of two separate sweeps whatever
+ * comes in between.  u0 must stay valid until then.  A host that launches work of its own on a stream pointer it cached earlier must call rs_sync or rs_stream first. */
 int rs_iterate(rs_solver *solver, int traverser, float *d_root_util);
 /* MCCFRTrainer::train (cfr.rs:188-265), deterministic: per iteration both traversers sweep, t += 1, then
  * the discount check `t > threshold` (d = p/(p+1), p = t/interval) until t > discount_cap. */
@@ -391,7 +398,8 @@ size_t rs_solver_workspace_bytes(const rs_solver *solver);
 int rs_jit_available(void);   /* 1 if libhiprtc.so can be loaded (needed for fuse_subtrees) */
 int rs_solver_n_launches(const rs_solver *solver, int traverser);
 /* which kernel forms the solver chose (rs_kernel_forms): bit 0 = deal sweeps walk the batch in last-round-cluster order (deal_order), bit 1 = some round subtree
-   stores delta rows (delta_rows); negative = bad solver */
+   stores delta rows (delta_rows), bit 2 = both traversers' lane sweeps run as one pair launch (pair_sweeps; rs_solver_n_launches then counts them under traverser 0);
+   negative = bad solver */
 int rs_solver_forms(const rs_solver *solver);
 
 /* ---- card-abstraction plumbing in front of get-infoset (host only; card_abstraction.rs) -----------------------------

@@ -55,6 +55,8 @@ int rs_jit_check_tree(const rs_tree *tree, int dtype, int mode, int opp_mode, in
 /* the same for deal batches (rs_solver_create_deals): the kernels of every round subtree -- reach-down half and table-updating walk, dense and
  * over a live-deal list, with and without LDS tiles */
 int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_kernels);
+/* the pair kernel (rs_kernel_forms.pair_sweeps: both traversers of a lane sweep in one walk per lane) of every topmost chance-free subtree, generated and compiled the same way */
+int rs_jit_check_pair(const rs_tree *tree, int dtype, int mode, int opp_mode, int *n_kernels);
 
 /* ---- self-test of the short exact division regret matching uses on i32 tables (rs_device.hpp div_exact_pos) against the compiler's f32 division, on the device:
  * n hashed (regret, sum) pairs; *mismatches must be 0.  first_bad (may be NULL): [2] = the first differing pair. */

@@ -60,7 +60,7 @@ class DealBatch(C.Structure):
 
 class KernelForms(C.Structure):   # rs_kernel_forms: every field 0 = the engine's own choice
     _fields_ = [("lane_fan", C.c_int32), ("deals_per_thread", C.c_int32), ("kept_records", C.c_int32), ("shadow", C.c_int32),
-                ("deal_order", C.c_int32), ("delta_rows", C.c_int32), ("direct_rows", C.c_int32), ("reserved", C.c_int32 * 1)]
+                ("deal_order", C.c_int32), ("delta_rows", C.c_int32), ("direct_rows", C.c_int32), ("pair_sweeps", C.c_int32)]
 
 
 class TableParams(C.Structure):
@@ -174,6 +174,7 @@ SYMBOLS = {
     "rs_jit_available": (C.c_int, []),
     "rs_jit_check_tree": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rs_jit_check_tree_deals": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "rs_jit_check_pair": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rs_cluster_file_read": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]),
     "rs_cluster_file_write": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_size_t]),
     "rs_free_u32": (None, [C.POINTER(C.c_uint32)]),

@@ -693,6 +693,7 @@ int rs_hand_unindex(const rs_hand_indexer *ix, int round, const uint64_t *indice
 
 // get_index for a batch on the device: d_cards[n_cards(round)][pitch] u8 (row i = card i of the hand), pitch = round_up(n, 64)
 int rs_hand_index_device(rs_table *t, rs_hand_indexer *ix, int round, const uint8_t *d_cards, uint32_t n, uint64_t *d_out) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !ix || !d_cards || !d_out) return fail(RS_ERR_INVALID, "rs_hand_index_device: NULL argument");
     if (round < 0 || round >= ix->rounds) return fail(RS_ERR_OOB, "rs_hand_index_device: round out of range");
     HandIndexView v;
@@ -872,6 +873,7 @@ int rs_card_abs_get_cluster(const rs_card_abs *a, const uint8_t *cards, size_t n
 // (the layout of rs_showdown_sign).  d_cluster_p0 / d_cluster_p1 [pitch] (either may be NULL).  Asynchronous; a deal whose bucket has no
 // dense id raises the abstraction's error word, reported by rs_card_abs_status.
 int rs_card_abs_clusters_device(rs_card_abs *a, rs_table *t, const uint8_t *d_cards, uint32_t n_deals, uint32_t *d_cluster_p0, uint32_t *d_cluster_p1) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     return rs::card_abs_clusters_on(a, t, t ? t->stream : nullptr, d_cards, n_deals, d_cluster_p0, d_cluster_p1);
 }
 }  // extern "C" (interrupted: the stream-taking forms below are internal)
@@ -963,6 +965,7 @@ extern "C" {
 
 // synchronises and reports (then clears) what the device kernels flagged since the last call
 int rs_card_abs_status(rs_card_abs *a, rs_table *t) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!a || !t) return fail(RS_ERR_INVALID, "rs_card_abs_status: NULL argument");
     rs_card_abs::Dev dev;
     if (int rc = abs_device(a, t, &dev)) return rc;
@@ -981,6 +984,7 @@ int rs_card_abs_status(rs_card_abs *a, rs_table *t) {
 // rand 0.7 Standard for f32: 24 high bits of a u32 times 2^-24.  The draw is counter kSampleMaxDraws of the deal's hash (generate_hand never
 // gets that far); t = the deal's global number (iterations completed before it in the sequential reading).
 int rs_deals_prune_flags(rs_table *t, uint64_t seed, uint64_t first_deal, uint64_t prune_threshold, uint32_t n_deals, uint8_t *d_flags) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     return rs::deal_prune_flags_on(t, t ? t->stream : nullptr, seed, first_deal, prune_threshold, n_deals, d_flags);
 }
 
@@ -989,6 +993,7 @@ int rs_deals_prune_flags(rs_table *t, uint64_t seed, uint64_t first_deal, uint64
 // the counter hash (seed, first_deal + i).  d_cards[9][pitch] as above.  d_err (may be NULL): bit 2 raised when a deal found no valid combo.
 int rs_deals_sample(rs_table *t, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
                     const uint8_t *d_hands_p1, uint32_t n_hands_p1, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     return rs::deals_sample_on(t, t ? t->stream : nullptr, seed, first_deal, board_mask, d_hands_p0, n_hands_p0, d_hands_p1, n_hands_p1, n_deals, d_cards, d_err,
                                nullptr, nullptr, 0);
 }

@@ -89,6 +89,7 @@ int rs_comm_unique_id(void *id_out) {
 }
 
 int rs_comm_create(rs_table *table, const void *id, int rank, int n_ranks, rs_comm **out) {
+    if (int rc_ = rs::table_settle(table, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!table || !id || !out || n_ranks < 1 || rank < 0 || rank >= n_ranks)
         return fail(RS_ERR_INVALID, "rs_comm_create: bad argument");
     Rccl *r = rccl();
@@ -124,6 +125,7 @@ void rs_comm_destroy(rs_comm *c) {
 // in-place all-gather of the exchange buffer [n_ranks][bytes_per_rank]: rank r contributes its r-th slot (xGMI: every rank
 // sends its slot to 7 peers over dedicated links; the slots are ~MBs, so the call is latency-bound)
 int rs_comm_allgather(rs_comm *c, rs_table *t, void *d_buf, size_t bytes_per_rank) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!c || !t || !d_buf) return fail(RS_ERR_INVALID, "rs_comm_allgather: NULL argument");
     if (bytes_per_rank % 4 != 0) return fail(RS_ERR_INVALID, "rs_comm_allgather: slot size must be a multiple of 4 bytes");
     Rccl *r = rccl();
@@ -139,6 +141,7 @@ int rs_comm_allgather(rs_comm *c, rs_table *t, void *d_buf, size_t bytes_per_ran
 // data-parallel deal batches: every rank swept its own deals into its delta tables; one in-place wrapping sum (ncclInt32) per
 // array makes them the deltas of the UNION batch on every rank (integer adds commute: any rank count, any order, same bits)
 int rs_comm_allreduce_deltas(rs_comm *c, rs_table *t) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!c || !t) return fail(RS_ERR_INVALID, "rs_comm_allreduce_deltas: NULL argument");
     if (!t->d_dregrets || !t->d_dssum) return fail(RS_ERR_INVALID, "rs_comm_allreduce_deltas: the table has no delta tables (rs_solver_create_deals makes them)");
     Rccl *r = rccl();
@@ -175,6 +178,7 @@ int comm_allgather_u32(rs_comm *c, rs_table *t, const void *d_send, void *d_recv
 extern "C" {
 
 int rs_replicated_begin(rs_table *t, uint32_t round_mask) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_replicated_begin: table is NULL");
     if (t->dtype == RS_F16) return fail(RS_ERR_UNSUPPORTED, "rs_replicated_begin: RS_F16 tables are not reduced (use RS_F32 accumulators)");
     hipError_t e = hipSetDevice(t->device);
@@ -216,6 +220,7 @@ int rs_replicated_begin(rs_table *t, uint32_t round_mask) {
 }
 
 int rs_allreduce_replicated(rs_table *t, rs_comm *c, uint32_t round_mask) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !c) return fail(RS_ERR_INVALID, "rs_allreduce_replicated: NULL argument");
     if (t->rep_mask != round_mask || t->rep_nodes.empty())
         return fail(RS_ERR_INVALID, "rs_allreduce_replicated: call rs_replicated_begin with the same round_mask first");

@@ -88,6 +88,7 @@ template <> struct Row<kDT_I32> {
         for (int j = 0; j < kVecD; j++) RS_STOREG(in[j], as_global<int>((int *)base + row_off) + v * kVecD + j);
 #endif
     }
+    static __device__ __forceinline__ void carry(val (&)[kVecD]) {}   // the value a store and a load give back: the register's own
 };
 template <> struct Row<kDT_F32> {
     using val = float;
@@ -107,6 +108,7 @@ template <> struct Row<kDT_F32> {
         for (int j = 0; j < kVecD; j++) RS_STOREG(in[j], as_global<float>((float *)base + row_off) + v * kVecD + j);
 #endif
     }
+    static __device__ __forceinline__ void carry(val (&)[kVecD]) {}
 };
 template <> struct Row<kDT_F16> {
     using val = float;  // binary16 in HBM, f32 in registers
@@ -125,6 +127,11 @@ template <> struct Row<kDT_F16> {
 #else
         for (int j = 0; j < kVecD; j++) RS_STOREG((_Float16)in[j], as_global<_Float16>((_Float16 *)base + row_off) + v * kVecD + j);
 #endif
+    }
+    // a value kept in registers past its store (rs_jit.cpp pair kernels) is what the next load of it would give: rounded to binary16 (RNE) and widened again
+    static __device__ __forceinline__ void carry(val (&x)[kVecD]) {
+#pragma unroll
+        for (int j = 0; j < kVecD; j++) x[j] = (float)(_Float16)x[j];
     }
 };
 

@@ -257,6 +257,7 @@ hipError_t launch_member_lists(const uint32_t *keys, size_t n, uint32_t k, uint3
                                uint32_t *members /* [n] */, hipStream_t stream);
 hipError_t launch_showdown_sign(const uint8_t *cards, float *sign, uint32_t n, uint32_t pitch, hipStream_t stream);
 hipError_t launch_next_seed(uint64_t *d_state /* {base, call_index, seed} */, hipStream_t stream);
+hipError_t launch_next_seed_pair(uint64_t *d_state /* {base, call_index, seed, seed of the pair's first walk} */, hipStream_t stream);
 hipError_t launch_probe_copy(const void *in, void *out, size_t bytes, unsigned blocks, hipStream_t stream);   // rs_stream_probe
 hipError_t launch_prune_reach(const NodeJob *d_jobs, int n_jobs, uint32_t max_n_vec,
                               int n_actions, KernelCfg cfg, hipStream_t stream);
@@ -294,6 +295,8 @@ struct Knobs {
     int ordered = kUnset;           // RS_JIT_ORDERED / deal_order: 1 on / 0 off
     int rows = kUnset;              // RS_JIT_ROWS / delta_rows: 1 on / 0 off (delta rows by list position + one summing pass per round)
     int direct_rows = kUnset;       // RS_JIT_DIRECT_ROWS / direct_rows: 1 on / 0 off
+    int waves = kUnset;             // RS_JIT_WAVES: pair kernels, waves per SIMD the register allocation is held to
+    int pair = kUnset;              // pair_sweeps: 1 on / 0 off (lane solvers with one chance-free subtree kernel per traverser walk both traversers in one launch)
     // test-only: forms the engine picks by size, forced onto small inputs
     int rows_chunk = kUnset;        // RS_JIT_ROWS_CHUNK: list entries one workgroup of the summing pass takes (small values: several chunks per row)
     int scan_all = kUnset;          // RS_JIT_SCAN_ALL: 0 = a root's live deals are compacted from its parent's lists (what batches beyond 64 K deals get), 1 = from the whole batch
@@ -358,12 +361,22 @@ struct JitSubtree {
     size_t off_c0 = 0, off_rcount = 0, off_rp = 0;                                         // the cluster range a job's LDS tiles cover
     size_t off_fan = 0, off_inv = 0, off_cvec = 0;                                        // lane sweeps: deals below the ENUM chance node the kernel walks itself
     std::vector<int> boundary_roots;   // tree id of every next-round root below this subtree, in the order of butil[] / breach[]
+    bool pair = false;                 // a pair kernel (JitPair) whose two walks index nodes, leaves and constants alike: entry(jobs[2], flags, out0, out1)
 };
 // staged rows (rs_device.hpp stage_rows): the shadow rows of a round subtree as the generated kernel needs to know them -- structure only, no addresses
 struct JitStage {
     int ch[2] = {0, 0};       // per PLAYER: 16-byte chunks of a row of that player's nodes in this round subtree (0: the kernel reads none)
     int chp[2] = {0, 0};      // the same in LDS: ch rounded up to an odd number
     std::vector<int> off;     // per tree node: ints from the start of its row to its record
+};
+// pair kernels (lane sweeps of a chance-free subtree): what traverser 1's walk is generated from.  The kernel's JArgs are TWO blobs of the single kernels' layout,
+// traverser 0's then traverser 1's; `ok` says whether both walks index nodes, leaves and constants alike (else there is no pair kernel)
+constexpr int kPairWaves = 1;   // ... and the waves per SIMD their registers are held to (RS_JIT_WAVES overrides; 1 = the compiler's choice)
+constexpr int kPairLanes = 2;   // lanes per thread of the pair kernels (RS_JIT_LANES overrides): NOTES.md, pair sweeps
+struct JitPair {
+    const std::vector<char> *has_own = nullptr;
+    const std::vector<int> *leaf_buf = nullptr, *leaf_flags = nullptr;
+    bool ok = false;
 };
 constexpr int kStageMaxChunks = 16;   // rows beyond 256 bytes keep their gathers (64 deals x 17 chunks x 16 B = 17 KB of LDS per wave)
 void jit_emit_subtree(const std::vector<rs_tree_node> &nodes, int root, int p, const std::vector<char> &has_own,
@@ -372,7 +385,8 @@ void jit_emit_subtree(const std::vector<rs_tree_node> &nodes, int root, int p, c
                       bool posrows = false, bool worklist = false, bool ordered = false, bool seg = false, bool rows = false,
                       const std::vector<char> *sigma = nullptr /* per tree node: its shadow record holds the strategy (opponent nodes of a deal sweep) */,
                       bool handoff = false /* deal sweeps: the reach-down kernel stores its draws by list position, the walk reads them (both kernels of a root alike) */,
-                      const JitStage *stage = nullptr /* list walkers, one deal per lane: the subtree's records come from rows the wave stages in LDS */);
+                      const JitStage *stage = nullptr /* list walkers, one deal per lane: the subtree's records come from rows the wave stages in LDS */,
+                      const struct JitPair *pair = nullptr /* lane sweeps, p = 0: the kernel walks traverser 1 right after traverser 0 (rs_jit.cpp, pair kernels) */);
 bool jit_available();
 int jit_get_kernel(const std::string &source, const std::string &entry, int device, hipFunction_t *fn, bool dump = false);
 uint64_t jit_source_key(const std::string &source);   // what the caches are keyed by (source + compiler version + options)
@@ -474,7 +488,9 @@ void solver_table_discounted(struct rs_solver *s, float d, uint64_t epoch_before
 int solver_kept_primary(struct rs_solver *s, bool on);
 constexpr uint64_t kKeptPrimaryMinTrips = 16;   // training loops shorter than this leave the table's rows the working copy (the write-back at the end would cost more than it saves)
 bool solver_is_primary(const struct rs_solver *s);
-int table_settle(rs_table *t);   // rs_table.cpp: the table's rows up to date before anything reads or writes them (a training loop's working copy written back)
+int solver_settle_held(struct rs_solver *s);   // rs_solver.cpp: a held traverser-0 sweep of a paired solver issued as the plain traverser-0 plan
+int solvers_settle_held(rs_table *t, const struct rs_solver *except);   // ... of every solver on the table but `except`
+int table_settle(rs_table *t, bool rows = true);   // rs_table.cpp: the table's rows up to date before anything reads or writes them (a training loop's working copy written back)
 // rs_comm.cpp: the collectives of a data-parallel deal sweep (rs_solver.cpp solver_exchange_deltas)
 int comm_world(const struct rs_comm *c);
 int comm_rank(const struct rs_comm *c);

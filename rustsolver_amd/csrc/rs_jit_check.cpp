@@ -210,4 +210,48 @@ int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_
     return RS_OK;
 }
 
+// the pair kernel (rs_solver.cpp setup_pair: both traversers of a lane sweep in one walk per lane) of every topmost chance-free subtree of `tree`, one shared sign buffer
+// per round as above
+int rs_jit_check_pair(const rs_tree *tree, int dtype, int mode, int opp_mode, int *n_kernels) {
+    if (!tree || tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_jit_check_pair: bad tree");
+    const std::vector<rs_tree_node> &nodes = tree->nodes;
+    const size_t n = nodes.size();
+    const Knobs knobs = knobs_resolve(nullptr);
+    std::vector<char> has_own[2] = {std::vector<char>(n, 0), std::vector<char>(n, 0)}, closed(n, 0);
+    std::vector<int> leaf_buf(n, -1), leaf_flags(n, 0);
+    for (size_t i = n; i-- > 0;) {   // children have larger ids than parents
+        const rs_tree_node &nd = nodes[i];
+        bool cl = nd.kind != RS_NODE_PUBLIC_CHANCE && nd.kind != RS_NODE_PRIVATE_CHANCE;
+        for (int p = 0; p < 2; ++p) {
+            bool own = nd.kind == RS_NODE_ACTION && nd.player == p;
+            for (int k = 0; k < nd.n_children; ++k) own = own || has_own[p][nd.children[k]];
+            has_own[p][i] = own;
+        }
+        for (int k = 0; k < nd.n_children; ++k) cl = cl && closed[nd.children[k]];
+        closed[i] = cl;
+        if (nd.kind == RS_NODE_TERMINAL && nd.ttype != RS_TERM_UNCONTESTED) {
+            leaf_buf[i] = nd.round;
+            leaf_flags[i] = 1;
+        }
+    }
+    std::map<std::string, int> seen;
+    for (size_t i = 0; i < n; ++i) {
+        const rs_tree_node &nd = nodes[i];
+        if (nd.kind != RS_NODE_ACTION || !closed[i] || nd.n_children == 0) continue;
+        if (nd.parent >= 0 && nodes[nd.parent].kind == RS_NODE_ACTION && closed[nd.parent]) continue;   // not topmost
+        JitPair jp;
+        jp.has_own = &has_own[1];
+        jp.leaf_buf = &leaf_buf;
+        jp.leaf_flags = &leaf_flags;
+        JitSubtree js;
+        jit_emit_subtree(nodes, int(i), 0, has_own[0], leaf_buf, leaf_flags, dtype, mode & RS_UPD_ARITH_MASK, opp_mode == RS_OPP_SAMPLE, false, false, false, false,
+                         (mode & RS_UPD_PRUNE) != 0, 4, nullptr, js, knobs, 0, false, false, false, false, false, false, nullptr, false, nullptr, &jp);
+        if (!js.pair) return fail(RS_ERR_INVALID, "rs_jit_check_pair: the two walks of a pair kernel index the subtree differently");
+        seen[js.source] = 1;
+    }
+    if (int rc = jit_compile_many(seen, knobs.dump != 0)) return rc;
+    if (n_kernels) *n_kernels = int(seen.size());
+    return RS_OK;
+}
+
 }  // extern "C"

@@ -726,6 +726,15 @@ __global__ void k_next_seed(uint64_t *state) {
         state[1] += 1;
     }
 }
+// the pair kernel of a chance-free lane tree walks both traversers in one launch: the seeds of the two sweeps, in the order two k_next_seed launches make them
+// (state[3] = traverser 0's, state[2] = traverser 1's), and the state left where they leave it
+__global__ void k_next_seed_pair(uint64_t *state) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        state[3] = sweep_seed(state[0], state[1]);
+        state[2] = sweep_seed(state[0], state[1] + 1);
+        state[1] += 2;
+    }
+}
 template <int DT>
 __global__ __launch_bounds__(kBlock) void k_fill_random(void *__restrict__ dst, size_t n, uint64_t seed, int64_t lo,
                                                         uint64_t span) {
@@ -1423,6 +1432,11 @@ hipError_t launch_probe_copy(const void *in, void *out, size_t bytes, unsigned b
 
 hipError_t launch_next_seed(uint64_t *d_state, hipStream_t stream) {
     hipLaunchKernelGGL(k_next_seed, dim3(1), dim3(64), 0, stream, d_state);
+    return hipGetLastError();
+}
+
+hipError_t launch_next_seed_pair(uint64_t *d_state, hipStream_t stream) {
+    hipLaunchKernelGGL(k_next_seed_pair, dim3(1), dim3(64), 0, stream, d_state);
     return hipGetLastError();
 }
 

@@ -717,6 +717,7 @@ int rs_histogram_distance(int dist, const float *p, const float *q, int n_bins, 
 // buffers, either may be NULL.  Asynchronous on the table's stream (the table only lends its device and stream).
 int rs_kmeans_predict(rs_table *t, int dist, const float *d_dataset, size_t n, const float *centers, int n_centers, int n_bins, uint32_t *d_clusters,
                       float *d_min_dist) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = check_args("rs_kmeans_predict", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
     if (!d_clusters && !d_min_dist) return RS_OK;
     const int nb = padded_bins(n_bins);
@@ -749,6 +750,7 @@ int rs_kmeans_predict(rs_table *t, int dist, const float *d_dataset, size_t n, c
 
 // update_min_dists (kmeans.rs:603-619), the kmeans++ step: d_min_dists[i] = min(d_min_dists[i], dist(dataset[i], new_center)^2); center on the HOST
 int rs_update_min_dists(rs_table *t, int dist, float *d_min_dists, const float *d_dataset, size_t n, const float *new_center, int n_bins) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = check_args("rs_update_min_dists", t, dist, d_dataset, n, new_center, 1, n_bins)) return rc;
     if (!d_min_dists && n) return fail(RS_ERR_INVALID, "rs_update_min_dists: NULL argument");
     const int nb = padded_bins(n_bins);
@@ -780,6 +782,7 @@ int rs_update_min_dists(rs_table *t, int dist, float *d_min_dists, const float *
 
 // the member lists of the float deal apply (launch_member_lists), on caller-owned DEVICE buffers; allocates and frees its own scratch, synchronises
 int rs_member_lists(rs_table *t, const uint32_t *d_keys, size_t n, uint32_t k, uint32_t *d_start, uint32_t *d_members) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_start || (n && (!d_keys || !d_members))) return fail(RS_ERR_INVALID, "rs_member_lists: NULL argument");
     if (k == 0 || n > 0xffffffffull) return fail(RS_ERR_INVALID, "rs_member_lists: k must be at least 1 and n below 2^32");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
@@ -969,6 +972,7 @@ extern "C" {
 // scores them exactly as coded -- per restart, distances[i] = sum over j != i of dist(c_i, c_j), sum over i, divided by the k (k - 1) pairs (:133-147) -- and returns
 // the index of the maximum (the LAST of equal maxima: Iterator::max_by, :151-156).  centers: HOST [n_restarts][k][n_bins]; cluster_dists: HOST out [n_restarts], may be NULL.
 int rs_kmeans_pick_restart(rs_table *t, int dist, const float *centers, int n_restarts, int n_centers, int n_bins, float *cluster_dists, int *best) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!best || n_restarts < 1) return fail(RS_ERR_INVALID, "rs_kmeans_pick_restart: bad argument");
     if (int rc = check_args("rs_kmeans_pick_restart", t, dist, centers, 0, centers, n_centers, n_bins)) return rc;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
@@ -1002,6 +1006,7 @@ int rs_kmeans_pick_restart(rs_table *t, int dist, const float *centers, int n_re
 
 // Kmeans::init_s (kmeans.rs:267-285) for callers that drive the loop themselves: s (HOST, in/out, n_centers floats) is only ever lowered, then halved
 int rs_kmeans_init_s(rs_table *t, int dist, const float *centers, int n_centers, int n_bins, float *s) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = check_args("rs_kmeans_init_s", t, dist, centers, 0, centers, n_centers, n_bins)) return rc;
     if (!s) return fail(RS_ERR_INVALID, "rs_kmeans_init_s: s is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
@@ -1018,6 +1023,7 @@ int rs_kmeans_init_s(rs_table *t, int dist, const float *centers, int n_centers,
 // in place; d_order (DEVICE, may be NULL): datum i is dataset[d_order[i]]; centers and s on the HOST.  Synchronises.
 int rs_kmeans_reassign(rs_table *t, int dist, const float *d_dataset, const uint32_t *d_order, size_t n, const float *centers, int n_centers, int n_bins, const float *s,
                        uint32_t *d_clusters, float *d_bounds) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = check_args("rs_kmeans_reassign", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
     if (!s || ((!d_clusters || !d_bounds) && n)) return fail(RS_ERR_INVALID, "rs_kmeans_reassign: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
@@ -1038,6 +1044,7 @@ int rs_kmeans_reassign(rs_table *t, int dist, const float *d_dataset, const uint
 // inertia: HOST out, may be NULL (sum of the upper bounds / n as printed at :594).  Synchronises.
 int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t n, float *centers, int n_centers, int n_bins, int iterations, uint32_t *d_clusters,
                           float *d_bounds, float *inertia) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = fit_check("rs_kmeans_fit_regular", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
     if (!d_clusters || iterations < 1) return fail(RS_ERR_INVALID, "rs_kmeans_fit_regular: d_clusters is NULL or iterations < 1");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
@@ -1076,6 +1083,7 @@ int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t 
 // centers: HOST in/out; d_clusters [batch] / d_bounds [batch][2]: DEVICE out; stats: HOST out {min_change p (:466-471), inertia as printed (:478)}, may be NULL.
 int rs_kmeans_fit_growbatch(rs_table *t, int dist, const float *d_dataset, size_t n, const uint32_t *d_order, size_t batch, float *centers, int n_centers, int n_bins,
                             uint32_t *d_clusters, float *d_bounds, float *stats) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (int rc = fit_check("rs_kmeans_fit_growbatch", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
     if (!d_order || !d_clusters || !d_bounds || batch == 0 || batch > n) return fail(RS_ERR_INVALID, "rs_kmeans_fit_growbatch: NULL argument or batch outside 1..n");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");

@@ -1,6 +1,6 @@
 // rs_knobs.cpp -- the ONE place where the library reads switches from the environment.
 //
-// A caller chooses kernel forms through the API (rs_kernel_forms in rs_solver_params, rs_table_params, rs_deal_trainer_params.prefetch).  The sixteen variables below
+// A caller chooses kernel forms through the API (rs_kernel_forms in rs_solver_params, rs_table_params, rs_deal_trainer_params.prefetch).  The eighteen variables below
 // exist for the test-suite and the profiling tools: each forces a form that the engine otherwise picks by batch or table size (so that small test inputs meet the forms big
 // inputs get), or switches a facility off that has a fallback (staged rows, helper processes, launch overlap); they are resolved once per solver / table / trainer, at its
 // creation.  Round 4 removed twenty-four more: forms measured as losers went with their code (the whole-deal-loop lane kernels, dense walks on delta rows, wide opponent
@@ -23,6 +23,8 @@ const Entry kEntries[] = {
     {"RS_JIT_LANES", INT, &Knobs::lanes, nullptr},
     {"RS_JIT_ORDERED", INT, &Knobs::ordered, nullptr},
     {"RS_JIT_ROWS", INT, &Knobs::rows, nullptr},
+    {"RS_JIT_PAIR", BOOL, &Knobs::pair, nullptr},
+    {"RS_JIT_WAVES", INT, &Knobs::waves, nullptr},
     {"RS_JIT_ROWS_CHUNK", INT, &Knobs::rows_chunk, nullptr},
     {"RS_JIT_DUMP", FLAG, &Knobs::dump, nullptr},
     {"RS_JIT_SCAN_ALL", INT, &Knobs::scan_all, nullptr},
@@ -52,6 +54,8 @@ Knobs knobs_resolve(const rs_kernel_forms *forms) {
         if (forms->direct_rows == RS_FORM_ON) k.direct_rows = 1;
         else if (forms->direct_rows == RS_FORM_OFF) k.direct_rows = 0;
         if (forms->kept_records == RS_FORM_OFF) k.no_kept = 1;
+        if (forms->pair_sweeps == RS_FORM_ON) k.pair = 1;
+        else if (forms->pair_sweeps == RS_FORM_OFF) k.pair = 0;
     }
     for (const Entry &e : kEntries) {   // then the test-only overrides
         const char *v = getenv(e.name);

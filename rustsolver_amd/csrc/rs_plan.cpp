@@ -501,6 +501,15 @@ int PlanBuilder::add_jit_job(int id, bool down, const std::vector<int> &sparse_s
         plan.jit.back().deals_per_trip = uint32_t(js.threads * js.lanes);
     }
     JitLaunch &JL = plan.jit[bi->second];
+    // a candidate for the pair kernel: a lane sweep's chance-free subtree walked by one plain generated kernel (no next-round roots, no fan, one cluster range)
+    plan.pair_src.n_jobs += int(parts.first);
+    if (!s->deal_mode && !down && js.boundary_roots.empty() && !fan_root[id] && parts.first == 1 && js.lanes == 4) {
+        plan.pair_src.root = id;
+        plan.pair_src.jit = bi->second;
+        plan.pair_src.has_own = has_own;
+        plan.pair_src.leaf_buf = leaf_buf;
+        plan.pair_src.leaf_flags = leaf_flags;
+    }
     for (uint32_t part = 0; part < parts.first; ++part) {   // one job per cluster range (one in all unless the tiles had to be partitioned)
     const size_t base = JL.blob.size();
     JL.blob.resize(base + js.args_size, 0);

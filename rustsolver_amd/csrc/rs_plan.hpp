@@ -124,6 +124,13 @@ struct Plan {
     size_t arena_bytes = 0;
     const float *root_util = nullptr;   // inside the arena
     size_t root_lanes = 0;
+    // lane sweeps: what a pair kernel (rs_solver.cpp setup_pair) is generated from -- the chance-free subtree this plan's one generated kernel walks, and that kernel's
+    // emitter inputs.  root < 0: no such subtree (or more than one generated launch)
+    struct PairSrc {
+        int root = -1, jit = -1, n_jobs = 0;
+        std::vector<char> has_own;
+        std::vector<int> leaf_buf, leaf_flags;
+    } pair_src;
     DevGraph graph;                     // last: destroyed before the buffers it launches on, the executable first
     DevGraphExec graph_exec;
 };
@@ -259,6 +266,20 @@ struct rs_solver : rs::SolverDevice {
     int first_round = 0;                // betting round of the first action node: its subtree walks the whole batch and keeps its tiles unless RS_JIT_ROWS = 2
     bool deal_mode = false;             // lanes are deals (rs_solver_create_deals)
     rs_deal_batch deals{};
+    // Pair sweeps (rs_kernel_forms.pair_sweeps): lane solvers whose traverser plans are one chance-free subtree kernel each walk both traversers in ONE launch
+    // (rs_jit.cpp pair kernels).  rs_iterate(s, 0) HOLDS that sweep (held, held_util); rs_iterate(s, 1) then issues the pair.  Anything else issues a held sweep as the plain
+    // traverser-0 plan first (solver_settle_held: table_settle, rs_sync, rs_stream, destroy, another solver's sweep on the table).
+    struct Pair {
+        bool on = false;
+        rs::JitLaunch jit;              // two argument blobs: traverser 0's plan's, traverser 1's (the seed pointer of the first moved to d_seed_state[3])
+        double bytes = 0.0;             // algorithmic bytes without the root utilities; + 4 per lane for each one written
+        size_t lanes = 0;
+        bool held = false;
+        float *held_util = nullptr;
+        rs::DevGraph graph;             // use_graph: captured for the root-utility pointers below
+        rs::DevGraphExec graph_exec;
+        float *graph_out[2] = {nullptr, nullptr};
+    } pair;
     const uint64_t *d_seed() const { return d_seed_state ? d_seed_state + 2 : nullptr; }
 };
 

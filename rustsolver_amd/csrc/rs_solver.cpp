@@ -240,6 +240,55 @@ static int run_plan_inner(rs_solver *s, int p, int phase) {
     return run_range(s, plan, lo, hi);
 }
 
+// both traversers' sweeps of a paired solver in one launch (rs_solver::Pair); u0 / u1: the callers' root utilities (written by the kernel itself), may be null
+int issue_pair(rs_solver *s, float *u0, float *u1) {
+    rs_table *t = s->table;
+    rs_solver::Pair &P = s->pair;
+    if (s->params.opp_mode == RS_OPP_SAMPLE) RS_HIP(launch_next_seed_pair(s->d_seed_state, t->stream), "k_next_seed_pair");
+    prof_begin(t, RS_K_TREE, P.bytes + 4.0 * double(P.lanes) * ((u0 ? 1.0 : 0.0) + (u1 ? 1.0 : 0.0)));
+    size_t blocks = std::min<size_t>(std::max<size_t>((size_t(P.jit.max_n_vec) + P.jit.threads - 1) / P.jit.threads, 1), 256 * 16);
+    if (s->knobs.max_blocks != kUnset) blocks = std::max<size_t>(1, std::min<size_t>(blocks, size_t(std::max(1, s->knobs.max_blocks))));
+    const void *d_blob = P.jit.d_blob;
+    int flags = s->params.mode & ~RS_UPD_ARITH_MASK;
+    void *params[] = {&d_blob, &flags, &u0, &u1};
+    const hipError_t e = hipModuleLaunchKernel(P.jit.fn, (unsigned)blocks, 1, 1, (unsigned)P.jit.threads, 1, 1, 0, t->stream, params, nullptr);
+    prof_end(t);
+    RS_HIP(e, "pair launch");
+    return RS_OK;
+}
+int run_pair(rs_solver *s, float *u0, float *u1) {
+    rs_table *t = s->table;
+    rs_solver::Pair &P = s->pair;
+    if (s->params.use_graph && !t->prof.on) {   // one graph per pair of root-utility pointers (callers pass the same ones every step, or none)
+        if (!P.graph_exec || P.graph_out[0] != u0 || P.graph_out[1] != u1) {
+            P.graph_exec.reset();
+            P.graph.reset();
+            RS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
+            const int rc = issue_pair(s, u0, u1);
+            hipError_t e = hipStreamEndCapture(t->stream, P.graph.put());
+            if (rc != RS_OK) return rc;
+            RS_HIP(e, "hipStreamEndCapture");
+            RS_HIP(hipGraphInstantiate(P.graph_exec.put(), P.graph, nullptr, nullptr, 0), "hipGraphInstantiate");
+            P.graph_out[0] = u0;
+            P.graph_out[1] = u1;
+        }
+        RS_HIP(hipGraphLaunch(P.graph_exec, t->stream), "hipGraphLaunch");
+    } else if (int rc = issue_pair(s, u0, u1)) return rc;
+    t->epoch += 2;   // two sweeps' worth of table writes
+    return RS_OK;
+}
+int copy_root(rs_solver *s, int traverser, float *d_root_util) {
+    if (d_root_util && s->ordered) {   // the sweep's lanes are ranks of its order: hand the utilities out by deal id
+        RS_HIP(launch_unpermute_f32(s->plan[traverser].root_util, s->d_arec_p[traverser], d_root_util, s->deals.n_deals, s->table->stream), "rs_iterate: root util by deal id");
+        return RS_OK;
+    }
+    if (d_root_util)
+        RS_HIP(hipMemcpyAsync(d_root_util, s->plan[traverser].root_util, s->plan[traverser].root_lanes * sizeof(float),
+                              hipMemcpyDeviceToDevice, s->table->stream),
+               "rs_iterate: root util copy");
+    return RS_OK;
+}
+
 
 }  // namespace
 
@@ -343,9 +392,26 @@ int rs::solver_discount_primary(rs_solver *s, float d) {
     return RS_OK;
 }
 
+// A held traverser-0 sweep (rs_solver::Pair) goes out as the plain traverser-0 plan: whatever comes next sees the table and the root utility as two separate sweeps leave them
+int rs::solver_settle_held(rs_solver *s) {
+    if (!s || !s->table || !s->pair.held) return RS_OK;
+    s->pair.held = false;
+    RS_HIP(hipSetDevice(s->table->device), "hipSetDevice");
+    if (int rc = run_plan(s, 0)) return rc;
+    return copy_root(s, 0, s->pair.held_util);
+}
+int rs::solvers_settle_held(rs_table *t, const rs_solver *except) {
+    if (!t) return RS_OK;
+    for (rs_solver *o : t->solvers)
+        if (o != except)
+            if (int rc = solver_settle_held(o)) return rc;
+    return RS_OK;
+}
+
 void rs::solver_release_device(rs_solver *s) {
     if (!s || !s->table) return;   // already detached (its table was destroyed first)
     rs_table *t = s->table;
+    (void)solver_settle_held(s);
     (void)hipSetDevice(t->device);
     (void)hipStreamSynchronize(t->stream);
     if (s->primary) {   // the table's rows back from the records BEFORE anything they live in is freed (k_unbuild_shadow reads d_shadow through d_kept_jobs)
@@ -357,6 +423,10 @@ void rs::solver_release_device(rs_solver *s) {
         pl.graph.reset();
         pl = Plan{};
     }
+    s->pair.graph_exec.reset();
+    s->pair.graph.reset();
+    s->pair.jit = JitLaunch{};
+    s->pair.on = false;
     static_cast<SolverDevice &>(*s) = SolverDevice{};
     s->d_arec = nullptr;
     for (void *&a : s->d_attr) a = nullptr;
@@ -866,6 +936,72 @@ static int trim_packed_records(rs_solver *s) {
 }
 
 
+// Pair sweeps (rs_kernel_forms.pair_sweeps, default on): a lane solver whose two traverser plans are each ONE generated kernel over the same chance-free subtree
+// (plus the seed launch of sampled sweeps) gets a third kernel that walks both traversers per lane, carrying every node's regrets in registers from the first walk to
+// the second: each regret row is read once and written once per iteration instead of being read twice (rs_jit.cpp).  Not for deal batches (the second sweep reads the
+// table after every deal's deltas are summed), ENUM chance nodes (traverser 1's river reach depends on ALL of traverser 0's river utilities), sharded sweeps or the level plan.
+static void setup_pair(rs_solver *s) {
+    const rs_table *t = s->table;
+    if (s->knobs.pair == 0 || s->deal_mode || s->sharded || !s->params.fuse_subtrees || s->before_sweep) return;
+    const Plan::PairSrc &ps0 = s->plan[0].pair_src, &ps1 = s->plan[1].pair_src;
+    for (int p = 0; p < 2; ++p) {
+        const Plan &pl = s->plan[p];
+        const Plan::PairSrc &ps = pl.pair_src;
+        if (ps.root < 0 || ps.root != ps0.root || ps.n_jobs != 1 || pl.jit.size() != 1) return;
+        int trees = 0;
+        for (const Launch &L : pl.launches) {
+            if (L.kind == L_TREE && L.first_job == ps.jit) ++trees;
+            else if (L.kind != L_SEED) return;
+        }
+        const JitLaunch &JL = pl.jit[size_t(ps.jit)];
+        if (trees != 1 || JL.n_jobs != 1 || !JL.members.empty() || JL.lds_bytes || JL.worklist || JL.blob.size() != JL.stride) return;
+    }
+    const JitLaunch &J0 = s->plan[0].jit[size_t(ps0.jit)], &J1 = s->plan[1].jit[size_t(ps1.jit)];
+    JitPair jp;
+    jp.has_own = &ps1.has_own;
+    jp.leaf_buf = &ps1.leaf_buf;
+    jp.leaf_flags = &ps1.leaf_flags;
+    JitSubtree js;
+    const bool sampled = s->params.opp_mode == RS_OPP_SAMPLE;
+    jit_emit_subtree(s->tree.nodes, ps0.root, 0, ps0.has_own, ps0.leaf_buf, ps0.leaf_flags, t->dtype, s->params.mode & RS_UPD_ARITH_MASK, sampled, false, false, false, false,
+                     (s->params.mode & RS_UPD_PRUNE) != 0, 4, nullptr, js, s->knobs, 0, false, false, false, false, false, false, nullptr, false, nullptr, &jp);
+    if (!js.pair || js.args_size != J0.stride || J1.stride != J0.stride || js.threads != J0.threads || J0.max_n_vec != J1.max_n_vec) return;
+    rs_solver::Pair &P = s->pair;
+    P.jit.source = js.source;
+    P.jit.entry = js.entry;
+    P.jit.src_off[0] = js.src_struct;
+    P.jit.src_off[1] = js.src_entry;
+    P.jit.src_off[2] = js.src_body;
+    P.jit.stride = js.args_size;
+    P.jit.threads = js.threads;
+    P.jit.n_jobs = 2;
+    P.jit.max_n_vec = J0.max_n_vec * uint32_t(4 / js.lanes);   // the single kernels' vectors are 4 lanes wide
+    P.jit.blob = J0.blob;
+    P.jit.blob.insert(P.jit.blob.end(), J1.blob.begin(), J1.blob.end());
+    if (sampled) {   // the first walk's seed: d_seed_state[3] (k_next_seed_pair)
+        const uint64_t *first = s->d_seed_state + 3;
+        std::memcpy(P.jit.blob.data() + js.off_seed, &first, sizeof(first));
+    }
+    // algorithmic bytes per lane: every row of every node read once and written once (traverser 1's regrets: written only), the strategy sums of both: 4 * S rows in all;
+    // the leaf rows of the first walk and those of the second that differ; reach rows where they are buffers.  Root utilities: + 4 B per lane each, counted per launch.
+    P.lanes = size_t(P.jit.max_n_vec) * size_t(js.lanes);
+    const double es = double(elem_size(t->dtype));
+    double per_lane = 0.0;
+    for (int id : js.node_ids) per_lane += 4.0 * es * s->tree.nodes[size_t(id)].n_children;
+    for (size_t i = 0; i < js.leaf_terms.size(); ++i) {
+        const void *l0 = nullptr, *l1 = nullptr;
+        std::memcpy(&l0, J0.blob.data() + js.off_leaf + 8 * i, 8);
+        std::memcpy(&l1, J1.blob.data() + js.off_leaf + 8 * i, 8);
+        per_lane += l0 == l1 ? 4.0 : 8.0;
+    }
+    for (const JitLaunch *J : {&J0, &J1}) {
+        const void *r = nullptr;
+        std::memcpy(&r, J->blob.data() + js.off_reach, 8);
+        if (r) per_lane += 4.0;
+    }
+    P.bytes = double(P.lanes) * per_lane;
+}
+
 static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
                               const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out) {
     if (!table || !tree || !leaves_p0 || !leaves_p1 || !params || !out)
@@ -922,8 +1058,8 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
     hipError_t e = hipSetDevice(table->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (params->opp_mode == RS_OPP_SAMPLE) {
-        const uint64_t init[3] = {params->sample_seed, 0, 0};
-        if ((e = s->d_seed_state.alloc(3, &s->dev_bytes)) != hipSuccess ||
+        const uint64_t init[4] = {params->sample_seed, 0, 0, 0};
+        if ((e = s->d_seed_state.alloc(4, &s->dev_bytes)) != hipSuccess ||
             (e = hipMemcpy(s->d_seed_state, init, sizeof(init), hipMemcpyHostToDevice)) != hipSuccess)
             return hip_fail(e, "rs_solver_create: seed state");
     }
@@ -958,11 +1094,13 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
     }
     if ((rc = plan_builder_emit(pb[0].get())) != RS_OK || (rc = plan_builder_emit(pb[1].get())) != RS_OK) return rc;
     if ((rc = merge_small_groups(s)) != RS_OK) return rc;
+    setup_pair(s);
     {   // the generated kernels of both plans: compiled together (concurrently where no cache has them), then bound to their launches
         std::vector<JitRequest> reqs;
         for (int p = 0; p < 2; ++p)
             for (JitLaunch &JL : s->plan[p].jit)
                 if (!JL.absorbed) reqs.push_back(JitRequest{&JL.source, &JL.entry, nullptr});
+        if (!s->pair.jit.source.empty()) reqs.push_back(JitRequest{&s->pair.jit.source, &s->pair.jit.entry, nullptr});
         if (!reqs.empty() && (rc = jit_get_kernels(reqs, table->device, s->knobs.dump != 0)) != RS_OK) return rc;
         size_t k = 0;
         for (int p = 0; p < 2; ++p)
@@ -970,6 +1108,14 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
                 if (!JL.absorbed) JL.fn = reqs[k++].fn;
                 JL.source = std::string();
             }
+        if (!s->pair.jit.source.empty()) {
+            s->pair.jit.fn = reqs[k++].fn;
+            s->pair.jit.source = std::string();
+            if ((e = s->pair.jit.d_blob.alloc(s->pair.jit.blob.size(), &s->dev_bytes)) != hipSuccess ||
+                (e = hipMemcpyAsync(s->pair.jit.d_blob, s->pair.jit.blob.data(), s->pair.jit.blob.size(), hipMemcpyHostToDevice, table->stream)) != hipSuccess)
+                return hip_fail(e, "rs_solver_create: pair-kernel argument upload");
+            s->pair.on = s->pair.jit.fn != nullptr;
+        }
     }
     for (int p = 0; p < 2; ++p) {
         Plan &pl = s->plan[p];
@@ -1031,17 +1177,6 @@ void rs_solver_destroy(rs_solver *s) {
     delete s;
 }
 
-static int copy_root(rs_solver *s, int traverser, float *d_root_util) {
-    if (d_root_util && s->ordered) {   // the sweep's lanes are ranks of its order: hand the utilities out by deal id
-        RS_HIP(launch_unpermute_f32(s->plan[traverser].root_util, s->d_arec_p[traverser], d_root_util, s->deals.n_deals, s->table->stream), "rs_iterate: root util by deal id");
-        return RS_OK;
-    }
-    if (d_root_util)
-        RS_HIP(hipMemcpyAsync(d_root_util, s->plan[traverser].root_util, s->plan[traverser].root_lanes * sizeof(float),
-                              hipMemcpyDeviceToDevice, s->table->stream),
-               "rs_iterate: root util copy");
-    return RS_OK;
-}
 
 // The buffers of the direct rows' items, all or nothing: fresh ones, moved in (and item_cap raised) once both exist.  A failure keeps what was there.
 static int grow_items(rs_solver *s, uint32_t cap, size_t world, const char *what) {
@@ -1182,6 +1317,17 @@ int rs_iterate(rs_solver *s, int traverser, float *d_root_util) {
     if (!s->table) return fail(RS_ERR_INVALID, "rs_iterate: the solver's table has been destroyed");
     if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_iterate: traverser must be 0 or 1");
     RS_HIP(hipSetDevice(s->table->device), "hipSetDevice");
+    if (s->pair.on && traverser == 1 && s->pair.held) {   // the held traverser-0 sweep and this one: one pair launch
+        if (int rc = solvers_settle_held(s->table, s)) return rc;
+        s->pair.held = false;
+        return run_pair(s, s->pair.held_util, d_root_util);
+    }
+    if (int rc = solvers_settle_held(s->table, nullptr)) return rc;   // a sweep held by any solver on this table (this one's included) goes first
+    if (s->pair.on && traverser == 0) {   // held until traverser 1's sweep comes, or anything else does
+        s->pair.held = true;
+        s->pair.held_util = d_root_util;
+        return RS_OK;
+    }
     if (s->sharded) {
         if (!s->comm) return fail(RS_ERR_INVALID, "rs_iterate: sharded solver without a communicator: rs_solver_attach_comm, or drive the "
                                                   "phases with rs_iterate_phase and exchange the slots yourself");
@@ -1220,6 +1366,7 @@ int rs_iterate_phase(rs_solver *s, int traverser, int phase, float *d_root_util)
         return fail(RS_ERR_UNSUPPORTED, "rs_iterate_phase: a float-table deal solver under a communicator exchanges per-deal delta items and sums them in global deal order "
                                         "inside rs_iterate; a host driving the phases has no delta tables to exchange (float sums do not associate): call rs_iterate");
     RS_HIP(hipSetDevice(s->table->device), "hipSetDevice");
+    if (int rc = solvers_settle_held(s->table, nullptr)) return rc;
     if (s->before_sweep && phase == 0)
         if (int rc = s->before_sweep(s->before_sweep_ctx, traverser)) return rc;
     if (int rc = run_plan(s, traverser, phase)) return rc;
@@ -1227,6 +1374,7 @@ int rs_iterate_phase(rs_solver *s, int traverser, int phase, float *d_root_util)
 }
 
 int rs_solver_attach_comm(rs_solver *s, rs_comm *comm) {
+    if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!s) return fail(RS_ERR_INVALID, "rs_solver_attach_comm: solver is NULL");
     if (comm && s->order_ahead) return fail(RS_ERR_UNSUPPORTED, "rs_solver_attach_comm: this solver's deal records are sorted ahead by its trainer (one GPU); attach the communicator through rs_deal_trainer_attach_comm before the first batch");
     if (comm && s->deal_mode && s->table && s->table->dtype == RS_I32) {   // the buffers of solver_exchange_deltas
@@ -1314,6 +1462,7 @@ int rs_solver_exchange_info(rs_solver *s, int traverser, void **d_buf, size_t *b
 }
 
 int rs_solver_training_loop(rs_solver *s, int on) {
+    if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!s) return fail(RS_ERR_INVALID, "rs_solver_training_loop: solver is NULL");
     if (!s->table) return fail(RS_ERR_INVALID, "rs_solver_training_loop: the solver's table has been destroyed");
     return solver_kept_primary(s, on != 0);
@@ -1350,8 +1499,9 @@ int rs_solver_exchange_bytes(const rs_solver *s, uint64_t *bytes, uint64_t *swee
     *sweeps = s->dp_sweeps;
     return RS_OK;
 }
-int rs_solver_forms(const rs_solver *s) { return s ? ((s->ordered ? 1 : 0) | (s->rows ? 2 : 0)) : RS_ERR_INVALID; }
+int rs_solver_forms(const rs_solver *s) { return s ? ((s->ordered ? 1 : 0) | (s->rows ? 2 : 0) | (s->pair.on ? 4 : 0)) : RS_ERR_INVALID; }
 int rs_solver_walk_counts(rs_solver *s, int traverser, uint64_t *out) {
+    if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!s || !s->table || !out || traverser < 0 || traverser > 1) return fail(RS_ERR_INVALID, "rs_solver_walk_counts: bad argument");
     if (!s->deal_mode) return fail(RS_ERR_INVALID, "rs_solver_walk_counts: not a deal-batch solver");
     const Plan &plan = s->plan[traverser];
@@ -1369,6 +1519,7 @@ int rs_solver_walk_counts(rs_solver *s, int traverser, uint64_t *out) {
 
 int rs_solver_n_launches(const rs_solver *s, int traverser) {
     if (!s || traverser < 0 || traverser > 1) return RS_ERR_INVALID;
+    if (s->pair.on) return traverser == 0 ? 1 + (s->params.opp_mode == RS_OPP_SAMPLE ? 1 : 0) : 0;   // one pair launch (and its seed launch) per iteration
     return int(s->plan[traverser].launches.size());
 }
 

@@ -74,8 +74,12 @@ double algo_bytes_update(const rs_table *t, int node, int n_buf_children, bool h
 // A training loop may have made a solver's kept shadow records the working copy (rs_solver.cpp solver_kept_primary): the table's rows of those nodes are stale until they are
 // written back.  Every entry point that reads or writes table contents settles that first -- rows written back, the records no longer the working copy (the loop goes on with table
 // and records both updated, as outside a loop) -- so that nothing ever reads stale rows or loses what a loop has trained.
-int table_settle(rs_table *t) {
+// A paired lane solver may hold a traverser-0 sweep (rs_solver.cpp rs_iterate): it goes out first, in every entry point that takes the table or a solver or trainer over it --
+// those that only wait for the stream or hand it out included (rows = false: the kept records stay the working copy).
+int table_settle(rs_table *t, bool rows) {
     if (!t) return RS_OK;
+    if (int rc = solvers_settle_held(t, nullptr)) return rc;
+    if (!rows) return RS_OK;
     for (rs_solver *s : t->solvers)
         if (solver_is_primary(s))
             if (int rc = solver_kept_primary(s, false)) return rc;
@@ -260,6 +264,7 @@ int rs_create_infosets(const rs_tree *tree, const uint32_t n_clusters[RS_MAX_ROU
 
 void rs_table_destroy(rs_table *t) {
     if (!t) return;
+    (void)table_settle(t, false);
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     while (!t->solvers.empty()) solver_release_device(t->solvers.back());   // they stay valid handles, but inert
@@ -286,7 +291,10 @@ size_t rs_table_cell_offset(const rs_table *t, int node) {
     return t->cell_off[node];
 }
 size_t rs_table_bytes(const rs_table *t) { return t ? 2 * t->n_cells * elem_size(t->dtype) : 0; }
-void *rs_stream(rs_table *t) { return t ? (void *)t->stream : nullptr; }
+void *rs_stream(rs_table *t) {
+    if (!t || table_settle(t, false) != RS_OK) return nullptr;
+    return (void *)t->stream;
+}
 
 // ---- host <-> device ------------------------------------------------------------------------------------------
 static int board_copy(rs_table *t, int node, int board, void *regrets, void *ssum, int dir, const char *fn) {
@@ -389,6 +397,7 @@ int rs_get_infosets(rs_table *t, int node, const uint32_t *lanes, size_t n, void
 // div_exact_pos (rs_device.hpp: the division of regret matching on i32 tables without the scale / fix-up instructions) against the compiler's `a / b` on n hashed
 // pairs from its domain: *mismatches must come back 0; first_bad (may be NULL) = the first differing (a, b)
 int rs_selftest_division(rs_table *t, size_t n, uint64_t seed, uint64_t *mismatches, float *first_bad) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !mismatches) return fail(RS_ERR_INVALID, "rs_selftest_division: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     DevBuf<char> d;
@@ -488,12 +497,14 @@ int rs_table_plant_saturating(rs_table *t, uint64_t seed, uint32_t one_in) {
     return RS_OK;
 }
 int rs_plant_outliers_f32(rs_table *t, float *d_dst, size_t n, uint64_t seed, uint32_t one_in, float magnitude) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_dst || one_in == 0) return fail(RS_ERR_INVALID, "rs_plant_outliers_f32: bad argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(launch_plant_outliers(d_dst, n, seed, one_in, magnitude, t->stream), "plant_outliers");
     return RS_OK;
 }
 int rs_fill_uniform_f32_at(rs_table *t, float *d_dst, size_t n, uint64_t seed, float lo, float hi, uint64_t index_offset) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_dst) return fail(RS_ERR_INVALID, "rs_fill_uniform_f32_at: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(launch_fill_uniform(d_dst, n, seed, lo, hi, t->stream, size_t(index_offset)), "fill_uniform");
@@ -537,6 +548,7 @@ int rs_table_checksum_logical(rs_table *t, const uint64_t *lane_off, uint64_t *o
     return logical_sweep(t, lane_off, 1, 0, 0, 0, 0, 0, out, "rs_table_checksum_logical");
 }
 int rs_fill_uniform_f32(rs_table *t, float *d_dst, size_t n, uint64_t seed, float lo, float hi) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_dst) return fail(RS_ERR_INVALID, "rs_fill_uniform_f32: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(launch_fill_uniform(d_dst, n, seed, lo, hi, t->stream), "fill_uniform");
@@ -545,12 +557,14 @@ int rs_fill_uniform_f32(rs_table *t, float *d_dst, size_t n, uint64_t seed, floa
 
 // ---- device memory helpers ------------------------------------------------------------------------------------------
 int rs_dmalloc(rs_table *t, size_t bytes, void **d_out) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_out) return fail(RS_ERR_INVALID, "rs_dmalloc: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipMalloc(d_out, bytes ? bytes : 1), "hipMalloc");
     return RS_OK;
 }
 int rs_dfree(rs_table *t, void *d_ptr) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_dfree: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
@@ -570,6 +584,7 @@ int rs_table_deltas(rs_table *t, int32_t **d_dregrets, int32_t **d_dssum) {
     return RS_OK;
 }
 int rs_h2d(rs_table *t, void *d_dst, const void *src, size_t bytes) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_dst || !src) return fail(RS_ERR_INVALID, "rs_h2d: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, t->stream), "hipMemcpyAsync(h2d)");
@@ -577,6 +592,7 @@ int rs_h2d(rs_table *t, void *d_dst, const void *src, size_t bytes) {
     return RS_OK;
 }
 int rs_d2h(rs_table *t, void *dst, const void *d_src, size_t bytes) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !dst || !d_src) return fail(RS_ERR_INVALID, "rs_d2h: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, t->stream), "hipMemcpyAsync(d2h)");
@@ -584,6 +600,7 @@ int rs_d2h(rs_table *t, void *dst, const void *d_src, size_t bytes) {
     return RS_OK;
 }
 int rs_dmemset(rs_table *t, void *d_dst, int byte, size_t bytes) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_dst) return fail(RS_ERR_INVALID, "rs_dmemset: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipMemsetAsync(d_dst, byte, bytes, t->stream), "hipMemsetAsync");
@@ -591,6 +608,7 @@ int rs_dmemset(rs_table *t, void *d_dst, int byte, size_t bytes) {
 }
 int rs_sync(rs_table *t) {
     if (!t) return fail(RS_ERR_INVALID, "rs_sync: table is NULL");
+    if (int rc = table_settle(t, false)) return rc;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
     return RS_OK;
@@ -729,6 +747,7 @@ float rs_discount_factor(uint64_t tc, uint64_t interval) {  // cfr.rs:248-249
 }
 
 int rs_discount(rs_table *t, float d) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_discount: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     for (rs_solver *s : t->solvers)
@@ -749,6 +768,7 @@ int rs_discount(rs_table *t, float d) {
 
 // ---- showdown signs from cards ------------------------------------------------------------------------------
 int rs_showdown_sign(rs_table *t, const uint8_t *d_cards, uint32_t n_deals, float *d_sign) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !d_cards || !d_sign) return fail(RS_ERR_INVALID, "rs_showdown_sign: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     const uint32_t pitch = uint32_t(round_up(n_deals, kLanePad));
@@ -758,6 +778,7 @@ int rs_showdown_sign(rs_table *t, const uint8_t *d_cards, uint32_t n_deals, floa
 
 // ---- profiling ----------------------------------------------------------------------------------------------------------------
 int rs_profile_enable(rs_table *t, int on) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_profile_enable: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
@@ -766,6 +787,7 @@ int rs_profile_enable(rs_table *t, int on) {
     return RS_OK;
 }
 int rs_profile_read(rs_table *t, rs_profile *out) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !out) return fail(RS_ERR_INVALID, "rs_profile_read: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
@@ -776,6 +798,7 @@ int rs_profile_read(rs_table *t, rs_profile *out) {
 // The streaming rate this card reaches on a plain float4 copy (read `bytes`, write `bytes`), best of a few grid sizes: the practical ceiling
 // the update kernels are compared with beside the 8 TB/s specification (cards of one pool differ by more than 10 %).
 int rs_stream_probe(rs_table *t, size_t bytes, int reps, double *gbps) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !gbps) return fail(RS_ERR_INVALID, "rs_stream_probe: NULL argument");
     if (bytes < (1u << 20) || reps < 1) return fail(RS_ERR_INVALID, "rs_stream_probe: at least 1 MiB and one repetition");
     bytes &= ~size_t(4095);
@@ -805,6 +828,7 @@ int rs_stream_probe(rs_table *t, size_t bytes, int reps, double *gbps) {
 }
 // step boundaries of bench.py's timed region: one event per mark on the table's stream, durations between consecutive marks
 int rs_profile_mark(rs_table *t) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_profile_mark: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     DevEvent e = prof_event(t);
@@ -814,6 +838,7 @@ int rs_profile_mark(rs_table *t) {
     return RS_OK;
 }
 int rs_profile_marks(rs_table *t, float *ms_out, size_t cap, size_t *n_out) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t || !n_out || (!ms_out && cap)) return fail(RS_ERR_INVALID, "rs_profile_marks: NULL argument");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");
@@ -827,6 +852,7 @@ int rs_profile_marks(rs_table *t, float *ms_out, size_t cap, size_t *n_out) {
     return RS_OK;
 }
 int rs_profile_reset(rs_table *t) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!t) return fail(RS_ERR_INVALID, "rs_profile_reset: table is NULL");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     RS_HIP(hipStreamSynchronize(t->stream), "hipStreamSynchronize");

@@ -486,6 +486,7 @@ size_t rs_deal_trainer_br_bytes(const rs_deal_trainer *tr) {
     return b;
 }
 int rs_deal_trainer_br_release(rs_deal_trainer *tr) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_br_release: trainer is NULL");
     for (int k = 0; k < 2; ++k) rs::br_release_workspace(tr->br_prepared[k]);
     return RS_OK;
@@ -495,6 +496,7 @@ int rs_deal_trainer_br_launches(const rs_deal_trainer *tr, int sorted) {   // la
 }
 
 int rs_deal_trainer_attach_comm(rs_deal_trainer *tr, rs_comm *comm) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_attach_comm: trainer is NULL");
     if (comm && tr->ahead) {   // sweeps under a communicator run phase by phase and sort their records themselves
         if (!solver_order_ahead(tr->solver, false, nullptr, nullptr))
@@ -531,6 +533,7 @@ int rs_deal_trainer_train(rs_deal_trainer *tr, uint64_t n_batches) {
 
 // synchronises; fails if any deal since the last call could not be sampled or addressed (the reference would spin or panic)
 int rs_deal_trainer_status(rs_deal_trainer *tr) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_status: trainer is NULL");
     uint32_t err = 0;
     if (tr->deal_stream && hipStreamSynchronize(tr->deal_stream) != hipSuccess) return fail(RS_ERR_HIP, "rs_deal_trainer_status: dealing stream");

@@ -589,6 +589,11 @@ class MCCFRTrainer:
         return bool(L.load().rs_solver_forms(self._h) & 1)
 
     @property
+    def paired(self):
+        """both traversers' sweeps run as one pair launch per iteration (rs_kernel_forms.pair_sweeps)"""
+        return bool(L.load().rs_solver_forms(self._h) & 4)
+
+    @property
     def delta_rows(self):
         """deal sweeps store their deltas by list position and sum them in one pass per sweep (rs_kernel_forms.delta_rows)"""
         return bool(L.load().rs_solver_forms(self._h) & 2)
@@ -832,6 +837,13 @@ def jit_check_tree(tree, dtype=L.I32, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_FULL)
     """compile (no GPU needed) every tree-specialised kernel of `tree`; returns the number of distinct kernels"""
     n = C.c_int()
     L.check(L.load().rs_jit_check_tree(tree._h, dtype, mode, opp_mode, C.byref(n)))
+    return n.value
+
+
+def jit_check_pair(tree, dtype=L.I32, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_FULL):
+    """compile (no GPU needed) the pair kernel (both traversers in one walk per lane) of every topmost chance-free subtree of `tree`; returns the number of distinct kernels"""
+    n = C.c_int()
+    L.check(L.load().rs_jit_check_pair(tree._h, dtype, mode, opp_mode, C.byref(n)))
     return n.value
 
 
