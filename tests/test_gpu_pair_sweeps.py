@@ -8,6 +8,7 @@ import pytest
 
 import rustsolver_amd as rs
 from rustsolver_amd import _lib as L
+from test_gpu_walk_restated import assert_same, edge_float, edge_i32, edge_utils, float_utils
 
 pytestmark = pytest.mark.gpu
 ON, OFF = {"pair_sweeps": L.FORM_ON}, {"pair_sweeps": L.FORM_OFF}
@@ -95,6 +96,61 @@ def test_pair_on_equals_pair_off(case, size):
         table.destroy()
     same_state(outs[0][0], outs[1][0])
     assert outs[0][1] == outs[1][1], "root utilities differ"
+
+
+# Edge inputs (tests/test_gpu_walk_restated.py), pair ON against pair OFF.  The float ones overflow on BOTH players' nodes in the first iteration, so the second reads
+# sigma = inf / inf = NaN: what a NaN reach does is the convention both forms share (test_float_nan_reach_still_updates), and they must still agree bit for bit -- the
+# inputs test_pair_float_edges_lanes has to keep away from the numpy walk.  The i32 ones: INT32_MIN / MAX, the prune threshold, deltas across 2^31 and 2^32 under RM+.
+EDGE_CASES = {
+    "f16-overflow": dict(dtype="f16", iters=2),
+    "f16-rmplus-overflow": dict(dtype="f16", rmplus=True, iters=2),
+    "f32-overflow": dict(dtype="f32", iters=2),
+    "f32-rmplus-overflow": dict(dtype="f32", rmplus=True, iters=2),
+    "i32-edges-rmplus": dict(dtype="i32", rmplus=True, iters=3),
+    "i32-edges-rmplus-prune": dict(dtype="i32", rmplus=True, prune=True, iters=3),
+}
+
+
+def run_edges(forms, dtype, iters, rmplus=False, prune=False, n=1021, seed=91):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n_actions, tree = rs.build_game_tree(rs.default_flop())
+    table = rs.create_infosets(n_actions, tree, [n], [1], {"i32": rs.I32, "f32": rs.F32, "f16": rs.F16}[dtype], 0)
+    half = dtype == "f16"
+    for nd in tree.action_nodes():
+        R, S = edge_i32(rng, nd.n_children, n) if dtype == "i32" else edge_float(half, big_rows=True)(rng, nd.n_children, n)
+        table.upload_node(nd.index, R, S)
+    lv = [{}, {}]
+    for i, nd in enumerate(tree.nodes):
+        if nd.kind == rs.NODE_TERMINAL and nd.ttype != rs.TERM_UNCONTESTED:
+            for p in (0, 1):   # LEAF_UTIL rows of each traverser's own
+                u = edge_utils(rng, n) if dtype == "i32" else float_utils(half)(rng, 0, n)[1]
+                lv[p][i] = (rs.LEAF_UTIL, table.lane_buffer(tree.nodes[nd.parent].index, 1, u))
+    mode = rs.UPD_CLAMP_I64 | (rs.UPD_RMPLUS if rmplus else 0) | (rs.UPD_PRUNE if prune else 0)
+    tr = rs.MCCFRTrainer(tree, table, lv[0], leaves_p1=lv[1], scale=100.0 if dtype == "i32" else 1.0, mode=mode, chance_mode=rs.CHANCE_PASS, fuse_subtrees=1, forms=forms)
+    assert tr.paired == (forms is ON)
+    assert tr.n_launches(0) + tr.n_launches(1) == (1 if forms is ON else 2)
+    idx, u0, u1 = root_buffers(tree, table)
+    out = []
+    for it in range(iters):
+        L.check(L.load().rs_iterate(tr._h, 0, u0.ptr))
+        L.check(L.load().rs_iterate(tr._h, 1, u1.ptr))
+        out.append(("root util p0 it=%d" % it, table.read_lane_buffer(u0, idx)[0]))
+        out.append(("root util p1 it=%d" % it, table.read_lane_buffer(u1, idx)[0]))
+    for nd in tree.action_nodes():
+        r, s_ = table.download_node(nd.index)
+        out += [("regrets of node %d" % nd.index, r), ("strategy sums of node %d" % nd.index, s_)]
+    tr.destroy()
+    table.destroy()
+    return out
+
+
+@pytest.mark.parametrize("case", sorted(EDGE_CASES))
+def test_pair_on_equals_pair_off_at_edges(case):
+    a, b = run_edges(ON, **EDGE_CASES[case]), run_edges(OFF, **EDGE_CASES[case])
+    if not case.startswith("i32"):   # the case is about what follows an overflow: it must have happened
+        assert any(np.isinf(x).any() for what, x in b if what.startswith("regrets"))
+    for (what, x), (_, y) in zip(a, b):
+        assert_same(x, y, what)   # bit for bit, every NaN one value
 
 
 def run_interleaved(forms, what):

@@ -4,11 +4,18 @@ that straddle 2^31 and 2^32 in waves that are all small, all large or mixed (the
 utilities, zero-probability opponent actions, all-non-positive rows; binary16 rows that overflow to inf, subnormal halves, -0.0 and NaN
 reaching the RM+ floor, f32 near FLT_MAX; lane counts that are no multiple of 4 or 64, fused and level plans, both lane-fan forms, graph
 replay, 64-lane table tiles, the deal-sweep forms, a round beyond 16 384 clusters, and DealTrainer batches replayed deal for deal.
-Bar: bit-equal, every NaN counted as one value."""
+Bar: bit-equal, every NaN counted as one value.
+
+Which kernel a lane case reaches.  run_lanes reads the root utilities and every node after each single sweep.  On a paired solver (river tree, CHANCE_PASS, fuse=1:
+rs_kernel_forms.pair_sweeps, the default) rs_iterate(s, 0) only HOLDS the sweep, and the read that follows settles it as a plain traverser-0 sweep; traverser 1 then finds
+nothing held and runs plain as well.  So run_lanes pins the plain kernels and the settle path (worth pinning; it returns tr.paired, and test_i32_edges_river asserts that its
+fuse=1 solvers ARE paired ones driven this way), and never a pair launch.  The pair kernel is pinned by run_pair_lanes and the test_pair_* cases below: rs_iterate(h, 0, u0),
+rs_iterate(h, 1, u1) with nothing in between, tr.paired and the launch count asserted, and only then the reads."""
 import numpy as np
 import pytest
 
 import rustsolver_amd as rs
+from rustsolver_amd import _lib as L
 from oracle import np_restate as npr
 from oracle import np_walk as npw
 from rustsolver_amd import abstraction as ab
@@ -108,6 +115,7 @@ def run_lanes(options, boards, C, init, make_leaves, mode="clamp", prune=False, 
     m = (rs.UPD_WRAP_I32 if mode == "wrap" else rs.UPD_CLAMP_I64) | (rs.UPD_PRUNE if prune else 0) | (rs.UPD_RMPLUS if rmplus else 0)
     tr = rs.MCCFRTrainer(tree, table, l0[0], leaves_p1=l1[0], scale=scale, mode=m, chance_mode=rs.CHANCE_ENUM if chance == "enum" else rs.CHANCE_PASS,
                          use_graph=graph, fuse_subtrees=fuse, opp_mode=rs.OPP_SAMPLE if opp == "sample" else rs.OPP_FULL, sample_seed=seed, forms=forms)
+    paired = tr.paired   # a paired solver's sweeps below are held, then settled as plain sweeps by the read: see the module docstring
     k = 0
     for it in range(iters):
         for player in players:
@@ -118,6 +126,7 @@ def run_lanes(options, boards, C, init, make_leaves, mode="clamp", prune=False, 
             k += 1
             same_tables(table, tab, "it=%d p=%d" % (it, player), before)
             assert_same(got, want, "root util it=%d p=%d" % (it, player))
+    return paired
 
 
 # ---- i32 tables through whole walks --------------------------------------------------------------------------------------------
@@ -128,8 +137,9 @@ def test_i32_edges_river(mode, fuse, graph, layout, monkeypatch):
     """the river tree over 4 099 lanes (no multiple of 4 or 64) with edge regrets and LEAF_UTIL leaves whose deltas straddle 2^31 and 2^32"""
     if layout == "tiled64":
         monkeypatch.setenv("RS_TABLE_TILE_LANES", "64")
-    run_lanes(rs.default_flop(), [1], 4099, edge_i32, lambda rng, r, n: ("util", edge_utils(rng, n)), mode=mode.split("+")[0], prune="prune" in mode,
-              rmplus="rmplus" in mode, scale=10000.0 if mode == "wrap" else 100.0, fuse=fuse, graph=graph, seed=11 + fuse)
+    paired = run_lanes(rs.default_flop(), [1], 4099, edge_i32, lambda rng, r, n: ("util", edge_utils(rng, n)), mode=mode.split("+")[0], prune="prune" in mode,
+                       rmplus="rmplus" in mode, scale=10000.0 if mode == "wrap" else 100.0, fuse=fuse, graph=graph, seed=11 + fuse)
+    assert paired == (fuse == 1)   # fuse=1: a paired solver whose held sweeps the per-sweep reads settled as plain ones (the pair launch itself: test_pair_i32_edges_river)
 
 
 @pytest.mark.parametrize("fuse", [1, 0])
@@ -171,11 +181,12 @@ def edge_float(half, big_rows=True):
     return init
 
 
-def float_utils(half):
+def float_utils(half, big=True):
     def make(rng, r, n):
         blk = (np.arange(n) // 16) % 4
         u = rng.uniform(-500, 500, size=n).astype(F32)
-        u[blk == 0] = (rng.uniform(-1, 1, size=int((blk == 0).sum())) * (6e4 if half else 3e38)).astype(F32)
+        if big:   # utilities that overflow a row near the largest finite value
+            u[blk == 0] = (rng.uniform(-1, 1, size=int((blk == 0).sum())) * (6e4 if half else 3e38)).astype(F32)
         u[blk == 1] = (rng.uniform(-1, 1, size=int((blk == 1).sum())) * 3e-5).astype(F32)
         u[np.nonzero(blk == 1)[0][::5]] = F32(-0.0)
         u[(blk == 2) & (np.arange(n) % 3 == 0)] = np.nan
@@ -209,6 +220,190 @@ def test_float_edges_three_streets_enum(dtype):
 def test_float_nan_reach_still_updates():
     """two sweeps on binary16 rows near 65504: the first overflows regrets to +inf, the second reads sigma = inf / inf = NaN there"""
     run_lanes(rs.default_flop(), [1], 1021, edge_float(True), float_utils(True), dtype="f16", scale=1.0, seed=41, iters=1)
+
+
+# ---- pair launches: both traversers of a chance-free lane tree in one kernel (rs_kernel_forms.pair_sweeps) ----------------------------------
+
+SENTINEL = F32(-12345.678)   # what a root-utility buffer holds before an iteration: a null side's buffer must still hold it afterwards
+
+
+def _of(x, player):
+    return x[player] if isinstance(x, tuple) else x
+
+
+def assert_no_nan_strategy(tab, what):
+    """The input condition of the float pair cases: the reference forms no NaN strategy (inf / inf, its only source) that a later walk would read.  Where it does, the
+    device's NaN-reach convention (test_float_nan_reach_still_updates) decides the outcome, not the pair kernel: such an input is to be changed, not skipped."""
+    for idx, (R, _) in tab.items():
+        with np.errstate(all="ignore"):
+            bad = np.isnan(npr.get_strategy_f32(R)).any(axis=0)
+        assert not bad.any(), "%s: node %d has a NaN strategy on %d lanes (first %d): change the test input" % (what, idx, int(bad.sum()), int(np.nonzero(bad)[0][0]))
+
+
+def run_pair_lanes(options, boards, C, init, make_leaves, mode="clamp", prune=False, rmplus=False, dtype="i32", opp="full", seed=1, iters=3, scale=100.0,
+                   graph=False, forms=None, nulls=None, settle=(), device=True):
+    """run_lanes for a real pair launch.  Per iteration rs_iterate(h, 0, u0) and rs_iterate(h, 1, u1) with nothing in between, then the reads; the reference is
+    iterate_lanes(player=0), iterate_lanes(player=1) with seeds sweep_seed(seed, 2 it), sweep_seed(seed, 2 it + 1).
+    init, make_leaves: as for run_lanes, or a pair of them (player 0's nodes, player 1's / traverser 0's leaves, traverser 1's).  nulls: it -> (u0 is null, u1 is null).
+    settle: the iterations in which a get_infosets between the two calls settles the held sweep (both sweeps of it then run plain; the seeds go on).
+    device=False: the numpy side alone (the input condition of the float cases can be checked where there is no GPU)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n_act, tree = rs.build_game_tree(options)
+    nodes = npw.tree_from_records(tree.nodes)
+    sampled = opp == "sample"
+    tab = {}
+    for nd in tree.action_nodes():
+        R, S = _of(init, nd.player)(rng, nd.n_children, boards[nd.round_idx] * C)
+        tab[nd.index] = (R.copy(), S.copy())
+    ln = [{}, {}]
+    for p in (0, 1):
+        for i, d in enumerate(nodes):
+            if d["kind"] == npw.TERMINAL and d["ttype"] != "UNCONTESTED":
+                r = nodes[d["parent"]]["round_idx"]
+                ln[p][i] = _of(make_leaves, p)(rng, r, boards[r] * C)
+    if dtype != "i32":
+        assert_no_nan_strategy(tab, "initial table")
+    if device:
+        table = rs.create_infosets(n_act, tree, [C], boards, DTYPES[dtype])
+        for idx, (R, S) in tab.items():
+            assert R.shape[1] == table.lanes(idx)
+            table.upload_node(idx, R, S)
+        lg = [{}, {}]
+        for p in (0, 1):
+            for i, (kind, buf) in ln[p].items():
+                lg[p][i] = (rs.LEAF_UTIL if kind == "util" else rs.LEAF_SIGN, table.lane_buffer(nodes[nodes[i]["parent"]]["index"], 1, buf))
+        m = (rs.UPD_WRAP_I32 if mode == "wrap" else rs.UPD_CLAMP_I64) | (rs.UPD_PRUNE if prune else 0) | (rs.UPD_RMPLUS if rmplus else 0)
+        tr = rs.MCCFRTrainer(tree, table, lg[0], leaves_p1=lg[1], scale=scale, mode=m, chance_mode=rs.CHANCE_PASS, use_graph=graph, fuse_subtrees=1,
+                             opp_mode=rs.OPP_SAMPLE if sampled else rs.OPP_FULL, sample_seed=seed, forms=forms)
+        # a solver that fell back to plain sweeps must fail here, not pass below
+        assert tr.paired, "the solver is not paired: these cases would compare plain sweeps"
+        assert tr.n_launches(0) + tr.n_launches(1) == (2 if sampled else 1)
+        root = tree.nodes[tree.nodes[0].children[0]].index
+        u = [table.lane_buffer(root, 1), table.lane_buffer(root, 1)]   # allocated once: the same pointers every iteration (one captured graph per pair of pointers)
+        sent = np.full(table.pitch(root), SENTINEL, dtype=F32)
+        probe = next(nd.index for nd in tree.action_nodes() if nd.player == 0)
+        lib = L.load()
+    for it in range(iters):
+        null = nulls(it) if nulls else (False, False)
+        before = {i: (R.copy(), S.copy()) for i, (R, S) in tab.items()}
+        if device:
+            for b in u:
+                b.upload(sent)
+            L.check(lib.rs_iterate(tr._h, 0, None if null[0] else u[0].ptr))
+            if it in settle:
+                table.get_infosets(probe, np.arange(0, min(64, table.lanes(probe)), dtype=np.uint32))
+            L.check(lib.rs_iterate(tr._h, 1, None if null[1] else u[1].ptr))
+            got = [table.read_lane_buffer(b, root)[0] for b in u]
+        want = []
+        for player in (0, 1):
+            want.append(npw.iterate_lanes(nodes, tab, ln[player], boards, C, player, scale=scale, mode=mode, prune=prune, rmplus=rmplus, dtype=dtype, chance="pass",
+                                          opp=opp, seed=npr.sweep_seed(seed, 2 * it + player)))
+            if dtype != "i32" and 2 * it + player < 2 * iters - 1:
+                assert_no_nan_strategy(tab, "after sweep it=%d p=%d" % (it, player))
+        if device:
+            same_tables(table, tab, "pair it=%d" % it, before)
+            for player in (0, 1):
+                if null[player]:
+                    assert_same(got[player], np.full(len(want[player]), SENTINEL, dtype=F32), "null root util buffer it=%d p=%d" % (it, player))
+                else:
+                    assert_same(got[player], want[player], "root util it=%d p=%d" % (it, player))
+    if device:
+        tr.destroy()
+        table.destroy()
+    return tab
+
+
+def I32_UTILS(rng, r, n):   # drawn per traverser: the two walks' leaves differ
+    return "util", edge_utils(rng, n)
+
+
+@pytest.mark.parametrize("mode", ["clamp", "wrap", "clamp+prune", "clamp+rmplus", "clamp+rmplus+prune"])
+@pytest.mark.parametrize("graph,layout", [(False, "plain"), (True, "plain"), (False, "tiled64"), (True, "tiled64")])
+def test_pair_i32_edges_river(mode, graph, layout, monkeypatch):
+    """test_i32_edges_river through pair launches: 4 099 lanes, edge regrets, LEAF_UTIL leaves of each traverser's own, 3 iterations"""
+    if layout == "tiled64":
+        monkeypatch.setenv("RS_TABLE_TILE_LANES", "64")
+    run_pair_lanes(rs.default_flop(), [1], 4099, edge_i32, I32_UTILS, mode=mode.split("+")[0], prune="prune" in mode, rmplus="rmplus" in mode,
+                   scale=10000.0 if mode == "wrap" else 100.0, graph=graph, seed=71)
+
+
+def carry_f16(rng, A, n):
+    """binary16 rows whose updates ROUND, in blocks of 16 lanes: (0) two positives 128 .. 2 176 below 65 504 (spacing 32; deltas below 16 a sweep: never 65 520, which would round to
+    inf) and a large negative; (1) subnormal halves k * 2^-24; (2) rows x, x (sigma 1/2, 1/2: every product exact) with x an integer in [1 024, 2 048) (spacing 1) and even negatives
+    in (-4 096, -2 048] (spacing 2), so that multiple-of-1/4 deltas land on round-to-nearest-even ties; (3) ordinary values with -0.0 and NaN cells"""
+    blk = (np.arange(n) // 16) % 4
+    R = npr.round_f16(rng.uniform(-1000, 1000, size=(A, n)))
+    S = npr.round_f16(rng.uniform(0, 1000, size=(A, n)))
+    R[:, blk == 0] = 65504.0 - 32.0 * rng.integers(4, 69, size=(A, int((blk == 0).sum())))
+    R[A - 1, blk == 0] *= rng.choice([-1.0, 1.0], size=int((blk == 0).sum()))
+    R[:, blk == 1] = rng.integers(-1023, 1024, size=(A, int((blk == 1).sum()))) * 2.0**-24
+    x = rng.integers(1024, 2048, size=int((blk == 2).sum()))
+    R[:, blk == 2] = -2.0 * rng.integers(1025, 2048, size=(A, int((blk == 2).sum())))
+    R[0, blk == 2] = R[1, blk == 2] = x
+    lanes3 = np.nonzero(blk == 3)[0]
+    R[:, lanes3[::3]] = -0.0
+    R[0, lanes3[1::5]] = np.nan
+    assert (npr.round_f16(R)[~np.isnan(R)] == R[~np.isnan(R)]).all()
+    return R.astype(F32), S.astype(F32)
+
+
+def carry_f16_utils(rng, r, n):
+    """utilities a few ulps of the row they meet: below 8 under 65 504, a few 2^-24 in the subnormal block, multiples of 1/2 in the tie block"""
+    blk = (np.arange(n) // 16) % 4
+    u = rng.uniform(-300, 300, size=n)
+    u[blk == 0] = rng.uniform(-8, 8, size=int((blk == 0).sum()))
+    u[blk == 1] = rng.integers(-6, 7, size=int((blk == 1).sum())) * 2.0**-24
+    u[blk == 2] = rng.integers(-80, 81, size=int((blk == 2).sum())) * 0.5
+    u = u.astype(F32)
+    u[np.nonzero(blk == 3)[0][::7]] = F32(-0.0)
+    return "util", u
+
+
+def test_pair_f16_carry_rounding():
+    """Row<F16>::carry: traverser 0's updated regrets stay in f32 registers and must come to the second walk as binary16 would give them back.  Every update of three blocks
+    in four rounds (ties, subnormals, spacing 32 below 65 504); 3 iterations, so that traverser 1's sigma of iteration 1 and everything after depend on it.  No value overflows."""
+    tab = run_pair_lanes(rs.default_flop(), [1], 1021, carry_f16, carry_f16_utils, dtype="f16", scale=1.0, seed=73, iters=3)
+    assert all(np.isfinite(R[~np.isnan(R)]).all() for R, _ in tab.values())
+
+
+# The NaN-reach rule (test_float_nan_reach_still_updates): a pair cannot take one sweep per fresh table, so the inputs keep what overflows where no later walk reads it -- rows
+# near the largest finite value on player 1's nodes, overflowing utilities on traverser 1's leaves, one iteration (traverser 1's is the last sweep) -- and NaN cells, NaN
+# utilities, -0.0 and subnormal halves everywhere.  run_pair_lanes asserts the condition on the reference (assert_no_nan_strategy).  The inputs that do overflow on player 0's
+# nodes are compared pair ON against pair OFF instead (tests/test_gpu_pair_sweeps.py).
+@pytest.mark.parametrize("dtype", ["f16", "f16+rmplus", "f32", "f32+rmplus"])
+def test_pair_float_edges_lanes(dtype):
+    half = dtype.startswith("f16")
+    run_pair_lanes(rs.default_flop(), [1], 1021, (edge_float(half, big_rows=False), edge_float(half)), (float_utils(half, big=False), float_utils(half)),
+                   rmplus="rmplus" in dtype, dtype=dtype.split("+")[0], scale=1.0, seed=75, iters=1)
+
+
+@pytest.mark.parametrize("lanes_per_thread", ["1", "2", "4"])
+@pytest.mark.parametrize("C", [4099, 37])
+@pytest.mark.parametrize("case", ["i32-clamp+prune", "f16-carry"])
+def test_pair_lanes_per_thread(case, C, lanes_per_thread, monkeypatch):
+    """the pair kernel's three forms (RS_JIT_LANES; its own default is 2) over 64-lane table tiles: a tile shift and a vector count rescaled from the four-lane kernels' arguments, at
+    lane counts that are no multiple of 4 or 64 and below one tile"""
+    monkeypatch.setenv("RS_JIT_LANES", lanes_per_thread)
+    monkeypatch.setenv("RS_TABLE_TILE_LANES", "64")
+    if case == "f16-carry":
+        run_pair_lanes(rs.default_flop(), [1], C, carry_f16, carry_f16_utils, dtype="f16", scale=1.0, seed=77, iters=2)
+    else:
+        run_pair_lanes(rs.default_flop(), [1], C, edge_i32, I32_UTILS, prune=True, seed=79, iters=2)
+
+
+@pytest.mark.parametrize("settle", [(), (1,)], ids=["pairs", "settled-between"])
+def test_pair_i32_edges_river_sampled(settle):
+    """OPP_SAMPLE with prune, 3 boards x 1 367 clusters: the two seeds of an iteration come from one k_next_seed_pair launch and must be sweep_seed(seed, 2 it) and (seed, 2 it + 1) --
+    also when iteration 1's held sweep was settled as a plain one (two k_next_seed launches) between two pair launches"""
+    run_pair_lanes(rs.default_flop(), [3], 1367, edge_i32, I32_UTILS, prune=True, opp="sample", seed=81, iters=4 if settle else 3, settle=settle)
+
+
+@pytest.mark.parametrize("graph", [True, False])
+def test_pair_null_root_utilities(graph):
+    """either root-utility pointer may be null: tables and the other side's output are what they are otherwise, the null side's buffer is not written, and under graph replay
+    every pair of pointers gets its own graph (7 iterations: both, u0 null, u1 null, both null, then the first three pairs again)"""
+    pattern = [(False, False), (True, False), (False, True), (True, True), (False, False), (True, False), (False, True)]
+    run_pair_lanes(rs.default_flop(), [1], 4099, edge_i32, I32_UTILS, rmplus=True, graph=graph, seed=83, iters=len(pattern), nulls=lambda it: pattern[it])
 
 
 # ---- deal sweeps -------------------------------------------------------------------------------------------------------------
