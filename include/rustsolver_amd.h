@@ -44,7 +44,9 @@ extern "C" {
                               5: rs_kernel_forms without `worklist` and RS_FAN_LOOP / RS_SHADOW_WIDE, with direct_rows and kept_records (same size: a zeroed struct means what it meant);
                                  rs_hand_index_verify, rs_deal_trainer_br_bytes / _br_release / _br_launches, RS_ERR_MISMATCH;
                               6: rs_deal_trainer_params.table_dtype (was `reserved`: zero = RS_I32 means what it meant), float deal tables RS_F16 and RS_UPD_RMPLUS,
-                                 rs_solver_exchange_bytes (diagnostics), data-parallel sweeps keep direct rows */
+                                 rs_solver_exchange_bytes (diagnostics), data-parallel sweeps keep direct rows;
+                                 still 6: Discounted CFR (rs_dcfr_params, rs_dcfr_params_default, rs_dcfr_factors, rs_discount_dcfr, rs_train_dcfr, rs_solver_dcfr_fused,
+                                 rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -247,6 +249,27 @@ int rs_discount(rs_table *table, float d);
 /* cfr.rs:248-249: p = (tc / interval) as f32; d = p / (p + 1.0) */
 float rs_discount_factor(uint64_t tc, uint64_t interval);
 
+/* Discounted CFR (Brown & Sandholm, AAAI 2019; an extension, the reference knows the one factor above): a tick multiplies regrets > 0 by d_pos, all other regrets by
+ * d_neg and strategy sums by d_sum.  rs_dcfr_factors, tick number p > 0, in double and each rounded once to f32:
+ *   out[0] = pos = p^alpha / (p^alpha + 1),  out[1] = neg = p^beta / (p^beta + 1),  out[2] = sum = (p / (p + 1))^gamma.
+ * alpha / beta = +INFINITY give exactly 1, -INFINITY exactly 0, for every p (a power that overflows double counts as +INFINITY); NaN exponents, a gamma that is not
+ * finite and p = 0 are refused.  (1.5, 0, 2) is the paper's DCFR, (1, 1, 1) Linear CFR, beta = -INFINITY on RS_UPD_RMPLUS tables behaves like CFR+.
+ * rs_discount_dcfr, per cell: i32 tables x = ((x as f32) * d) as i32 as rs_discount, f32 tables one multiply, binary16 tables the multiply in f32 and one rounding to
+ * nearest even on the store; three equal factors ARE rs_discount(d), bit for bit.  With unequal factors a deal solver's kept shadow records (rs_kernel_forms.kept_records)
+ * are not swept: the table's rows are brought up to date first (which ends a training loop's working-copy state, see rs_solver_training_loop), and the records are rebuilt
+ * before the next sweep -- one transpose of the kept nodes per tick (profiles/dcfr.md). */
+typedef struct rs_dcfr_params {
+    double alpha, beta, gamma;   /* +-INFINITY allowed for alpha / beta */
+    uint64_t interval;           /* a tick after iteration t when t % interval == 0; p = t / interval; > 0 */
+    uint64_t cap;                /* no tick once t > cap */
+    uint64_t t0;                 /* iterations done before this call: a run split in two equals one run */
+    int32_t fused;               /* RS_FORM_*: apply a pending tick inside the next sweeps' row loads (rs_train_dcfr) */
+    int32_t reserved;
+} rs_dcfr_params;
+int rs_dcfr_params_default(rs_dcfr_params *out);   /* 1.5, 0, 2, interval 1, cap UINT64_MAX, t0 0, fused RS_FORM_DEFAULT */
+int rs_dcfr_factors(double alpha, double beta, double gamma, uint64_t p, float out[3]);   /* pos, neg, sum */
+int rs_discount_dcfr(rs_table *table, float d_pos, float d_neg, float d_sum);
+
 /* ---- iterate: MCCFRTrainer (cfr.rs) ------------------------------------------------------------
  * Lane model: lane (board b, cluster c) is one scalar cfr() traversal (cfr.rs:481-627)
  * in which get_cluster() (cfr.rs:564-568) returns c for either player and evaluate() is replaced by
@@ -372,6 +395,20 @@ int rs_iterate(rs_solver *solver, int traverser, float *d_root_util);
 /* MCCFRTrainer::train (cfr.rs:188-265), deterministic: per iteration both traversers sweep, t += 1, then
  * the discount check `t > threshold` (d = p/(p+1), p = t/interval) until t > discount_cap. */
 int rs_train(rs_solver *solver, uint64_t iterations, uint64_t discount_interval, uint64_t discount_cap);
+/* Discounted CFR over full sweeps.  Per iteration both traversers sweep, t += 1 (starting from params->t0), and if t <= cap and t % interval == 0 a tick with
+ * rs_dcfr_factors(alpha, beta, gamma, t / interval).
+ * FUSED form: the tick is not swept but left pending, and the next iteration's sweeps apply it to the rows they load anyway -- traverser 0's sweep discounts player 0's
+ * regrets (by sign) and strategy sums before it updates and stores them and player 1's regrets for regret matching only; traverser 1's sweep discounts player 1's rows and
+ * reads player 0's as just written.  No pass over the table of its own: on the 14-node river tree 776 bytes per lane and iteration instead of 776 + 608 (or, paired,
+ * 612 + 608).  Bit-identical to "rs_discount_dcfr after iteration t, then both sweeps of iteration t + 1"; a tick still pending when the call returns -- the one after the
+ * last iteration included -- is swept before it does.  Who fuses: lane solvers with fuse_subtrees = 1 on one rank whose traverser plans are one chance-free subtree kernel
+ * each (what makes a solver pairable), with RS_OPP_FULL and without RS_UPD_PRUNE -- only then does every sweep load every row the tick must reach.  Sampled opponents and
+ * pruning leave nodes unvisited, ENUM chance nodes and the level plan spread a sweep over several kernels, deal batches share cells between lanes: all of those take
+ * rs_discount_dcfr between the iterations, as does params->fused = RS_FORM_OFF.  The discounted kernels are generated and compiled on the first fused call (cached like the
+ * others); a paired solver issues its two unpaired launches while the fused loop runs (there is no discounted pair kernel) and pairs again afterwards.
+ * rs_solver_dcfr_fused: 1 if the last rs_train_dcfr on the solver applied its ticks inside the sweeps, 0 if it swept them. */
+int rs_train_dcfr(rs_solver *solver, uint64_t iterations, const rs_dcfr_params *params);
+int rs_solver_dcfr_fused(const rs_solver *solver);
 /* For a host that writes MCCFRTrainer::train's loop itself (rs_iterate / rs_iterate_phase per batch, rs_discount at its ticks): on = 1 in front of the loop, on = 0 behind
  * it.  In between the solver's kept shadow records (rs_kernel_forms.kept_records) are the working copy, as they are inside rs_train and rs_deal_trainer_train: the table's rows
  * of those nodes are neither added to nor discounted until on = 0 writes them back.  Any call that reads or writes table contents in between (download, upload, strategy
@@ -533,6 +570,10 @@ uint64_t rs_deal_trainer_iterations(const rs_deal_trainer *trainer);   /* t of c
  * before the first tick).  rs_deal_trainer_calc_br / _best_response run the two readers on the trainer's own tree, ranges and
  * abstraction at any time (best response: single-round trainers on a full board). */
 int rs_deal_trainer_set_tick_br(rs_deal_trainer *trainer, int enable);
+/* Discounted CFR at the trainer's ticks: WHEN a tick comes stays the reference's rule (t > threshold, discount_interval, discount_cap: cfr.rs:240-262); the sweep then
+ * takes rs_dcfr_factors(alpha, beta, gamma, t / discount_interval) through rs_discount_dcfr instead of the one factor of cfr.rs:248-249 (only the exponents of `params`
+ * are read).  i32, f32 and binary16 tables, with or without a communicator: the factors depend on t alone, every rank computes the same.  NULL: back to cfr.rs:248-261. */
+int rs_deal_trainer_set_dcfr(rs_deal_trainer *trainer, const rs_dcfr_params *params);
 int rs_deal_trainer_last_br(const rs_deal_trainer *trainer, float *out /*[2]*/, uint64_t *iterations);
 int rs_deal_trainer_calc_br(rs_deal_trainer *trainer, float *out /*[2]*/);
 int rs_deal_trainer_best_response(rs_deal_trainer *trainer, int mode, double *out /*[2]*/);

@@ -58,6 +58,10 @@ int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_
 /* the pair kernel (rs_kernel_forms.pair_sweeps: both traversers of a lane sweep in one walk per lane) of every topmost chance-free subtree, generated and compiled the same way */
 int rs_jit_check_pair(const rs_tree *tree, int dtype, int mode, int opp_mode, int *n_kernels);
 
+/* the discounted variants (rs_train_dcfr, fused form) of both traversers' lane kernels of every topmost chance-free subtree, generated and compiled the same way; fails if
+ * requesting a variant changes the source of the plain kernel generated from the same inputs */
+int rs_jit_check_dcfr(const rs_tree *tree, int dtype, int mode, int *n_kernels);
+
 /* ---- self-test of the short exact division regret matching uses on i32 tables (rs_device.hpp div_exact_pos) against the compiler's f32 division, on the device:
  * n hashed (regret, sum) pairs; *mismatches must be 0.  first_bad (may be NULL): [2] = the first differing pair. */
 int rs_selftest_division(rs_table *table, size_t n, uint64_t seed, uint64_t *mismatches, float *first_bad);

@@ -80,6 +80,11 @@ class DealTrainerParams(C.Structure):
                 ("prune_threshold", C.c_uint64), ("prefetch", C.c_int32), ("table_dtype", C.c_int32)]
 
 
+class DcfrParams(C.Structure):   # rs_dcfr_params
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("interval", C.c_uint64), ("cap", C.c_uint64), ("t0", C.c_uint64),
+                ("fused", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint64 * K_COUNT), ("ms", C.c_double * K_COUNT), ("algo_bytes", C.c_double * K_COUNT)]
 
@@ -158,6 +163,13 @@ SYMBOLS = {
     "rs_solver_destroy": (None, [_P]),
     "rs_iterate": (C.c_int, [_P, C.c_int, _P]),
     "rs_train": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "rs_dcfr_params_default": (C.c_int, [C.POINTER(DcfrParams)]),
+    "rs_dcfr_factors": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_float)]),
+    "rs_discount_dcfr": (C.c_int, [_P, C.c_float, C.c_float, C.c_float]),
+    "rs_train_dcfr": (C.c_int, [_P, C.c_uint64, C.POINTER(DcfrParams)]),
+    "rs_solver_dcfr_fused": (C.c_int, [_P]),
+    "rs_deal_trainer_set_dcfr": (C.c_int, [_P, C.POINTER(DcfrParams)]),
+    "rs_jit_check_dcfr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rs_solver_attach_comm": (C.c_int, [_P, _P]),
     "rs_iterate_phase": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "rs_solver_exchange_info": (C.c_int, [_P, C.c_int, _PP, C.POINTER(C.c_size_t)]),

@@ -237,6 +237,18 @@ struct DiscountJob {
     size_t n_vec;
 };
 hipError_t launch_discount_jobs(const DiscountJob *d_jobs, int n_jobs, size_t max_vec, float d, int dtype, hipStream_t stream);
+// Discounted CFR (rs_discount_dcfr): the sweep with one factor for regrets > 0, one for the others and one for the strategy sums
+hipError_t launch_discount3(void *regrets, void *ssum, size_t n_cells, float d_pos, float d_neg, float d_sum, int dtype, hipStream_t stream);
+// ... and its fused form (rs_train_dcfr): the tail of a discounted lane kernel's job descriptor, one entry per PLAYER whose rows the kernel loads (rs_jit.cpp, JArgs.dc[2]).
+// pending = 0: the rows are used as loaded, nothing is multiplied.
+struct DcfrSide {
+    uint32_t pending;
+    float pos, neg, sum;
+};
+struct DcfrArm {
+    DcfrSide side[4];   // traverser 0's descriptor (player 0, player 1), then traverser 1's
+};
+hipError_t launch_dcfr_arm(DcfrSide *d_p0, DcfrSide *d_p1, const DcfrArm &v, hipStream_t stream);
 hipError_t launch_unbuild_shadow(const ShadowJob *d_jobs, int n_jobs, uint32_t max_clusters, hipStream_t stream);
 hipError_t launch_row_apply(const RowSumJob *d_jobs, int n_jobs, uint32_t max_entries, hipStream_t stream);
 // data-parallel deal batches: the rows of the direct rounds as 12-byte (job, row, cluster, delta) items for the ranks to exchange, and every rank's items applied
@@ -362,6 +374,7 @@ struct JitSubtree {
     size_t off_fan = 0, off_inv = 0, off_cvec = 0;                                        // lane sweeps: deals below the ENUM chance node the kernel walks itself
     std::vector<int> boundary_roots;   // tree id of every next-round root below this subtree, in the order of butil[] / breach[]
     bool pair = false;                 // a pair kernel (JitPair) whose two walks index nodes, leaves and constants alike: entry(jobs[2], flags, out0, out1)
+    size_t off_dcfr = 0;               // discounted variant (JitPair::dcfr): JArgs.dc[2], two DcfrSide behind everything the plain kernel's descriptor holds
 };
 // staged rows (rs_device.hpp stage_rows): the shadow rows of a round subtree as the generated kernel needs to know them -- structure only, no addresses
 struct JitStage {
@@ -377,6 +390,10 @@ struct JitPair {
     const std::vector<char> *has_own = nullptr;
     const std::vector<int> *leaf_buf = nullptr, *leaf_flags = nullptr;
     bool ok = false;
+    // Not a pair at all (has_own == nullptr), but the DISCOUNTED variant of traverser p's plain lane kernel (rs_train_dcfr, fused form): a pending Discounted-CFR tick is
+    // applied to every row where the walk uses it -- own nodes' regrets and strategy sums, opponent nodes' regrets -- under the per-player words of JArgs.dc[].  Full-width
+    // opponents without pruning only: every node of the subtree is visited by every lane.
+    bool dcfr = false;
 };
 constexpr int kStageMaxChunks = 16;   // rows beyond 256 bytes keep their gathers (64 deals x 17 chunks x 16 B = 17 KB of LDS per wave)
 void jit_emit_subtree(const std::vector<rs_tree_node> &nodes, int root, int p, const std::vector<char> &has_own,

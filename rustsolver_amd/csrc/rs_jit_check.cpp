@@ -254,4 +254,53 @@ int rs_jit_check_pair(const rs_tree *tree, int dtype, int mode, int opp_mode, in
     return RS_OK;
 }
 
+// the discounted variants of the plain lane kernels (rs_solver.cpp setup_dcfr): both traversers of every topmost chance-free subtree, full-width opponents, no pruning.
+// The plain kernel of the same inputs is generated before and after the variant: its text must not move.
+int rs_jit_check_dcfr(const rs_tree *tree, int dtype, int mode, int *n_kernels) {
+    if (!tree || tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_jit_check_dcfr: bad tree");
+    const std::vector<rs_tree_node> &nodes = tree->nodes;
+    const size_t n = nodes.size();
+    const Knobs knobs = knobs_resolve(nullptr);
+    std::vector<char> has_own[2] = {std::vector<char>(n, 0), std::vector<char>(n, 0)}, closed(n, 0);
+    std::vector<int> leaf_buf(n, -1), leaf_flags(n, 0);
+    for (size_t i = n; i-- > 0;) {   // children have larger ids than parents
+        const rs_tree_node &nd = nodes[i];
+        bool cl = nd.kind != RS_NODE_PUBLIC_CHANCE && nd.kind != RS_NODE_PRIVATE_CHANCE;
+        for (int p = 0; p < 2; ++p) {
+            bool own = nd.kind == RS_NODE_ACTION && nd.player == p;
+            for (int k = 0; k < nd.n_children; ++k) own = own || has_own[p][nd.children[k]];
+            has_own[p][i] = own;
+        }
+        for (int k = 0; k < nd.n_children; ++k) cl = cl && closed[nd.children[k]];
+        closed[i] = cl;
+        if (nd.kind == RS_NODE_TERMINAL && nd.ttype != RS_TERM_UNCONTESTED) {
+            leaf_buf[i] = nd.round;
+            leaf_flags[i] = 1;
+        }
+    }
+    std::map<std::string, int> seen;
+    JitPair jp;
+    jp.dcfr = true;
+    for (size_t i = 0; i < n; ++i) {
+        const rs_tree_node &nd = nodes[i];
+        if (nd.kind != RS_NODE_ACTION || !closed[i] || nd.n_children == 0) continue;
+        if (nd.parent >= 0 && nodes[nd.parent].kind == RS_NODE_ACTION && closed[nd.parent]) continue;   // not topmost
+        for (int p = 0; p < 2; ++p) {
+            JitSubtree plain, js, again;
+            jit_emit_subtree(nodes, int(i), p, has_own[p], leaf_buf, leaf_flags, dtype, mode & RS_UPD_ARITH_MASK, false, false, false, false, false, false, 4, nullptr, plain, knobs);
+            jit_emit_subtree(nodes, int(i), p, has_own[p], leaf_buf, leaf_flags, dtype, mode & RS_UPD_ARITH_MASK, false, false, false, false, false, false, 4, nullptr, js, knobs, 0, false,
+                             false, false, false, false, false, nullptr, false, nullptr, &jp);
+            jit_emit_subtree(nodes, int(i), p, has_own[p], leaf_buf, leaf_flags, dtype, mode & RS_UPD_ARITH_MASK, false, false, false, false, false, false, 4, nullptr, again, knobs);
+            if (plain.source != again.source || plain.args_size != again.args_size)
+                return fail(RS_ERR_MISMATCH, "rs_jit_check_dcfr: the plain kernel's source changed once the discounted variant had been generated");
+            if (!js.off_dcfr || js.off_dcfr != plain.args_size || js.source == plain.source)
+                return fail(RS_ERR_INVALID, "rs_jit_check_dcfr: no discounted variant came out, or its descriptor does not extend the plain kernel's");
+            seen[js.source] = 1;
+        }
+    }
+    if (int rc = jit_compile_many(seen, knobs.dump != 0)) return rc;
+    if (n_kernels) *n_kernels = int(seen.size());
+    return RS_OK;
+}
+
 }  // extern "C"

@@ -433,6 +433,63 @@ __global__ __launch_bounds__(kBlock) void k_discount_jobs(const DiscountJob *__r
     discount_body<DT>(j.regrets, j.ssum, j.n_vec, d);
 }
 
+// ---- Discounted CFR sweep (Brown & Sandholm 2019; rs_discount_dcfr): the same walk over the two arrays with three factors -- a regret takes d_pos when it is > 0 and d_neg
+// otherwise (zero, -0.0 and NaN included), a strategy sum takes d_sum.  The factor is picked per element (a select, no branch); the arithmetic per cell is k_discount's, so
+// three equal factors give its bits.  Same access pattern: 16-byte nontemporal loads, U vectors per array in flight, one contiguous 16 KB per array and workgroup trip.
+template <int DT>
+__device__ __forceinline__ void discount3_body(void *__restrict__ regrets, void *__restrict__ ssum, size_t n_vec, float d_pos, float d_neg, float d_sum) {
+    using R = Row<DT>;
+    using V = typename R::val;
+    constexpr size_t esize = (DT == RS_F16) ? 2 : 4;
+    constexpr int U = 4;
+    const size_t chunk = (size_t)kBlock * U;
+    for (size_t v0 = (size_t)blockIdx.x * chunk + threadIdx.x; v0 < n_vec; v0 += (size_t)gridDim.x * chunk) {
+        constexpr size_t stride = kBlock;
+        V r[U][kVec], s[U][kVec];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const size_t v = v0 + (size_t)u * stride;
+            if (v < n_vec) {   // 64-bit offsets: a table can exceed 2^32 cells
+                R::load((char *)regrets + v * kVec * esize, 0, 0, r[u]);
+                R::load((char *)ssum + v * kVec * esize, 0, 0, s[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const size_t v = v0 + (size_t)u * stride;
+            if (v < n_vec) {
+#pragma unroll
+                for (int j = 0; j < kVec; j++) {
+                    const float d = r[u][j] > 0 ? d_pos : d_neg;
+                    if constexpr (DT == RS_I32) {
+                        r[u][j] = f32_as_i32((float)r[u][j] * d);
+                        s[u][j] = f32_as_i32((float)s[u][j] * d_sum);
+                    } else {
+                        r[u][j] = r[u][j] * d;
+                        s[u][j] = s[u][j] * d_sum;
+                    }
+                }
+                R::store((char *)regrets + v * kVec * esize, 0, 0, r[u]);
+                R::store((char *)ssum + v * kVec * esize, 0, 0, s[u]);
+            }
+        }
+    }
+}
+template <int DT>
+__global__ __launch_bounds__(kBlock) void k_discount3(void *__restrict__ regrets, void *__restrict__ ssum, size_t n_vec, float d_pos, float d_neg, float d_sum) {
+    discount3_body<DT>(regrets, ssum, n_vec, d_pos, d_neg, d_sum);
+}
+// the pending-tick words of the two fused DCFR sweeps' job descriptors (rs_solver.cpp run_dcfr_iteration), written on the table's stream in front of them: the descriptors
+// stay where a captured graph found them
+__global__ void k_dcfr_arm(DcfrSide *__restrict__ a, DcfrSide *__restrict__ b, DcfrArm v) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {   // one thread, plain vector stores
+        a[0] = v.side[0];
+        a[1] = v.side[1];
+        b[0] = v.side[2];
+        b[1] = v.side[3];
+    }
+}
+
 // ---- sparse deal sweeps: the deals whose reach into a subtree is not NaN, as an index list.  A workgroup counts the live lanes of its 256
 // with four ballots, ONE atomic reserves the slots (a first version issued one returning atomic per wave on 72 adjacent counters: they share three
 // cache lines, the L2 serialised 1.2 M of them, 8.3 ms per launch; counters now sit 256 B apart).  The order of workgroups in the list is
@@ -1470,6 +1527,19 @@ hipError_t launch_discount(void *regrets, void *ssum, size_t n_cells, float d, i
     if (dtype == RS_I32) hipLaunchKernelGGL((k_discount<RS_I32>), grid, block, 0, stream, regrets, ssum, n_vec, d);
     else if (dtype == RS_F32) hipLaunchKernelGGL((k_discount<RS_F32>), grid, block, 0, stream, regrets, ssum, n_vec, d);
     else hipLaunchKernelGGL((k_discount<RS_F16>), grid, block, 0, stream, regrets, ssum, n_vec, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_discount3(void *regrets, void *ssum, size_t n_cells, float d_pos, float d_neg, float d_sum, int dtype, hipStream_t stream) {
+    const size_t n_vec = n_cells / kVec;
+    dim3 grid(grid_for((n_vec + 3) / 4)), block(kBlock);
+    if (dtype == RS_I32) hipLaunchKernelGGL((k_discount3<RS_I32>), grid, block, 0, stream, regrets, ssum, n_vec, d_pos, d_neg, d_sum);
+    else if (dtype == RS_F32) hipLaunchKernelGGL((k_discount3<RS_F32>), grid, block, 0, stream, regrets, ssum, n_vec, d_pos, d_neg, d_sum);
+    else hipLaunchKernelGGL((k_discount3<RS_F16>), grid, block, 0, stream, regrets, ssum, n_vec, d_pos, d_neg, d_sum);
+    return hipGetLastError();
+}
+hipError_t launch_dcfr_arm(DcfrSide *d_p0, DcfrSide *d_p1, const DcfrArm &v, hipStream_t stream) {
+    hipLaunchKernelGGL(k_dcfr_arm, dim3(1), dim3(64), 0, stream, d_p0, d_p1, v);
     return hipGetLastError();
 }
 

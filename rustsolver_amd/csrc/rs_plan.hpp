@@ -280,6 +280,16 @@ struct rs_solver : rs::SolverDevice {
         rs::DevGraphExec graph_exec;
         float *graph_out[2] = {nullptr, nullptr};
     } pair;
+    // Discounted CFR, fused form (rs_train_dcfr): the discounted variants of the two traversers' lane kernels (rs_jit.cpp, JitPair::dcfr), generated and compiled on the
+    // first fused call.  Their descriptors are the plain kernels' plus two DcfrSide each; `armed`: some pending word on the device is set (k_dcfr_arm clears it again).
+    struct Dcfr {
+        bool tried = false, ok = false, armed = false;
+        int last_fused = 0;             // rs_solver_dcfr_fused
+        rs::JitLaunch jit[2];
+        size_t off_dc = 0;
+        rs::DevGraph graph[2];          // use_graph: one captured launch per traverser
+        rs::DevGraphExec graph_exec[2];
+    } dcfr;
     const uint64_t *d_seed() const { return d_seed_state ? d_seed_state + 2 : nullptr; }
 };
 

@@ -427,6 +427,12 @@ void rs::solver_release_device(rs_solver *s) {
     s->pair.graph.reset();
     s->pair.jit = JitLaunch{};
     s->pair.on = false;
+    for (int p = 0; p < 2; ++p) {
+        s->dcfr.graph_exec[p].reset();
+        s->dcfr.graph[p].reset();
+        s->dcfr.jit[p] = JitLaunch{};
+    }
+    s->dcfr.ok = false;
     static_cast<SolverDevice &>(*s) = SolverDevice{};
     s->d_arec = nullptr;
     for (void *&a : s->d_attr) a = nullptr;
@@ -1002,6 +1008,120 @@ static void setup_pair(rs_solver *s) {
     P.bytes = double(P.lanes) * per_lane;
 }
 
+// Discounted CFR, fused form (rs_train_dcfr).  Who may fuse: the solvers a pair kernel is possible for -- a lane solver on one rank whose traverser plans are ONE generated
+// kernel over the same chance-free subtree -- with full-width opponents and no pruning: only then does every sweep of traverser p load every row of player p (to update it)
+// and every regret row of the opponent (to match regrets), so that a tick left pending reaches every cell exactly once.  Sampled opponents and pruning leave nodes
+// unvisited, ENUM chance nodes and the level plan spread a sweep over several kernels: those solvers take the standalone sweep between iterations.
+static bool dcfr_eligible(const rs_solver *s) {
+    if (s->deal_mode || s->sharded || s->comm || !s->params.fuse_subtrees || s->before_sweep) return false;
+    if (s->params.opp_mode != RS_OPP_FULL || (s->params.mode & RS_UPD_PRUNE)) return false;
+    const Plan::PairSrc &ps0 = s->plan[0].pair_src;
+    for (int p = 0; p < 2; ++p) {
+        const Plan &pl = s->plan[p];
+        const Plan::PairSrc &ps = pl.pair_src;
+        if (ps.root < 0 || ps.root != ps0.root || ps.n_jobs != 1 || pl.jit.size() != 1) return false;
+        if (pl.launches.size() != 1 || pl.launches[0].kind != L_TREE || pl.launches[0].first_job != ps.jit) return false;
+        const JitLaunch &JL = pl.jit[size_t(ps.jit)];
+        if (JL.n_jobs != 1 || !JL.members.empty() || JL.lds_bytes || JL.worklist || JL.blob.size() != JL.stride) return false;
+    }
+    return true;
+}
+// the discounted variants of both traversers' kernels, on the first fused rs_train_dcfr: generated from what the plain kernels were generated from, compiled through the
+// same caches and helper processes, their descriptors the plain ones' with the two pending words behind them.  A variant that cannot be had is an error, not a fallback.
+static int setup_dcfr(rs_solver *s) {
+    rs_solver::Dcfr &D = s->dcfr;
+    if (D.ok) return RS_OK;
+    rs_table *t = s->table;
+    JitPair jp;
+    jp.dcfr = true;
+    for (int p = 0; p < 2; ++p) {
+        const Plan::PairSrc &ps = s->plan[p].pair_src;
+        const JitLaunch &JL = s->plan[p].jit[size_t(ps.jit)];
+        JitSubtree js;
+        jit_emit_subtree(s->tree.nodes, ps.root, p, ps.has_own, ps.leaf_buf, ps.leaf_flags, t->dtype, s->params.mode & RS_UPD_ARITH_MASK, false, false, false, false, false, false, 4,
+                         nullptr, js, s->knobs, 0, false, false, false, false, false, false, nullptr, false, nullptr, &jp);
+        if (!js.off_dcfr || js.off_dcfr != JL.stride || js.args_size != JL.stride + 2 * sizeof(DcfrSide) || js.threads != JL.threads || js.lanes != 4)
+            return fail(RS_ERR_INVALID, "rs_train_dcfr: the discounted kernel's descriptor does not extend the plain kernel's");
+        JitLaunch &V = D.jit[p];
+        V = JitLaunch{};
+        V.source = js.source;
+        V.entry = js.entry;
+        V.stride = js.args_size;
+        V.threads = js.threads;
+        V.n_jobs = 1;
+        V.max_n_vec = JL.max_n_vec;
+        V.bytes = JL.bytes;
+        V.blob = JL.blob;
+        V.blob.resize(js.args_size, 0);   // nothing pending
+        D.off_dc = js.off_dcfr;
+    }
+    std::vector<JitRequest> reqs;
+    for (int p = 0; p < 2; ++p) reqs.push_back(JitRequest{&D.jit[p].source, &D.jit[p].entry, nullptr});
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    if (int rc = jit_get_kernels(reqs, t->device, s->knobs.dump != 0)) return rc;
+    for (int p = 0; p < 2; ++p) {
+        JitLaunch &V = D.jit[p];
+        V.fn = reqs[size_t(p)].fn;
+        V.source = std::string();
+        if (!V.fn) return fail(RS_ERR_HIP, "rs_train_dcfr: the discounted kernel did not load");
+        RS_HIP(V.d_blob.alloc(V.blob.size(), &s->dev_bytes), "rs_train_dcfr: kernel arguments");
+        RS_HIP(hipMemcpyAsync(V.d_blob, V.blob.data(), V.blob.size(), hipMemcpyHostToDevice, t->stream), "rs_train_dcfr: kernel arguments");
+    }
+    RS_HIP(hipStreamSynchronize(t->stream), "rs_train_dcfr: kernel arguments");
+    D.armed = false;
+    D.ok = true;
+    return RS_OK;
+}
+// one discounted sweep of traverser p: the plan's one launch with the variant's kernel and descriptor (as one captured graph where the plan would be one)
+static int issue_dcfr(rs_solver *s, int p) {
+    rs_table *t = s->table;
+    const JitLaunch &JL = s->dcfr.jit[p];
+    size_t blocks = std::min<size_t>(std::max<size_t>((size_t(JL.max_n_vec) + JL.threads - 1) / JL.threads, 1), 256 * 16);
+    if (s->knobs.max_blocks != kUnset) blocks = std::max<size_t>(1, std::min<size_t>(blocks, size_t(std::max(1, s->knobs.max_blocks))));
+    const void *d_blob = JL.d_blob;
+    int flags = s->params.mode & ~RS_UPD_ARITH_MASK;
+    void *params[] = {&d_blob, &flags};
+    prof_begin(t, RS_K_TREE, JL.bytes);
+    const hipError_t e = hipModuleLaunchKernel(JL.fn, (unsigned)blocks, 1, 1, (unsigned)JL.threads, 1, 1, 0, t->stream, params, nullptr);
+    prof_end(t);
+    RS_HIP(e, "discounted sweep launch");
+    return RS_OK;
+}
+static int run_dcfr_sweep(rs_solver *s, int p) {
+    rs_table *t = s->table;
+    rs_solver::Dcfr &D = s->dcfr;
+    if (s->params.use_graph && !t->prof.on) {
+        if (!D.graph_exec[p]) {
+            RS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
+            const int rc = issue_dcfr(s, p);
+            hipError_t e = hipStreamEndCapture(t->stream, D.graph[p].put());
+            if (rc != RS_OK) return rc;
+            RS_HIP(e, "hipStreamEndCapture");
+            RS_HIP(hipGraphInstantiate(D.graph_exec[p].put(), D.graph[p], nullptr, nullptr, 0), "hipGraphInstantiate");
+        }
+        RS_HIP(hipGraphLaunch(D.graph_exec[p], t->stream), "hipGraphLaunch");
+    } else if (int rc = issue_dcfr(s, p)) return rc;
+    ++t->epoch;
+    return RS_OK;
+}
+// Both sweeps of one iteration with a tick that may be pending from the iteration before.  Traverser 0's sweep discounts player 0's rows as it loads them (and stores them
+// updated) and player 1's regrets for regret matching alone; traverser 1's sweep discounts player 1's rows -- still as the tick found them -- and reads player 0's as
+// just written.  The words are written in front of the sweeps whenever they change; a captured graph replays unchanged.
+static int run_dcfr_iteration(rs_solver *s, bool pending, const float *f) {
+    rs_table *t = s->table;
+    rs_solver::Dcfr &D = s->dcfr;
+    if (pending || D.armed) {
+        const DcfrSide off{0u, 1.0f, 1.0f, 1.0f}, on{1u, f[0], f[1], f[2]};
+        DcfrArm v;
+        v.side[0] = v.side[1] = v.side[3] = pending ? on : off;
+        v.side[2] = off;
+        RS_HIP(launch_dcfr_arm(reinterpret_cast<DcfrSide *>(D.jit[0].d_blob + D.off_dc), reinterpret_cast<DcfrSide *>(D.jit[1].d_blob + D.off_dc), v, t->stream), "k_dcfr_arm");
+        D.armed = pending;
+    }
+    if (int rc = run_dcfr_sweep(s, 0)) return rc;
+    return run_dcfr_sweep(s, 1);
+}
+
 static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
                               const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out) {
     if (!table || !tree || !leaves_p0 || !leaves_p1 || !params || !out)
@@ -1489,6 +1609,57 @@ int rs_train(rs_solver *s, uint64_t iterations, uint64_t discount_interval, uint
     }
     const int rc_off = solver_kept_primary(s, false);
     return rc != RS_OK ? rc : rc_off;
+}
+
+// Discounted CFR (Brown & Sandholm 2019) over full sweeps: per iteration both traversers sweep, t += 1 (from t0), and after iteration t with t <= cap and t % interval == 0
+// a tick with the three factors of p = t / interval.  Fused (dcfr_eligible, setup_dcfr): the tick stays pending and the next iteration's sweeps apply it to the rows they
+// load -- no pass of its own over the table; a tick still pending when the loop ends is swept.  Otherwise rs_discount_dcfr between the iterations.
+// kDcfrFusedDefault: what RS_FORM_DEFAULT means for an eligible solver (profiles/dcfr.md).
+constexpr bool kDcfrFusedDefault = true;
+int rs_train_dcfr(rs_solver *s, uint64_t iterations, const rs_dcfr_params *params) {
+    if (!s || !params) return fail(RS_ERR_INVALID, "rs_train_dcfr: NULL argument");
+    if (params->interval == 0) return fail(RS_ERR_INVALID, "rs_train_dcfr: interval must be > 0");
+    if (params->fused != RS_FORM_DEFAULT && params->fused != RS_FORM_ON && params->fused != RS_FORM_OFF) return fail(RS_ERR_INVALID, "rs_train_dcfr: fused must be an RS_FORM_* value");
+    {
+        float probe[3];
+        if (int rc = rs_dcfr_factors(params->alpha, params->beta, params->gamma, 1, probe)) return rc;   // NaN exponents, an infinite gamma
+    }
+    if (!s->table) return fail(RS_ERR_INVALID, "rs_train_dcfr: the solver's table has been destroyed");
+    rs_table *t = s->table;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    s->dcfr.last_fused = 0;
+    const bool fused = params->fused != RS_FORM_OFF && (params->fused == RS_FORM_ON || kDcfrFusedDefault) && dcfr_eligible(s);
+    if (fused)
+        if (int rc = setup_dcfr(s)) return rc;
+    if (int rc = table_settle(t, fused)) return rc;   // a held pair sweep first; the fused sweeps go to the table's rows
+    if (!fused && iterations >= kKeptPrimaryMinTrips)
+        if (int rc = solver_kept_primary(s, true)) return rc;   // as rs_train: equal factors (Linear CFR) sweep the working copy, unequal ones end it at their first tick
+    uint64_t it = params->t0;
+    bool pending = false;
+    float f[3] = {1.0f, 1.0f, 1.0f};
+    int rc = RS_OK;
+    for (uint64_t k = 0; k < iterations && rc == RS_OK; ++k) {
+        if (fused) {
+            rc = run_dcfr_iteration(s, pending, f);
+            pending = false;
+        } else {
+            for (int player = 0; player < 2 && rc == RS_OK; ++player) rc = rs_iterate(s, player, nullptr);
+        }
+        if (rc != RS_OK) break;
+        it += 1;
+        if (it > params->cap || it % params->interval != 0) continue;
+        if ((rc = rs_dcfr_factors(params->alpha, params->beta, params->gamma, it / params->interval, f)) != RS_OK) break;
+        if (fused) pending = true;
+        else rc = rs_discount_dcfr(t, f[0], f[1], f[2]);
+    }
+    if (rc == RS_OK && pending) rc = rs_discount_dcfr(t, f[0], f[1], f[2]);   // the pending state never outlives the call
+    const int rc_off = fused ? RS_OK : solver_kept_primary(s, false);
+    if (rc == RS_OK && fused) s->dcfr.last_fused = 1;
+    return rc != RS_OK ? rc : rc_off;
+}
+int rs_solver_dcfr_fused(const rs_solver *s) {
+    if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
+    return s ? s->dcfr.last_fused : RS_ERR_INVALID;
 }
 
 size_t rs_solver_workspace_bytes(const rs_solver *s) { return s ? s->dev_bytes : 0; }

@@ -766,6 +766,53 @@ int rs_discount(rs_table *t, float d) {
     return RS_OK;
 }
 
+// ---- Discounted CFR (Brown & Sandholm, "Solving Imperfect-Information Games via Discounted Regret Minimization", AAAI 2019) ----------------
+int rs_dcfr_params_default(rs_dcfr_params *out) {
+    if (!out) return fail(RS_ERR_INVALID, "rs_dcfr_params_default: out is NULL");
+    *out = rs_dcfr_params{};
+    out->alpha = 1.5;
+    out->beta = 0.0;
+    out->gamma = 2.0;
+    out->interval = 1;
+    out->cap = UINT64_MAX;
+    out->t0 = 0;
+    out->fused = RS_FORM_DEFAULT;
+    return RS_OK;
+}
+
+// x / (x + 1) for x = p^e in double; e = +inf is the limit 1, e = -inf the limit 0, whatever p is; a power that overflows double is 1 as well
+static double dcfr_ratio(double p, double e) {
+    if (std::isinf(e)) return e > 0 ? 1.0 : 0.0;
+    const double x = std::pow(p, e);
+    return std::isinf(x) ? 1.0 : x / (x + 1.0);
+}
+int rs_dcfr_factors(double alpha, double beta, double gamma, uint64_t p, float out[3]) {
+    if (!out) return fail(RS_ERR_INVALID, "rs_dcfr_factors: out is NULL");
+    if (p == 0) return fail(RS_ERR_INVALID, "rs_dcfr_factors: p must be > 0 (the first tick comes after the first interval)");
+    if (std::isnan(alpha) || std::isnan(beta) || !std::isfinite(gamma)) return fail(RS_ERR_INVALID, "rs_dcfr_factors: alpha and beta must not be NaN, gamma must be finite");
+    const double pd = double(p);
+    out[0] = float(dcfr_ratio(pd, alpha));
+    out[1] = float(dcfr_ratio(pd, beta));
+    out[2] = float(std::pow(pd / (pd + 1.0), gamma));
+    return RS_OK;
+}
+
+int rs_discount_dcfr(rs_table *t, float d_pos, float d_neg, float d_sum) {
+    if (!t) return fail(RS_ERR_INVALID, "rs_discount_dcfr: table is NULL");
+    if (d_pos == d_neg && d_neg == d_sum) return rs_discount(t, d_pos);   // one factor: rs_discount's sweep, kept shadow records included
+    // Kept shadow records hold regrets and strategy sums interleaved per cluster; the sweep over them (solver_discount_primary, solver_table_discounted) treats the buffer as two
+    // anonymous halves, which is only right for one factor.  So: the table's rows up to date (a training loop's working copy written back, which ends it), the table swept,
+    // and the records rebuilt from it before the next sweep, as after any other write to the table (rs_table.epoch).  Cost of the rebuild per tick: profiles/dcfr.md.
+    if (int rc = table_settle(t, true)) return rc;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    prof_begin(t, RS_K_DISCOUNT, double(t->n_cells) * 4.0 * elem_size(t->dtype));
+    hipError_t e = launch_discount3(t->d_regrets, t->d_ssum, t->n_cells, d_pos, d_neg, d_sum, t->dtype, t->stream);
+    prof_end(t);
+    RS_HIP(e, "k_discount3");
+    ++t->epoch;
+    return RS_OK;
+}
+
 // ---- showdown signs from cards ------------------------------------------------------------------------------
 int rs_showdown_sign(rs_table *t, const uint8_t *d_cards, uint32_t n_deals, float *d_sign) {
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)

@@ -40,6 +40,8 @@ struct rs_deal_trainer {
     bool live_prune = false;           // the live batch has deals beyond the threshold
     uint64_t live_first = 0, staged_first = 0;   // global number of deal 0 of the live / staged batch
     int tick_br = 0;                   // calc_br at every discount tick (cfr.rs:244-246)
+    bool dcfr_on = false;              // rs_deal_trainer_set_dcfr: the ticks sweep with Discounted CFR's three factors instead of cfr.rs:248-249's one
+    rs_dcfr_params dcfr{};
     float last_br[2] = {0.0f, 0.0f};
     uint64_t last_br_t = 0;
     bool have_br = false;
@@ -392,12 +394,29 @@ int rs_deal_trainer_finish_batch(rs_deal_trainer *tr) {
             tr->last_br_t = tr->t;
             tr->have_br = true;
         }
-        if (int rc = rs_discount(tr->table, rs_discount_factor(tr->t, tr->params.discount_interval))) return rc;   // cfr.rs:248-261
+        if (tr->dcfr_on) {   // the reference's tick, Discounted CFR's factors at p = t / interval: a function of t alone, the same on every rank
+            float f[3];
+            if (int rc = rs_dcfr_factors(tr->dcfr.alpha, tr->dcfr.beta, tr->dcfr.gamma, tr->t / tr->params.discount_interval, f)) return rc;
+            if (int rc = rs_discount_dcfr(tr->table, f[0], f[1], f[2])) return rc;
+        } else if (int rc = rs_discount(tr->table, rs_discount_factor(tr->t, tr->params.discount_interval))) return rc;   // cfr.rs:248-261
         tr->threshold = tr->t + tr->params.discount_interval;     // cfr.rs:262
     }
     return RS_OK;
 }
 
+int rs_deal_trainer_set_dcfr(rs_deal_trainer *tr, const rs_dcfr_params *params) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
+    if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_dcfr: trainer is NULL");
+    if (!params) {   // back to cfr.rs:248-261
+        tr->dcfr_on = false;
+        return RS_OK;
+    }
+    float probe[3];
+    if (int rc = rs_dcfr_factors(params->alpha, params->beta, params->gamma, 1, probe)) return rc;
+    tr->dcfr = *params;   // only the exponents are read: when a tick comes stays the trainer's own rule (discount_interval, discount_cap)
+    tr->dcfr_on = true;
+    return RS_OK;
+}
 int rs_deal_trainer_set_tick_br(rs_deal_trainer *tr, int enable) {
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_tick_br: trainer is NULL");
     tr->tick_br = enable;

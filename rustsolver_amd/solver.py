@@ -441,6 +441,10 @@ class InfosetTable:
         """cfr.rs:250-261"""
         L.check(L.load().rs_discount(self._h, float(d)))
 
+    def discount_dcfr(self, d_pos, d_neg, d_sum):
+        """rs_discount_dcfr: regrets > 0 times d_pos, the other regrets times d_neg, strategy sums times d_sum (three equal factors = discount(d))"""
+        L.check(L.load().rs_discount_dcfr(self._h, float(d_pos), float(d_neg), float(d_sum)))
+
     def sync(self):
         L.check(L.load().rs_sync(self._h))
 
@@ -638,6 +642,18 @@ class MCCFRTrainer:
                                   discount_cap or self.DISCOUNT_CAP))
         self.infosets.sync()
 
+    def train_dcfr(self, iterations, alpha=1.5, beta=0.0, gamma=2.0, interval=1, cap=None, t0=0, fused=None):
+        """rs_train_dcfr: Discounted CFR over full sweeps -- a tick with dcfr_factors(alpha, beta, gamma, t / interval) after every iteration t <= cap with t % interval == 0,
+        t counted from t0.  fused: None = the engine's choice, True / False = apply a pending tick inside the next sweeps' row loads where the solver can / sweep every tick"""
+        p = dcfr_params(alpha, beta, gamma, interval, cap, t0, fused)
+        L.check(L.load().rs_train_dcfr(self._h, iterations, C.byref(p)))
+        self.infosets.sync()
+
+    @property
+    def dcfr_fused(self):
+        """the last train_dcfr applied its ticks inside the sweeps (rs_solver_dcfr_fused)"""
+        return bool(L.load().rs_solver_dcfr_fused(self._h))
+
     def destroy(self):
         if self._h:
             L.load().rs_solver_destroy(self._h)
@@ -737,6 +753,14 @@ class DealTrainer:
     @property
     def iterations(self):
         return int(L.load().rs_deal_trainer_iterations(self._h))
+
+    def set_dcfr(self, alpha=1.5, beta=0.0, gamma=2.0, enable=True):
+        """rs_deal_trainer_set_dcfr: the trainer's discount ticks sweep with Discounted CFR's three factors at p = t / discount_interval; enable=False: back to cfr.rs:248-261"""
+        if not enable:
+            L.check(L.load().rs_deal_trainer_set_dcfr(self._h, None))
+            return
+        p = dcfr_params(alpha, beta, gamma)
+        L.check(L.load().rs_deal_trainer_set_dcfr(self._h, C.byref(p)))
 
     def set_tick_br(self, enable=True):
         """calc_br at every discount tick, as train() does (cfr.rs:244-246)"""
@@ -845,6 +869,32 @@ def jit_check_pair(tree, dtype=L.I32, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_FULL)
     n = C.c_int()
     L.check(L.load().rs_jit_check_pair(tree._h, dtype, mode, opp_mode, C.byref(n)))
     return n.value
+
+
+def jit_check_dcfr(tree, dtype=L.I32, mode=L.UPD_CLAMP_I64):
+    """compile (no GPU needed) the discounted variants (train_dcfr, fused) of both traversers' lane kernels of every topmost chance-free subtree of `tree`; returns the number
+    of distinct kernels"""
+    n = C.c_int()
+    L.check(L.load().rs_jit_check_dcfr(tree._h, dtype, mode, C.byref(n)))
+    return n.value
+
+
+def dcfr_params(alpha=1.5, beta=0.0, gamma=2.0, interval=1, cap=None, t0=0, fused=None):
+    """an rs_dcfr_params: rs_dcfr_params_default with the given fields"""
+    p = L.DcfrParams()
+    L.check(L.load().rs_dcfr_params_default(C.byref(p)))
+    p.alpha, p.beta, p.gamma, p.interval, p.t0 = float(alpha), float(beta), float(gamma), int(interval), int(t0)
+    if cap is not None:
+        p.cap = int(cap)
+    p.fused = L.FORM_DEFAULT if fused is None else (L.FORM_ON if fused else L.FORM_OFF)
+    return p
+
+
+def dcfr_factors(alpha, beta, gamma, p):
+    """rs_dcfr_factors: (pos, neg, sum) of tick number p > 0 as float32"""
+    out = (C.c_float * 3)()
+    L.check(L.load().rs_dcfr_factors(float(alpha), float(beta), float(gamma), int(p), out))
+    return np.array(out[:], dtype=np.float32)
 
 
 def jit_check_tree_deals(tree, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_SAMPLE):
