@@ -46,7 +46,8 @@ extern "C" {
                               6: rs_deal_trainer_params.table_dtype (was `reserved`: zero = RS_I32 means what it meant), float deal tables RS_F16 and RS_UPD_RMPLUS,
                                  rs_solver_exchange_bytes (diagnostics), data-parallel sweeps keep direct rows;
                                  still 6: Discounted CFR (rs_dcfr_params, rs_dcfr_params_default, rs_dcfr_factors, rs_discount_dcfr, rs_train_dcfr, rs_solver_dcfr_fused,
-                                 rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning */
+                                 rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning;
+                                 still 6: RS_BR_REAL (a mode bit of rs_best_response, rs_best_response_rounds, rs_deal_trainer_best_response) -- modes without it mean what they meant */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -220,6 +221,14 @@ enum { RS_BR_MAX = 0, RS_BR_AVERAGE = 1,
                                     difference of prefix sums of the opponent's reach over that order, corrected for the hands that hold one of the traverser's cards --
                                     O(n log n) per run-out instead of the pair loop of cfr.rs:323-347 (full 1 176-combo ranges from a flop: 3.1 s -> ~0.2 s per call).  The
                                     sums run in a fixed order of their own: equal to the pair loop within f64 rounding (1e-12 relative), identical to the oracle's sorted mode */
+enum { RS_BR_REAL = 0x200 };     /* OR into RS_BR_MAX (optionally with RS_BR_SORTED): the best response in the REAL game against the abstracted average strategy.  The
+                                    traverser sees its own two cards: at each of its nodes of round r every (prefix of round r, hand) pair that is a deal (the hand holds none
+                                    of the prefix's new cards) takes the action with the largest sum of its lanes' counterfactual values over the run-outs of that prefix, added
+                                    in ascending run-out order, first maximum; lanes whose hand holds a later card of the run-out are no deals (not added, worth 0).  The opponent
+                                    plays its average strategy through cluster[...] as before; the traverser's own ids are validated but not read for its decisions.  out[p] in
+                                    the same per-deal units: (out[0] + out[1]) / 2 is the exploitability of the average profile in the real game -- never below the abstract
+                                    number, equal to it where every (prefix, hand) pair is a cluster of its own, and the one to compare abstractions by.  RS_BR_AVERAGE | RS_BR_REAL: RS_ERR_INVALID
+                                    (the average strategy lives in the abstraction) */
 int rs_best_response(rs_table *table, const rs_tree *tree, const uint8_t *board, const uint8_t *hands_p0, size_t n_hands_p0, const uint32_t *cluster_p0,
                      const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *cluster_p1, int mode, double *out /*[2]*/);
 /* The same over MULTI-ROUND trees (flop or turn start).  A lane is (run-out b, hand h): generate_hand (cfr.rs:100-143) completes the board to five cards first --
@@ -228,7 +237,8 @@ int rs_best_response(rs_table *table, const rs_tree *tree, const uint8_t *board,
  * first r new cards, prefixes and run-outs enumerated with the first new card most significant, cards ascending among those still in the deck (rs_br_runouts writes
  * the run-outs, [NB][5], and returns NB = 1, 48 or 2 352); entries of (prefix, hand) pairs that share a card are ignored.  RS_BR_MAX: at each of p's nodes every cluster
  * takes the action with the largest SUM of its lanes' counterfactual values over all run-outs and hands -- the best response inside the abstraction when it has perfect
- * recall, otherwise the value of a valid pure strategy of the abstracted game (a lower bound).  f64, fixed-order sums; synchronises. */
+ * recall, otherwise the value of a valid pure strategy of the abstracted game: a lower bound on what a responder who sees its own cards takes -- RS_BR_MAX | RS_BR_REAL
+ * computes that number, the best response in the real game.  f64, fixed-order sums; synchronises. */
 int rs_best_response_rounds(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
                             const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, int mode, double *out /*[2]*/);
 size_t rs_br_runouts(const uint8_t *board0, int n_board0, uint8_t *out_cards /* [NB][5], may be NULL */);

@@ -993,6 +993,136 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_cols_jobs(const void *__res
     }
 }
 
+// ---- own nodes in the real game (RS_BR_MAX | RS_BR_REAL) ---------------------------------------------------------------------------------------------------------
+// The traverser sees its own two cards: an info set of round r is (prefix of round r, hand), and its lanes are hand h under the run-outs [f * pp, (f + 1) * pp) of the
+// prefix (pp = per_prefix[r]; enumerate_runouts puts the first new card most significant) -- lane (f * pp + k) * n_hands + h, an arithmetic progression.  No lists, no
+// cluster ids: a thread takes a (prefix, hand) pair, neighbouring threads neighbouring hands, so run-out k of a wave's info sets is ONE stretch of a row.  Lanes whose hand
+// holds a card of the run-out are no deal: not added, worth 0.  The sums run down the run-outs in ascending order from 0.0 and the first maximum under strict < wins --
+// what br_own_body computes when every (prefix, hand) pair is a cluster of its own, bit for bit.
+// A child that is an opponent's node (level plan) is not summed by k_br_sum_jobs first: its children's rows are added up here in action order from 0.0 (br_sum_body's
+// additions) as they are loaded, as k_br_own_grouped_jobs does.
+struct BrRealChild {
+    const double *row;   // ns == 0: the child's row; else the first of ns rows, n_pad apart, whose sum in order is the child's row
+    uint32_t ns;
+};
+__device__ __forceinline__ BrRealChild br_real_child(const double *__restrict__ vch, const BrJob *__restrict__ jp, uint32_t a, uint32_t n_pad) {
+    if (jp && jp->sum_n[a]) return {jp->sum_src[a], jp->sum_n[a]};   // (read where they lie: indexed by the action)
+    return {vch + (size_t)a * n_pad, 0u};
+}
+template <int N>
+__device__ __forceinline__ void br_real_load(BrRealChild ch, uint32_t n_pad, const uint32_t (&lane)[N], double (&t)[N]) {
+    if (ch.ns == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) t[q] = ch.row[lane[q]];
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) t[q] = 0.0;
+    for (uint32_t c = 0; c < ch.ns; c++) {
+        const double *vc = ch.row + (size_t)c * n_pad;
+#pragma unroll
+        for (int q = 0; q < N; q++) t[q] += vc[lane[q]];
+    }
+}
+// the last round (pp == 1): an info set is a single lane, the node an element-wise first maximum over its children's rows -- every child row read once, the node's row
+// written once, all of it whole rows
+__device__ __forceinline__ void br_own_real_last_body(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
+                                                      uint32_t n_actions, const double *__restrict__ vch, const BrJob *__restrict__ jp, double *__restrict__ v) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    const uint32_t b = lane / n_hands, h = lane - b * n_hands;
+    if (mask_p[h] & bmask[b]) {
+        v[lane] = 0.0;
+        return;
+    }
+    const uint32_t at[1] = {lane};
+    double t[RS_MAX_ACTIONS][1];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)   // every child's value on its way before the first comparison
+        if ((uint32_t)a < n_actions) br_real_load<1>(br_real_child(vch, jp, (uint32_t)a, n_pad), n_pad, at, t[a]);
+    double best = t[0][0];
+#pragma unroll
+    for (int a = 1; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < n_actions && best < t[a][0]) best = t[a][0];   // first maximum, strict < (cfr.rs:684-690); the sum of one lane compares as the lane
+    v[lane] = best;
+}
+// earlier rounds (pp = 48 or 2 352 run-outs per info set): a workgroup takes 64 neighbouring (prefix, hand) pairs, and its four waves share the ACTIONS (wave w adds up
+// actions w, w + 4, ...): each action's additions stay sequential down the run-outs, eight loads in flight as in k_br_own_cols_jobs, and a flop node of n_hands info sets
+// gets four times the waves a thread per info set would give it.  The sums meet in 4 KB of LDS, every thread picks its pair's leader, and the waves share the run-outs of
+// the write-back in blocks of eight.  (A thread per (info set, action) with the choice made through LDS: the split the chain of 2 352 dependent additions asks for; the
+// lanes themselves never pass through LDS.)
+constexpr int kBrRealPairs = 64, kBrRealWaves = kBrBlock / 64, kBrRealFlight = 8;
+__device__ __forceinline__ void br_own_real_cols_body(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs, uint32_t pp,
+                                                      uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, const BrJob *__restrict__ jp, double *__restrict__ v) {
+    __shared__ double sums[RS_MAX_ACTIONS][kBrRealPairs];
+    const uint32_t x = threadIdx.x & 63u, w = threadIdx.x >> 6, pair = blockIdx.x * kBrRealPairs + x;
+    const bool valid = pair < n_pairs;
+    const uint32_t f = valid ? pair / n_hands : 0u, h = valid ? pair - f * n_hands : 0u;
+    const uint64_t mine = mask_p[h];
+    const uint64_t *__restrict__ bm = bmask + (size_t)f * pp;
+    const uint32_t lane0 = f * pp * n_hands + h;   // run-out k of the pair: lane0 + k * n_hands (below n < 2^31)
+    if (valid)
+        for (uint32_t a = w; a < n_actions; a += kBrRealWaves) {
+            const BrRealChild ch = br_real_child(vch, jp, a, n_pad);
+            double acc = 0.0;
+            for (uint32_t k = 0; k < pp; k += kBrRealFlight) {
+                uint32_t lane[kBrRealFlight];
+                bool deal[kBrRealFlight];
+                double t[kBrRealFlight];
+#pragma unroll
+                for (int q = 0; q < kBrRealFlight; q++) {
+                    const uint32_t kk = min(k + q, pp - 1);
+                    lane[q] = lane0 + kk * n_hands;
+                    deal[q] = k + q < pp && !(mine & bm[kk]);
+                }
+                br_real_load<kBrRealFlight>(ch, n_pad, lane, t);
+#pragma unroll
+                for (int q = 0; q < kBrRealFlight; q++)
+                    if (deal[q]) acc += t[q];   // ascending run-outs, one after the other
+            }
+            sums[a][x] = acc;
+        }
+    __syncthreads();
+    if (!valid) return;
+    uint32_t best = 0;
+    for (uint32_t a = 1; a < n_actions; a++)
+        if (sums[best][x] < sums[a][x]) best = a;   // first maximum, strict < (cfr.rs:684-690)
+    const BrRealChild ch = br_real_child(vch, jp, best, n_pad);
+    for (uint32_t k = w * kBrRealFlight; k < pp; k += kBrRealWaves * kBrRealFlight) {
+        uint32_t lane[kBrRealFlight];
+        bool deal[kBrRealFlight];
+        double t[kBrRealFlight];
+#pragma unroll
+        for (int q = 0; q < kBrRealFlight; q++) {
+            const uint32_t kk = min(k + q, pp - 1);
+            lane[q] = lane0 + kk * n_hands;
+            deal[q] = !(mine & bm[kk]);
+        }
+        br_real_load<kBrRealFlight>(ch, n_pad, lane, t);
+#pragma unroll
+        for (int q = 0; q < kBrRealFlight; q++)
+            if (k + q < pp) v[lane[q]] = deal[q] ? t[q] : 0.0;
+    }
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_own_real_last(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
+                                                               uint32_t n_actions, const double *__restrict__ vch, double *__restrict__ v) {
+    br_own_real_last_body(mask_p, bmask, n_hands, n, n_pad, n_actions, vch, nullptr, v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_own_real_last_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
+                                                                    uint32_t n_pad, const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_own_real_last_body(mask_p, bmask, n_hands, n, n_pad, jp->n_children, jp->vch, jp, jp->v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
+                                                               uint32_t pp, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, double *__restrict__ v) {
+    br_own_real_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, n_actions, vch, nullptr, v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
+                                                                    uint32_t pp, uint32_t n_pad, const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_own_real_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, jp->n_children, jp->vch, jp, jp->v);
+}
+
 // ---- the kernels: one node per launch (the depth-first walk), or one JOB per node and grid row (the level plan: all nodes of one tree depth and kind in one launch) -------------
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_opp_reach(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
@@ -1093,6 +1223,8 @@ struct BrRun {
     const rs_tree *tree = nullptr;
     int mode = RS_BR_MAX;
     bool sorted = false;           // RS_BR_SORTED: showdowns by rank order
+    bool real = false;             // RS_BR_REAL (this call): the traverser's info sets are (prefix, hand), its own nodes go to k_br_own_real_*
+    uint32_t per_prefix[RS_MAX_ROUNDS] = {1, 1, 1};   // run-outs under a prefix of round r
     int p = 0;
     uint32_t NB = 1;
     uint64_t *d_bmask = nullptr;
@@ -1164,7 +1296,9 @@ struct BrRun {
         std::vector<std::pair<int, int>> grp_at(N, {-1, -1});   // an own node taken by groups: (round, index in up_grp[round][depth])
         std::vector<std::vector<BrJob>> up_cols(size_t(max_depth) + 1);   // own nodes by columns
         std::vector<std::vector<BrJob>> up_grp[RS_MAX_ROUNDS], down_grp[RS_MAX_ROUNDS];   // own / opponent nodes taken by groups of run-outs, per round (the groups are the round's)
+        std::vector<std::vector<BrJob>> up_real[RS_MAX_ROUNDS];   // own nodes in the real game, per round (the round's run-outs per prefix shape the grid); grp_at serves them too
         for (auto &v : up_grp) v.resize(size_t(max_depth) + 1);
+        for (auto &v : up_real) v.resize(size_t(max_depth) + 1);
         for (auto &v : down_grp) v.resize(size_t(max_depth) + 1);
         std::vector<BrJob> leaves;
         for (size_t id = 0; id < N; ++id) {   // parents before children: a node's q and v slot are known when it comes up
@@ -1200,7 +1334,11 @@ struct BrRun {
                 j.start = me.d_start[r];
                 j.order = me.d_order[r];
                 j.n_clusters = me.n_clusters[r];
-                if (mode == RS_BR_MAX && me.grouped[r]) {
+                if (real) {   // whatever the abstraction's lists would have asked for
+                    grp_at[id] = {r, int(up_real[r][size_t(d)].size())};
+                    up_real[r][size_t(d)].push_back(j);
+                }
+                else if (mode == RS_BR_MAX && me.grouped[r]) {
                     grp_at[id] = {r, int(up_grp[r][size_t(d)].size())};
                     up_grp[r][size_t(d)].push_back(j);
                 }
@@ -1220,12 +1358,12 @@ struct BrRun {
                 j.q = q_in[id];
                 j.q_out = qch[id];
                 (op.grouped[r] ? down_grp[r] : down)[size_t(d)].push_back(j);
-                // its value is the sum of its children's; where the parent is an own node taken by groups, that kernel adds the rows up as it stages them
+                // its value is the sum of its children's; where the parent is an own node taken by groups (or in the real game), that kernel adds the rows up as it loads them
                 const int par = n.parent;
                 bool taken = false;
                 if (par >= 0 && grp_at[size_t(par)].first >= 0) {
                     const rs_tree_node &pn = tree->nodes[size_t(par)];
-                    BrJob &pj = up_grp[grp_at[size_t(par)].first][size_t(depth_of[size_t(par)])][size_t(grp_at[size_t(par)].second)];
+                    BrJob &pj = (real ? up_real : up_grp)[grp_at[size_t(par)].first][size_t(depth_of[size_t(par)])][size_t(grp_at[size_t(par)].second)];
                     for (int a = 0; a < pn.n_children && !taken; ++a)
                         if (pn.children[a] == int(id)) {
                             pj.sum_src[a] = vch[id];
@@ -1245,13 +1383,14 @@ struct BrRun {
             all.insert(all.end(), v.begin(), v.end());
             return at_;
         };
-        std::vector<size_t> o_down, o_own, o_wave, o_sum, o_cols, o_grp[RS_MAX_ROUNDS], o_dgrp[RS_MAX_ROUNDS];
+        std::vector<size_t> o_down, o_own, o_wave, o_sum, o_cols, o_grp[RS_MAX_ROUNDS], o_dgrp[RS_MAX_ROUNDS], o_real[RS_MAX_ROUNDS];
         for (int d = 0; d <= max_depth; ++d) {
             o_down.push_back(put(down[size_t(d)]));
             o_cols.push_back(put(up_cols[size_t(d)]));
             o_own.push_back(put(up_own[size_t(d)]));
             for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_grp[r].push_back(put(up_grp[r][size_t(d)]));
             for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_dgrp[r].push_back(put(down_grp[r][size_t(d)]));
+            for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_real[r].push_back(put(up_real[r][size_t(d)]));
             o_wave.push_back(put(up_wave[size_t(d)]));
             o_sum.push_back(put(up_sum[size_t(d)]));
         }
@@ -1354,6 +1493,12 @@ struct BrRun {
                     err = hipGetLastError();
                     ++n_launches;
                 }
+            for (int r = 0; r < RS_MAX_ROUNDS && err == hipSuccess; ++r)
+                if (const uint32_t nj = uint32_t(up_real[r][size_t(d)].size())) {
+                    launch_real(r, nj, d_jobs + o_real[r][size_t(d)], 0, nullptr, nullptr);
+                    err = hipGetLastError();
+                    ++n_launches;
+                }
             if (const uint32_t nj = uint32_t(up_own[size_t(d)].size())) {
                 uint32_t ncl = 0;
                 for (const BrJob &j : up_own[size_t(d)]) ncl = std::max(ncl, j.n_clusters);
@@ -1373,6 +1518,20 @@ struct BrRun {
         return err == hipSuccess ? RS_OK : hip_fail(err, "rs_best_response (level plan)");
     }
     int n_launches = 0;
+
+    // the traverser's own nodes of round r in the real game: the node (vch -> v) of the depth-first walk, or nj jobs of the level plan
+    void launch_real(int r, uint32_t nj, const BrJob *jobs, uint32_t n_actions, const double *vch, double *v) {
+        const BrSide &me = side[p];
+        const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
+        if (pp == 1) {
+            if (jobs) hipLaunchKernelGGL(k_br_own_real_last_jobs, dim3(grid1(me.n), nj), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, jobs);
+            else hipLaunchKernelGGL(k_br_own_real_last, dim3(grid1(me.n)), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, n_actions, vch, v);
+            return;
+        }
+        const uint32_t blocks = (n_pairs + kBrRealPairs - 1) / kBrRealPairs;
+        if (jobs) hipLaunchKernelGGL(k_br_own_real_cols_jobs, dim3(blocks, nj), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, jobs);
+        else hipLaunchKernelGGL(k_br_own_real_cols, dim3(blocks), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, n_actions, vch, v);
+    }
 
     void walk(int id, const double *q, double *v_out, int level) {
         if (err != hipSuccess) return;
@@ -1402,7 +1561,8 @@ struct BrRun {
         if (int(n.player) == p) {
             for (int a = 0; a < n.n_children; ++a) walk(n.children[a], q, vch + size_t(a) * me.n_pad, level + 1);
             if (err != hipSuccess) return;
-            if (size_t(me.n) >= size_t(me.n_clusters[r]) * 32) {   // many lanes per info set: a wave each
+            if (real) launch_real(r, 0, nullptr, uint32_t(n.n_children), vch, v_out);
+            else if (size_t(me.n) >= size_t(me.n_clusters[r]) * 32) {   // many lanes per info set: a wave each
                 const uint32_t blocks = uint32_t(std::min<size_t>((size_t(me.n_clusters[r]) * 64 + kBrBlock - 1) / kBrBlock, 8192));
 #define RS_OWNW(DT_)                                                                                                                                    \
     hipLaunchKernelGGL((k_br_own_wave<DT_>), dim3(blocks), dim3(kBrBlock), 0, t->stream, t->d_ssum, row, me.d_start[r], me.d_order[r], me.n_clusters[r], \
@@ -1692,6 +1852,7 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
     run.tree = tree;
     run.sorted = sorted;
     run.NB = uint32_t(NB);
+    for (int r = 0; r < RS_MAX_ROUNDS; ++r) run.per_prefix[r] = uint32_t(per_prefix[r]);
     run.d_bmask = run.upload(bmask);
     uint8_t *d_boards = run.upload(cards);
     uint32_t *d_cnt0 = run.upload(cnt0);
@@ -1795,15 +1956,25 @@ void br_release_workspace(BrRun *run) {
 }
 int br_last_launches(const BrRun *run) { return run && run->last_level_plan ? run->last_launches : -1; }
 
+static int br_check_mode(int mode /* without RS_BR_SORTED and RS_BR_REAL */, bool real) {
+    if (mode != RS_BR_MAX && mode != RS_BR_AVERAGE) return fail(RS_ERR_INVALID, "rs_best_response: mode is RS_BR_MAX or RS_BR_AVERAGE (| RS_BR_SORTED, RS_BR_MAX | RS_BR_REAL)");
+    if (real && mode != RS_BR_MAX)
+        return fail(RS_ERR_INVALID, "rs_best_response: RS_BR_REAL goes with RS_BR_MAX (the average strategy lives in the abstraction: RS_BR_AVERAGE | RS_BR_REAL means nothing)");
+    return RS_OK;
+}
+
 // the walk: both traversers against the table as it stands
 int br_execute(BrRun *prepared, int mode, double *out) {
     if (!prepared || !out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
-    if (mode != RS_BR_MAX && mode != RS_BR_AVERAGE) return fail(RS_ERR_INVALID, "rs_best_response: mode is RS_BR_MAX or RS_BR_AVERAGE (| RS_BR_SORTED)");
+    const bool real = (mode & RS_BR_REAL) != 0;
+    mode &= ~RS_BR_REAL;
+    if (int rc = br_check_mode(mode, real)) return rc;
     BrRun &run = *prepared;
     rs_table *t = run.t;
     if (int rc = table_settle(t)) return rc;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     run.mode = mode;
+    run.real = real;
     run.err = hipSuccess;
     // The level plan wants a buffer per tree edge (full 1 176-combo ranges from a flop on the 706-node tree: 59 GB, and an allocation of that size takes seconds; 200 combos: 10 GB)
     // and buys launches, not kernel time (4 300 -> 66 per call; at full ranges both orders spend 0.24-0.27 s in their kernels): it is taken while it fits kBrLevelPlanBytes and half
@@ -1863,7 +2034,7 @@ int rs_best_response_rounds(rs_table *t, const rs_tree *tree, const uint8_t *boa
     if (!out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
-    if (mode != RS_BR_MAX && mode != RS_BR_AVERAGE) return fail(RS_ERR_INVALID, "rs_best_response: mode is RS_BR_MAX or RS_BR_AVERAGE (| RS_BR_SORTED)");
+    if (int rc = rs::br_check_mode(mode & ~RS_BR_REAL, (mode & RS_BR_REAL) != 0)) return rc;
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
     const int rc = rs::br_execute(run, mode, out);

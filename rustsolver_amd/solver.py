@@ -366,7 +366,8 @@ class InfosetTable:
 
     def best_response(self, tree, board, hands0, cluster0, hands1, cluster1, mode=L.BR_MAX):
         """value per deal of each player against the other's average strategy: mode BR_MAX a best response inside the abstraction,
-        BR_AVERAGE its own average strategy; exploitability = best_response(...).sum() / 2"""
+        BR_MAX | BR_REAL a best response in the real game (every hand decides for itself), BR_AVERAGE its own average strategy;
+        exploitability = best_response(...).sum() / 2"""
         b = np.ascontiguousarray(board, dtype=np.uint8)
         h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
         h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
@@ -792,10 +793,11 @@ class DealTrainer:
     def br_launches(self, sorted_showdowns=True):
         return int(L.load().rs_deal_trainer_br_launches(self._h, int(sorted_showdowns)))
 
-    def exploitability(self, sorted_showdowns=True):
+    def exploitability(self, sorted_showdowns=True, real=False):
         """(BR value of player 0 + BR value of player 1) / 2 against the current average strategies, per deal, in pot units of the leaves.  sorted_showdowns: the leaves by
-        rank order (RS_BR_SORTED: O(n log n) per run-out, equal to the pair loop of cfr.rs:323-347 within f64 rounding)"""
-        return float(self.best_response(L.BR_MAX | (L.BR_SORTED if sorted_showdowns else 0)).sum() / 2.0)
+        rank order (RS_BR_SORTED: O(n log n) per run-out, equal to the pair loop of cfr.rs:323-347 within f64 rounding).  real: the responder plays the real game
+        (RS_BR_REAL: an info set is the board seen so far and its own two cards) instead of the abstraction -- never the smaller number, and the one to compare abstractions by"""
+        return float(self.best_response(L.BR_MAX | (L.BR_SORTED if sorted_showdowns else 0) | (L.BR_REAL if real else 0)).sum() / 2.0)
 
     def _download(self, ptr, dtype, count):
         out = np.empty(count, dtype=dtype)
