@@ -93,18 +93,6 @@ __global__ __launch_bounds__(kBrBlock) void k_hand_scores(const uint8_t *__restr
     score[h] = evaluate_suits(m);
 }
 
-// opponent node: q_a[h] = q[h] * sigma_bar(cluster(h), a) for every action (cfr.rs:585's reach product, over the whole range at once)
-template <int DT>
-__device__ __forceinline__ void br_opp_reach_body(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n,
-                                                           uint32_t n_pad, const double *__restrict__ q, double *__restrict__ q_out /*[A][n_pad]*/) {
-    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
-    if (h >= n) return;
-    float sig[RS_MAX_ACTIONS];
-    final_sigma<DT>(ssum, row.cell_off, row.pitch, row.n_actions, cid[h], sig);
-    const double qh = q[h];
-    for (uint32_t a = 0; a < row.n_actions; a++) q_out[(size_t)a * n_pad + h] = qh * (double)sig[a];
-}
-
 // terminal: v[hp] = pw[hp] * sum over the opponent's hands ho that share no card with hp, ascending, of q[ho] * u(hp, ho);
 // u as the trainer's leaves (cfr.rs:314-348): UNCONTESTED -pot for the folder / +pot for the other, SHOWDOWN and ALLIN +-pot by score, 0 on a tie
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
@@ -204,13 +192,8 @@ __device__ __forceinline__ void br_own_body(const void *__restrict__ ssum, BrNod
 }
 
 static unsigned grid1(uint32_t n) { return (n + kBrBlock - 1) / kBrBlock ? (n + kBrBlock - 1) / kBrBlock : 1; }
-
-#define RS_BR_DT(dtype_, CALL)                 \
-    do {                                       \
-        if ((dtype_) == RS_I32) { CALL(kDT_I32); } \
-        else if ((dtype_) == RS_F32) { CALL(kDT_F32); } \
-        else { CALL(kDT_F16); }                \
-    } while (0)
+// the kernel's instantiation for the table's cell type
+#define RS_BR_PICK(dtype_, K) ((dtype_) == RS_I32 ? K<kDT_I32> : ((dtype_) == RS_F32 ? K<kDT_F32> : K<kDT_F16>))
 
 // ---- host side of calc_br: cfr.rs:640-745 over the gathered bucket-0 strategies -------------------------------------------------
 struct Pay { float v[2]; };   // res[player][0]
@@ -295,9 +278,7 @@ int rs_calc_br(rs_table *t, const rs_tree *tree, float *out) {
         hipError_t e = d_prob.alloc(prob.size());
         if (e == hipSuccess) e = hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(BrNodeRow), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-#define RS_B0(DT_) hipLaunchKernelGGL((k_bucket0_final_strategy<DT_>), dim3(grid1(n_nodes)), dim3(kBrBlock), 0, t->stream, t->d_ssum.get(), d_rows.get(), n_nodes, d_prob.get())
-            RS_BR_DT(t->dtype, RS_B0);
-#undef RS_B0
+            hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_bucket0_final_strategy), dim3(grid1(n_nodes)), dim3(kBrBlock), 0, t->stream, t->d_ssum.get(), d_rows.get(), n_nodes, d_prob.get());
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(prob.data(), d_prob, prob.size() * sizeof(float), hipMemcpyDeviceToHost, t->stream);
@@ -904,7 +885,7 @@ __global__ __launch_bounds__(kBrGroupBlock) void k_br_own_grouped_jobs(const BrJ
 }
 
 // The opponent's reach through the same groups: sigma_bar of an info set is computed ONCE (a lane-parallel kernel gathers the strategy-sum rows for each of its 4.3 lanes)
-// into LDS; the group's lanes then stream through: q in, A products out, whole rows.  Lanes in no info set take cluster 0's strategy, as br_opp_reach_body has it (their
+// into LDS; the group's lanes then stream through: q in, A products out, whole rows.  Lanes in no info set take cluster 0's strategy, as k_br_opp_reach_jobs has it (their
 // reach is never looked at: the leaves skip hands that hold a card of the run-out).
 template <int DT>
 __global__ __launch_bounds__(kBrGroupBlock) void k_br_opp_reach_grouped_jobs(const void *__restrict__ ssum, const BrJob *__restrict__ jobs, BrGroups g, uint32_t n_pad) {
@@ -1123,7 +1104,19 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols_jobs(const uint64
     br_own_real_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, jp->n_children, jp->vch, jp, jp->v);
 }
 
-// ---- the kernels: one node per launch (the depth-first walk), or one JOB per node and grid row (the level plan: all nodes of one tree depth and kind in one launch) -------------
+// ---- the kernels: one node per launch, its pointers as kernel arguments (the depth-first walk), or one JOB per node and grid row (the level plan: all nodes of one tree
+// depth and kind in one launch).  Both forward to the same bodies; BrRun::launch picks. -----------------------------------------------------------------------------------
+// opponent node: q_a[h] = q[h] * sigma_bar(cluster(h), a) for every action (cfr.rs:585's reach product, over the whole range at once)
+template <int DT>
+__device__ __forceinline__ void br_opp_reach_body(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n,
+                                                           uint32_t n_pad, const double *__restrict__ q, double *__restrict__ q_out /*[A][n_pad]*/) {
+    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
+    if (h >= n) return;
+    float sig[RS_MAX_ACTIONS];
+    final_sigma<DT>(ssum, row.cell_off, row.pitch, row.n_actions, cid[h], sig);
+    const double qh = q[h];
+    for (uint32_t a = 0; a < row.n_actions; a++) q_out[(size_t)a * n_pad + h] = qh * (double)sig[a];
+}
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_opp_reach(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
                                                            const double *__restrict__ q, double *__restrict__ q_out) {
@@ -1196,6 +1189,22 @@ __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards_jobs(const uint
     br_terminal_boards_body(mask_p, score_p, pw, n_p, mask_o, score_o, j.q, n_o, bmask, j.uncontested, j.value, j.v);
 }
 
+// What a node asks of the device.  The kinds stand in the order of their launches within a tree depth -- reach on the way down, values on the way up -- which traces and
+// br_launches() show.  A new own-node form is a body, a kind here, a line in BrRun::own_kind and a case in BrRun::launch.
+enum BrKind { kBrReachGrouped, kBrReach, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnThread, kBrSum, kBrKinds };
+// launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
+static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal; }
+// P, Pc, O and Q of br_terminal_sorted_body
+static size_t br_sorted_leaf_lds(uint32_t n_o) { return (size_t(n_o) * 2 + 52 * kBrCardHolders + 65) * sizeof(double); }
+// a wave per info set (k_br_own_wave_jobs), where info sets hold many lanes
+static bool br_wave_per_info_set(uint32_t lanes, uint32_t n_clusters) { return size_t(lanes) >= size_t(n_clusters) * 32; }
+static uint32_t br_wave_blocks(uint32_t n_clusters) { return uint32_t(std::min<size_t>((size_t(n_clusters) * 64 + kBrBlock - 1) / kBrBlock, 8192)); }
+// what a leaf is worth to traverser p before the showdown decides the sign: tn.value as f32 (cfr.rs:316); UNCONTESTED -pot for the folder, +pot for the other (cfr.rs:314-348)
+static double br_terminal_value(const rs_tree_node &n, int p) {
+    const double pot = double(float(n.value));
+    return n.ttype == RS_TERM_UNCONTESTED && p == int(n.last_to_act) ? -pot : pot;
+}
+
 constexpr size_t kBrLevelPlanBytes = size_t(96) << 30;   // the level plan's workspace is kept with the object: not beyond 96 GB (a third of the card; 16 GB until round 5, when
                                                          // the plan bought launches only -- since the leaf loop it halves the terminals' traffic, and full 1 176-combo ranges need 59 GB)
 
@@ -1259,11 +1268,12 @@ struct BrRun {
         return d;
     }
 
-    // ---- the level plan: every node gets buffers of its own (an action node: [A][n_pad] for its children's values, an opponent's node the same for their reach), so the
-    // nodes of one tree depth no longer wait for each other and ONE launch takes all of a depth's nodes of one kind (grid row = node): reach down level by level, every
-    // leaf in one launch, values up level by level -- about sixty launches per traverser instead of one or two per tree node (1 864 nodes: 4 300 launches per call).
-    // The arithmetic of a node is the depth-first walk's (same kernels' bodies), so are its bits.  Costs memory: see level_plan_bytes.
-    int max_depth = 0;
+    // ---- the two tree orders.  The LEVEL PLAN gives every node buffers of its own (an action node: [A][n_pad] for its children's values, an opponent's node the same for
+    // their reach), so the nodes of one tree depth no longer wait for each other and ONE launch takes all of a depth's nodes of one kind (grid row = node): reach down level by
+    // level, every leaf in one launch, values up level by level -- about sixty launches per traverser instead of one or two per tree node (1 864 nodes: 4 300 launches per
+    // call).  Costs memory: see level_plan_bytes.  The DEPTH-FIRST walk shares two buffers per tree depth among the depth's nodes and launches node by node.  Both run the
+    // same jobs through the same kernels (build_plan, launch), so their bits are the same.
+    int max_depth = 0;            // action nodes on the longest path: the levels of child buffers
     std::vector<int> depth_of;    // per tree node: action-node ancestors
     void fill_depths() {
         depth_of.assign(tree->nodes.size(), 0);
@@ -1281,37 +1291,62 @@ struct BrRun {
             if (n.kind == RS_NODE_ACTION && n.n_children > 0) doubles += size_t(n.n_children) * (size_t(me.n_pad) + (int(n.player) != pl ? size_t(op.n_pad) : 0));
         return doubles * sizeof(double);
     }
-    int run_levels(double *ws, double **root_out) {
+
+    // which kernel takes the traverser's own nodes of round r / the opponent's: groups and columns are the level plan's only
+    BrKind own_kind(int r) const {
+        const BrSide &me = side[p];
+        if (real) return kBrOwnReal;   // whatever the abstraction's lists would have asked for
+        if (ws_levels && mode == RS_BR_MAX && me.grouped[r]) return kBrOwnGrouped;
+        if (ws_levels && me.d_tord[r]) return kBrOwnCols;
+        return br_wave_per_info_set(me.n, me.n_clusters[r]) ? kBrOwnWave : kBrOwnThread;
+    }
+    BrKind reach_kind(int r) const { return ws_levels && side[1 - p].grouped[r] ? kBrReachGrouped : kBrReach; }
+
+    // One traverser's pass as jobs in the order of their launches: reach by ascending depth, the leaves, values by descending depth, within a depth by kind (and round, where
+    // the kind is launched per round).  A run of equal `key` is one launch of the level plan.
+    struct BrPlan {
+        struct Entry {
+            uint32_t key;
+            BrKind kind;
+            int round, node;
+        };
+        std::vector<Entry> entries;
+        std::vector<BrJob> jobs;           // jobs[i] is entries[i]'s
+        std::vector<int> job_at, sum_at;   // per tree node: its job (leaf, own node, an opponent node's reach) and an opponent node's sum job, -1 = none
+        double *root = nullptr;            // where the root's values arrive
+    };
+    // host only: gives every node its buffers and fills the jobs
+    int build_plan(BrPlan &pl) {
         const BrSide &me = side[p], &op = side[1 - p];
         const size_t N = tree->nodes.size();
-        if (depth_of.size() != N) fill_depths();
-        std::vector<const double *> q_in(N, nullptr);
-        std::vector<double *> v_out(N, nullptr), vch(N, nullptr), qch(N, nullptr);
         double *at = ws;
-        *root_out = at;
-        at += me.n_pad;
-        v_out[0] = *root_out;
+        auto slot = [&](size_t doubles) {   // level plan: the next stretch of the workspace
+            double *s = at;
+            at += doubles;
+            return s;
+        };
+        pl.root = ws_levels ? slot(me.n_pad) : d_root;
+        std::vector<const double *> q_in(N, nullptr);
+        std::vector<double *> v_out(N, nullptr);
+        std::vector<int> folds(N, -1);   // an own node whose kernel adds up the rows below an opponent's child itself (by groups, real game; level plan): its job
+        v_out[0] = pl.root;
         q_in[0] = op.d_init_q;
-        std::vector<std::vector<BrJob>> down(size_t(max_depth) + 1), up_own(size_t(max_depth) + 1), up_wave(size_t(max_depth) + 1), up_sum(size_t(max_depth) + 1);
-        std::vector<std::pair<int, int>> grp_at(N, {-1, -1});   // an own node taken by groups: (round, index in up_grp[round][depth])
-        std::vector<std::vector<BrJob>> up_cols(size_t(max_depth) + 1);   // own nodes by columns
-        std::vector<std::vector<BrJob>> up_grp[RS_MAX_ROUNDS], down_grp[RS_MAX_ROUNDS];   // own / opponent nodes taken by groups of run-outs, per round (the groups are the round's)
-        std::vector<std::vector<BrJob>> up_real[RS_MAX_ROUNDS];   // own nodes in the real game, per round (the round's run-outs per prefix shape the grid); grp_at serves them too
-        for (auto &v : up_grp) v.resize(size_t(max_depth) + 1);
-        for (auto &v : up_real) v.resize(size_t(max_depth) + 1);
-        for (auto &v : down_grp) v.resize(size_t(max_depth) + 1);
-        std::vector<BrJob> leaves;
+        std::vector<BrPlan::Entry> entries;   // in the tree's order; gathered into pl in launch order below
+        std::vector<BrJob> jobs;
+        auto add = [&](BrKind kind, int r, size_t id, const BrJob &j) {
+            const int d = depth_of[id], step = kind < kBrLeaf ? d : (kind == kBrLeaf ? max_depth + 1 : 2 * max_depth + 2 - d);
+            entries.push_back({(uint32_t(step) * kBrKinds + kind) * RS_MAX_ROUNDS + uint32_t(br_per_round(kind) ? r : 0), kind, r, int(id)});
+            jobs.push_back(j);
+        };
         for (size_t id = 0; id < N; ++id) {   // parents before children: a node's q and v slot are known when it comes up
             const rs_tree_node &n = tree->nodes[id];
             if (n.kind == RS_NODE_TERMINAL) {
-                const int unc = n.ttype == RS_TERM_UNCONTESTED;
-                const double pot = double(float(n.value));   // tn.value as f32 (cfr.rs:316)
                 BrJob j{};
                 j.q = q_in[id];
                 j.v = v_out[id];
-                j.uncontested = unc;
-                j.value = unc ? (p == int(n.last_to_act) ? -pot : pot) : pot;
-                leaves.push_back(j);
+                j.uncontested = n.ttype == RS_TERM_UNCONTESTED;
+                j.value = br_terminal_value(n, p);
+                add(kBrLeaf, 0, id, j);
                 continue;
             }
             if (n.kind != RS_NODE_ACTION) {   // chance nodes pass through (cfr.rs:306-313)
@@ -1323,113 +1358,109 @@ struct BrRun {
             }
             if (n.n_children == 0) return fail(RS_ERR_UNSUPPORTED, "rs_best_response: an action node without actions");
             const int r = n.round_idx, d = depth_of[id];
-            vch[id] = at;
-            at += size_t(n.n_children) * me.n_pad;
             BrJob j{};
             j.row = row_of(t, n.index);
-            j.vch = vch[id];
+            double *vch = ws_levels ? slot(size_t(n.n_children) * me.n_pad) : v_level[size_t(d)];
+            j.vch = vch;
             j.v = v_out[id];
             j.n_children = uint32_t(n.n_children);
             if (int(n.player) == p) {
+                const BrKind kind = own_kind(r);
                 j.start = me.d_start[r];
                 j.order = me.d_order[r];
                 j.n_clusters = me.n_clusters[r];
-                if (real) {   // whatever the abstraction's lists would have asked for
-                    grp_at[id] = {r, int(up_real[r][size_t(d)].size())};
-                    up_real[r][size_t(d)].push_back(j);
-                }
-                else if (mode == RS_BR_MAX && me.grouped[r]) {
-                    grp_at[id] = {r, int(up_grp[r][size_t(d)].size())};
-                    up_grp[r][size_t(d)].push_back(j);
-                }
-                else if (me.d_tord[r]) {
+                if (kind == kBrOwnCols) {
                     j.tord = me.d_tord[r];
                     j.perm = me.d_perm[r];
                     j.n_sets = me.n_sets[r];
                     j.kmax = me.kmax[r];
-                    up_cols[size_t(d)].push_back(j);
                 }
-                else (size_t(me.n) >= size_t(me.n_clusters[r]) * 32 ? up_wave : up_own)[size_t(d)].push_back(j);   // many lanes per info set: a wave each
+                if (ws_levels && (kind == kBrOwnGrouped || kind == kBrOwnReal)) folds[id] = int(jobs.size());
+                add(kind, r, id, j);
                 for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = q_in[id];
             } else {
-                qch[id] = at;
-                at += size_t(n.n_children) * op.n_pad;
+                double *qch = ws_levels ? slot(size_t(n.n_children) * op.n_pad) : q_level[size_t(d)];
                 j.cid = op.d_cid[r];
                 j.q = q_in[id];
-                j.q_out = qch[id];
-                (op.grouped[r] ? down_grp[r] : down)[size_t(d)].push_back(j);
-                // its value is the sum of its children's; where the parent is an own node taken by groups (or in the real game), that kernel adds the rows up as it loads them
+                j.q_out = qch;
+                add(reach_kind(r), r, id, j);
+                // its value is the sum of its children's; where the parent folds, that kernel adds the rows up as it loads them
                 const int par = n.parent;
                 bool taken = false;
-                if (par >= 0 && grp_at[size_t(par)].first >= 0) {
+                if (par >= 0 && folds[size_t(par)] >= 0) {
                     const rs_tree_node &pn = tree->nodes[size_t(par)];
-                    BrJob &pj = (real ? up_real : up_grp)[grp_at[size_t(par)].first][size_t(depth_of[size_t(par)])][size_t(grp_at[size_t(par)].second)];
+                    BrJob &pj = jobs[size_t(folds[size_t(par)])];
                     for (int a = 0; a < pn.n_children && !taken; ++a)
                         if (pn.children[a] == int(id)) {
-                            pj.sum_src[a] = vch[id];
+                            pj.sum_src[a] = vch;
                             pj.sum_n[a] = uint32_t(n.n_children);
                             taken = true;
                         }
                 }
-                if (!taken) up_sum[size_t(d)].push_back(j);
-                for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = qch[id] + size_t(a) * op.n_pad;
+                if (!taken) add(kBrSum, r, id, j);
+                for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = qch + size_t(a) * op.n_pad;
             }
-            for (int a = 0; a < n.n_children; ++a) v_out[size_t(n.children[a])] = vch[id] + size_t(a) * me.n_pad;
+            for (int a = 0; a < n.n_children; ++a) v_out[size_t(n.children[a])] = vch + size_t(a) * me.n_pad;
         }
-        // all jobs in one upload
-        std::vector<BrJob> all;
-        auto put = [&](const std::vector<BrJob> &v) {
-            const size_t at_ = all.size();
-            all.insert(all.end(), v.begin(), v.end());
-            return at_;
+        // into launch order; within a launch the nodes keep the tree's order
+        std::vector<uint32_t> perm(entries.size());
+        for (uint32_t i = 0; i < perm.size(); ++i) perm[i] = i;
+        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return entries[a].key < entries[b].key; });
+        pl.job_at.assign(N, -1);
+        pl.sum_at.assign(N, -1);
+        pl.entries.reserve(perm.size());
+        pl.jobs.reserve(perm.size());
+        for (uint32_t i : perm) {
+            const BrPlan::Entry &e = entries[i];
+            (e.kind == kBrSum ? pl.sum_at : pl.job_at)[size_t(e.node)] = int(pl.jobs.size());
+            pl.entries.push_back(e);
+            pl.jobs.push_back(jobs[i]);
+        }
+        return RS_OK;
+    }
+
+    // The launcher: for every kind the ONE place that knows its grid, block and LDS size, its attributes, the instantiation for the cell type and the leaf form.  d_jobs[0 .. nj)
+    // are the launch's jobs (one grid row each), h the same jobs on the host; r is the round of a kind that is launched per round.  The depth-first walk passes no d_jobs and
+    // one job: the node goes to the kind's one-node entry, its pointers as kernel arguments (what the walk has always done; the _jobs kernels with a one-row grid would
+    // compute the same bits, but whether they are as fast has not been measured: profiles/br_launcher.md).
+    int n_launches = 0;
+    void launch(BrKind kind, int r, const BrJob *d_jobs, uint32_t nj, const BrJob *h) {
+        if (err != hipSuccess) return;
+        const BrSide &me = side[p], &op = side[1 - p];
+        const hipStream_t s = t->stream;
+        const void *ssum = t->d_ssum.get();
+        const dim3 block(kBrBlock);
+        auto most = [&](auto field) {   // the grid is sized by the largest of the launch's jobs
+            uint32_t m = 0;
+            for (uint32_t i = 0; i < nj; ++i) m = std::max<uint32_t>(m, field(h[i]));
+            return m;
         };
-        std::vector<size_t> o_down, o_own, o_wave, o_sum, o_cols, o_grp[RS_MAX_ROUNDS], o_dgrp[RS_MAX_ROUNDS], o_real[RS_MAX_ROUNDS];
-        for (int d = 0; d <= max_depth; ++d) {
-            o_down.push_back(put(down[size_t(d)]));
-            o_cols.push_back(put(up_cols[size_t(d)]));
-            o_own.push_back(put(up_own[size_t(d)]));
-            for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_grp[r].push_back(put(up_grp[r][size_t(d)]));
-            for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_dgrp[r].push_back(put(down_grp[r][size_t(d)]));
-            for (int r = 0; r < RS_MAX_ROUNDS; ++r) o_real[r].push_back(put(up_real[r][size_t(d)]));
-            o_wave.push_back(put(up_wave[size_t(d)]));
-            o_sum.push_back(put(up_sum[size_t(d)]));
+        auto n_clusters = [](const BrJob &j) { return j.n_clusters; };
+        const BrJob &j = h[0];   // the node of a one-node launch
+        switch (kind) {
+        case kBrReachGrouped: {
+            const BrGroups &g = op.groups[r];
+            const size_t lds = size_t(most([](const BrJob &j) { return j.row.n_actions; })) * (size_t(g.max_sets) + 1) * sizeof(float);
+            const auto k = RS_BR_PICK(t->dtype, k_br_opp_reach_grouped_jobs);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+            hipLaunchKernelGGL(k, dim3(8u * ((g.n_groups + 7u) / 8u), nj), dim3(kBrGroupBlock), lds, s, ssum, d_jobs, g, op.n_pad);
+            break;
         }
-        const size_t o_leaves = put(leaves);
-        DevBuf<BrJob> d_jobs;
-        err = d_jobs.alloc(all.size());
-        if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, all.data(), all.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(t->stream);   // `all` is a local
-        n_launches = 0;
-        for (int d = 0; d <= max_depth && err == hipSuccess; ++d) {   // reach, level by level
-            for (int r = 0; r < RS_MAX_ROUNDS && err == hipSuccess; ++r)
-                if (const uint32_t nj = uint32_t(down_grp[r][size_t(d)].size())) {
-                    uint32_t amax = 0;
-                    for (const BrJob &j : down_grp[r][size_t(d)]) amax = std::max(amax, j.row.n_actions);
-                    const size_t lds = size_t(amax) * (size_t(op.groups[r].max_sets) + 1) * sizeof(float);
-#define RS_OPPG(DT_)                                                                                                                                                      \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_br_opp_reach_grouped_jobs<DT_>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));                    \
-    hipLaunchKernelGGL((k_br_opp_reach_grouped_jobs<DT_>), dim3(8u * ((op.groups[r].n_groups + 7u) / 8u), nj), dim3(kBrGroupBlock), lds, t->stream, t->d_ssum, d_jobs + o_dgrp[r][size_t(d)], \
-                       op.groups[r], op.n_pad)
-                    RS_BR_DT(t->dtype, RS_OPPG);
-#undef RS_OPPG
-                    err = hipGetLastError();
-                    ++n_launches;
-                }
-            const uint32_t nj = uint32_t(down[size_t(d)].size());
-            if (!nj) continue;
-            const uint32_t sliced = 8u * grid1(NB * ((op.n_hands + 7u) / 8u));
-#define RS_OPPJ(DT_) hipLaunchKernelGGL((k_br_opp_reach_jobs<DT_>), dim3(sliced, nj), dim3(kBrBlock), 0, t->stream, t->d_ssum, d_jobs + o_down[size_t(d)], op.n, op.n_pad, op.n_hands)
-            RS_BR_DT(t->dtype, RS_OPPJ);
-#undef RS_OPPJ
-            err = hipGetLastError();
-            ++n_launches;
+        case kBrReach: {
+            if (!d_jobs) {
+                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_opp_reach), dim3(grid1(op.n)), block, 0, s, ssum, j.row, j.cid, op.n, op.n_pad, j.q, j.q_out);
+                break;
+            }
+            const auto k = RS_BR_PICK(t->dtype, k_br_opp_reach_jobs);
+            hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((op.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, op.n, op.n_pad, op.n_hands);
+            break;
         }
-        for (size_t lo = 0; lo < leaves.size() && err == hipSuccess; lo += 16384) {   // every leaf
-            const uint32_t nj = uint32_t(std::min<size_t>(16384, leaves.size() - lo));
+        case kBrLeaf: {
             // (small ranges keep a workgroup per (run-out, leaf): the loop's scans are unrolled for 1 326 hands whatever the range holds -- 200 combos: 0.047 against 0.059 s per call)
             const uint32_t most_hands = std::max(me.n_hands, op.n_hands);
-            if (sorted && most_hands <= uint32_t(kBrHandsPerThread) * kBrBlock && op.n_hands <= uint32_t(kBrChunkMax) * 64u) {   // a workgroup per run-out (and slice of the leaves, when run-outs alone do not fill the card)
-                const size_t lds = (size_t(op.n_hands) * 2 + 52 * kBrCardHolders + 65) * sizeof(double) + (((size_t(op.n_hands) + 3) & ~size_t(3)) + 52 * kBrCardHolders) * sizeof(uint16_t) + 64;
+            if (sorted && ws_levels && most_hands <= uint32_t(kBrHandsPerThread) * kBrBlock && op.n_hands <= uint32_t(kBrChunkMax) * 64u) {
+                // the level plan's leaf loop: a workgroup per run-out (and slice of the leaves, when run-outs alone do not fill the card)
+                const size_t lds = br_sorted_leaf_lds(op.n_hands) + (((size_t(op.n_hands) + 3) & ~size_t(3)) + 52 * kBrCardHolders) * sizeof(uint16_t) + 64;
                 // slices of the leaves: enough workgroups to fill the card, and a count that leaves the last round of workgroups (two per CU at full ranges: 220 registers;
                 // four and more for the small-range forms) nearly full -- 2 352 run-outs on 512 slots are 4.6 rounds (the fifth 59 % full), three slices 13.8
                 const int form = most_hands <= 256 ? 0 : (most_hands <= 512 ? 1 : (most_hands <= 1024 ? 2 : 3));
@@ -1446,156 +1477,114 @@ struct BrRun {
                     }
                 }
 #define RS_LEAF_LOOP(HPT_, CHUNK_)                                                                                                                                     \
-    hipLaunchKernelGGL((k_br_terminal_sorted_loop<HPT_, CHUNK_, (HPT_ == kBrHandsPerThread)>), dim3(NB, slices), dim3(kBrBlock), lds, t->stream, me.d_hands, me.d_mask, me.d_pw, me.n_hands, op.n_hands, \
-                       d_bmask, me.index, d_jobs + o_leaves + lo, nj)
+    hipLaunchKernelGGL((k_br_terminal_sorted_loop<HPT_, CHUNK_, (HPT_ == kBrHandsPerThread)>), dim3(NB, slices), block, lds, s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, \
+                       op.n_hands, d_bmask, me.index, d_jobs, nj)
                 if (form == 0) RS_LEAF_LOOP(1, 4);
                 else if (form == 1) RS_LEAF_LOOP(2, 8);
                 else if (form == 2) RS_LEAF_LOOP(4, 16);
                 else RS_LEAF_LOOP(kBrHandsPerThread, kBrChunkMax);
 #undef RS_LEAF_LOOP
-            } else if (sorted) {
-                const size_t lds = (size_t(op.n_hands) * 2 + 52 * kBrCardHolders + 65) * sizeof(double);
-                hipLaunchKernelGGL(k_br_terminal_sorted_jobs, dim3(NB, nj), dim3(kBrBlock), lds, t->stream, me.d_hands, me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask, me.index,
-                                   d_jobs + o_leaves + lo);
+            } else if (sorted) {   // a workgroup per (run-out, leaf)
+                if (!d_jobs)
+                    hipLaunchKernelGGL(k_br_terminal_sorted, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands, d_bmask,
+                                       me.index, j.uncontested, j.value, j.v);
+                else
+                    hipLaunchKernelGGL(k_br_terminal_sorted_jobs, dim3(NB, nj), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask,
+                                       me.index, d_jobs);
             } else {
                 const size_t lds = size_t(op.n_hands) * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
-                hipLaunchKernelGGL(k_br_terminal_boards_jobs, dim3(grid1(me.n_hands), NB, nj), dim3(kBrBlock), lds, t->stream, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask,
-                                   op.d_score, op.n_hands, d_bmask, d_jobs + o_leaves + lo);
+                if (!d_jobs)
+                    hipLaunchKernelGGL(k_br_terminal_boards, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
+                                       op.n_hands, d_bmask, j.uncontested, j.value, j.v);
+                else
+                    hipLaunchKernelGGL(k_br_terminal_boards_jobs, dim3(grid1(me.n_hands), NB, nj), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score,
+                                       op.n_hands, d_bmask, d_jobs);
             }
-            err = hipGetLastError();
-            ++n_launches;
+            break;
         }
-        for (int d = max_depth; d >= 0 && err == hipSuccess; --d) {   // values, deepest level first
-            if (const uint32_t nj = uint32_t(up_wave[size_t(d)].size())) {
-                uint32_t ncl = 0;
-                for (const BrJob &j : up_wave[size_t(d)]) ncl = std::max(ncl, j.n_clusters);
-                const uint32_t blocks = uint32_t(std::min<size_t>((size_t(ncl) * 64 + kBrBlock - 1) / kBrBlock, 8192));
-#define RS_OWNWJ(DT_) hipLaunchKernelGGL((k_br_own_wave_jobs<DT_>), dim3(blocks, nj), dim3(kBrBlock), 0, t->stream, t->d_ssum, d_jobs + o_wave[size_t(d)], me.n_pad, mode)
-                RS_BR_DT(t->dtype, RS_OWNWJ);
-#undef RS_OWNWJ
-                err = hipGetLastError();
-                ++n_launches;
+        case kBrOwnWave: {
+            if (!d_jobs) {
+                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own_wave), dim3(br_wave_blocks(j.n_clusters)), block, 0, s, ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch,
+                                   mode, j.v);
+                break;
             }
-            if (const uint32_t nj = uint32_t(up_cols[size_t(d)].size())) {
-                uint32_t ns = 0;
-                for (const BrJob &j : up_cols[size_t(d)]) ns = std::max(ns, j.n_sets);
-#define RS_OWNC(DT_) hipLaunchKernelGGL((k_br_own_cols_jobs<DT_>), dim3(grid1(ns), nj), dim3(kBrBlock), 0, t->stream, t->d_ssum, d_jobs + o_cols[size_t(d)], me.n_pad, mode)
-                RS_BR_DT(t->dtype, RS_OWNC);
-#undef RS_OWNC
-                err = hipGetLastError();
-                ++n_launches;
-            }
-            for (int r = 0; r < RS_MAX_ROUNDS && err == hipSuccess; ++r)
-                if (const uint32_t nj = uint32_t(up_grp[r][size_t(d)].size())) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_br_own_grouped_jobs), hipFuncAttributeMaxDynamicSharedMemorySize, int(me.group_lds[r]));
-                    hipLaunchKernelGGL(k_br_own_grouped_jobs, dim3(me.groups[r].n_groups, nj), dim3(kBrGroupBlock), me.group_lds[r], t->stream, d_jobs + o_grp[r][size_t(d)],
-                                       me.groups[r], me.n_pad);
-                    err = hipGetLastError();
-                    ++n_launches;
-                }
-            for (int r = 0; r < RS_MAX_ROUNDS && err == hipSuccess; ++r)
-                if (const uint32_t nj = uint32_t(up_real[r][size_t(d)].size())) {
-                    launch_real(r, nj, d_jobs + o_real[r][size_t(d)], 0, nullptr, nullptr);
-                    err = hipGetLastError();
-                    ++n_launches;
-                }
-            if (const uint32_t nj = uint32_t(up_own[size_t(d)].size())) {
-                uint32_t ncl = 0;
-                for (const BrJob &j : up_own[size_t(d)]) ncl = std::max(ncl, j.n_clusters);
-#define RS_OWNJ(DT_) hipLaunchKernelGGL((k_br_own_jobs<DT_>), dim3(grid1(ncl), nj), dim3(kBrBlock), 0, t->stream, t->d_ssum, d_jobs + o_own[size_t(d)], me.n_pad, mode)
-                RS_BR_DT(t->dtype, RS_OWNJ);
-#undef RS_OWNJ
-                if (err == hipSuccess) err = hipGetLastError();
-                ++n_launches;
-            }
-            if (const uint32_t nj = uint32_t(up_sum[size_t(d)].size())) {
-                hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), dim3(kBrBlock), 0, t->stream, d_jobs + o_sum[size_t(d)], me.n, me.n_pad);
-                if (err == hipSuccess) err = hipGetLastError();
-                ++n_launches;
-            }
+            const auto k = RS_BR_PICK(t->dtype, k_br_own_wave_jobs);
+            hipLaunchKernelGGL(k, dim3(br_wave_blocks(most(n_clusters)), nj), block, 0, s, ssum, d_jobs, me.n_pad, mode);
+            break;
         }
-        if (err == hipSuccess) err = hipStreamSynchronize(t->stream);   // d_jobs is freed on return
-        return err == hipSuccess ? RS_OK : hip_fail(err, "rs_best_response (level plan)");
-    }
-    int n_launches = 0;
-
-    // the traverser's own nodes of round r in the real game: the node (vch -> v) of the depth-first walk, or nj jobs of the level plan
-    void launch_real(int r, uint32_t nj, const BrJob *jobs, uint32_t n_actions, const double *vch, double *v) {
-        const BrSide &me = side[p];
-        const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
-        if (pp == 1) {
-            if (jobs) hipLaunchKernelGGL(k_br_own_real_last_jobs, dim3(grid1(me.n), nj), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, jobs);
-            else hipLaunchKernelGGL(k_br_own_real_last, dim3(grid1(me.n)), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, n_actions, vch, v);
+        case kBrOwnCols: {
+            const auto k = RS_BR_PICK(t->dtype, k_br_own_cols_jobs);
+            hipLaunchKernelGGL(k, dim3(grid1(most([](const BrJob &j) { return j.n_sets; })), nj), block, 0, s, ssum, d_jobs, me.n_pad, mode);
+            break;
+        }
+        case kBrOwnGrouped:
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_br_own_grouped_jobs), hipFuncAttributeMaxDynamicSharedMemorySize, int(me.group_lds[r]));
+            hipLaunchKernelGGL(k_br_own_grouped_jobs, dim3(me.groups[r].n_groups, nj), dim3(kBrGroupBlock), me.group_lds[r], s, d_jobs, me.groups[r], me.n_pad);
+            break;
+        case kBrOwnReal: {
+            const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
+            const dim3 cols_grid((n_pairs + kBrRealPairs - 1) / kBrRealPairs, nj);
+            if (pp == 1 && !d_jobs) hipLaunchKernelGGL(k_br_own_real_last, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v);
+            else if (pp == 1) hipLaunchKernelGGL(k_br_own_real_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
+            else if (!d_jobs) hipLaunchKernelGGL(k_br_own_real_cols, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, j.n_children, j.vch, j.v);
+            else hipLaunchKernelGGL(k_br_own_real_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
+            break;
+        }
+        case kBrOwnThread: {
+            if (!d_jobs) {
+                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own), dim3(grid1(j.n_clusters)), block, 0, s, ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch, mode, j.v);
+                break;
+            }
+            const auto k = RS_BR_PICK(t->dtype, k_br_own_jobs);
+            hipLaunchKernelGGL(k, dim3(grid1(most(n_clusters)), nj), block, 0, s, ssum, d_jobs, me.n_pad, mode);
+            break;
+        }
+        case kBrSum:
+            if (!d_jobs) hipLaunchKernelGGL(k_br_sum, dim3(grid1(me.n)), block, 0, s, j.vch, j.n_children, me.n, me.n_pad, j.v);
+            else hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), block, 0, s, d_jobs, me.n, me.n_pad);
+            break;
+        case kBrKinds:   // a count, no kind
             return;
-        }
-        const uint32_t blocks = (n_pairs + kBrRealPairs - 1) / kBrRealPairs;
-        if (jobs) hipLaunchKernelGGL(k_br_own_real_cols_jobs, dim3(blocks, nj), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, jobs);
-        else hipLaunchKernelGGL(k_br_own_real_cols, dim3(blocks), dim3(kBrBlock), 0, t->stream, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, n_actions, vch, v);
-    }
-
-    void walk(int id, const double *q, double *v_out, int level) {
-        if (err != hipSuccess) return;
-        const rs_tree_node &n = tree->nodes[size_t(id)];
-        const BrSide &me = side[p], &op = side[1 - p];
-        if (n.kind == RS_NODE_TERMINAL) {
-            const int unc = n.ttype == RS_TERM_UNCONTESTED;
-            const double pot = double(float(n.value));   // tn.value as f32 (cfr.rs:316)
-            const double value = unc ? (p == int(n.last_to_act) ? -pot : pot) : pot;
-            if (sorted) {
-                const size_t lds = (size_t(op.n_hands) * 2 + 52 * kBrCardHolders + 65) * sizeof(double);
-                hipLaunchKernelGGL(k_br_terminal_sorted, dim3(NB), dim3(kBrBlock), lds, t->stream, me.d_hands, me.d_mask, me.d_pw, me.n_hands, q, op.n_hands, d_bmask, me.index,
-                                   unc, value, v_out);
-                err = hipGetLastError();
-                return;
-            }
-            const size_t lds = size_t(op.n_hands) * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
-            hipLaunchKernelGGL(k_br_terminal_boards, dim3(grid1(me.n_hands), NB), dim3(kBrBlock), lds, t->stream, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask,
-                               op.d_score, q, op.n_hands, d_bmask, unc, value, v_out);
-            err = hipGetLastError();
-            return;
-        }
-        if (n.kind != RS_NODE_ACTION) return walk(n.children[0], q, v_out, level);   // chance nodes pass through (cfr.rs:306-313)
-        const BrNodeRow row = row_of(t, n.index);
-        const int r = n.round_idx;
-        double *vch = v_level[size_t(level)];
-        if (int(n.player) == p) {
-            for (int a = 0; a < n.n_children; ++a) walk(n.children[a], q, vch + size_t(a) * me.n_pad, level + 1);
-            if (err != hipSuccess) return;
-            if (real) launch_real(r, 0, nullptr, uint32_t(n.n_children), vch, v_out);
-            else if (size_t(me.n) >= size_t(me.n_clusters[r]) * 32) {   // many lanes per info set: a wave each
-                const uint32_t blocks = uint32_t(std::min<size_t>((size_t(me.n_clusters[r]) * 64 + kBrBlock - 1) / kBrBlock, 8192));
-#define RS_OWNW(DT_)                                                                                                                                    \
-    hipLaunchKernelGGL((k_br_own_wave<DT_>), dim3(blocks), dim3(kBrBlock), 0, t->stream, t->d_ssum, row, me.d_start[r], me.d_order[r], me.n_clusters[r], \
-                       me.n_pad, vch, mode, v_out)
-                RS_BR_DT(t->dtype, RS_OWNW);
-#undef RS_OWNW
-            } else {
-#define RS_OWN(DT_)                                                                                                                                            \
-    hipLaunchKernelGGL((k_br_own<DT_>), dim3(grid1(me.n_clusters[r])), dim3(kBrBlock), 0, t->stream, t->d_ssum, row, me.d_start[r], me.d_order[r], me.n_clusters[r], \
-                       me.n_pad, vch, mode, v_out)
-                RS_BR_DT(t->dtype, RS_OWN);
-#undef RS_OWN
-            }
-        } else {
-            double *qch = q_level[size_t(level)];
-#define RS_OPP(DT_) hipLaunchKernelGGL((k_br_opp_reach<DT_>), dim3(grid1(op.n)), dim3(kBrBlock), 0, t->stream, t->d_ssum, row, op.d_cid[r], op.n, op.n_pad, q, qch)
-            RS_BR_DT(t->dtype, RS_OPP);
-#undef RS_OPP
-            err = hipGetLastError();
-            for (int a = 0; a < n.n_children; ++a) walk(n.children[a], qch + size_t(a) * op.n_pad, vch + size_t(a) * me.n_pad, level + 1);
-            if (err != hipSuccess) return;
-            hipLaunchKernelGGL(k_br_sum, dim3(grid1(me.n)), dim3(kBrBlock), 0, t->stream, vch, uint32_t(n.n_children), me.n, me.n_pad, v_out);
         }
         err = hipGetLastError();
+        ++n_launches;
+    }
+
+    // depth first: a node's launches around its children's, one node each and straight from the host's jobs
+    void walk(const BrPlan &pl, int id) {
+        if (err != hipSuccess) return;
+        const rs_tree_node &n = tree->nodes[size_t(id)];
+        if (n.kind != RS_NODE_TERMINAL && n.kind != RS_NODE_ACTION) return walk(pl, n.children[0]);   // chance nodes pass through (cfr.rs:306-313)
+        auto one = [&](int at) { launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, nullptr, 1, &pl.jobs[size_t(at)]); };
+        const bool own = n.kind == RS_NODE_ACTION && int(n.player) == p;
+        if (!own) one(pl.job_at[size_t(id)]);   // a leaf, or the reach of an opponent node's children
+        if (n.kind == RS_NODE_TERMINAL) return;
+        for (int a = 0; a < n.n_children; ++a) walk(pl, n.children[a]);
+        one(own ? pl.job_at[size_t(id)] : pl.sum_at[size_t(id)]);
+    }
+
+    // one traverser's pass: the plan, the launches in the tree order the workspace was made for (the level plan after one upload of its jobs), the root's values back
+    int run_traverser(double *root_host) {
+        BrPlan pl;
+        if (int rc = build_plan(pl)) return rc;
+        DevBuf<BrJob> d_jobs;
+        n_launches = 0;
+        if (!ws_levels) walk(pl, 0);
+        else {   // reach downwards by depth, the leaves in slices of 16 384, values upwards by depth: the plan's order
+            err = d_jobs.alloc(pl.jobs.size());
+            if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, pl.jobs.data(), pl.jobs.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
+            for (size_t lo = 0, hi; lo < pl.jobs.size() && err == hipSuccess; lo = hi) {
+                const size_t most = pl.entries[lo].kind == kBrLeaf ? 16384 : pl.jobs.size();
+                for (hi = lo + 1; hi < pl.jobs.size() && hi - lo < most && pl.entries[hi].key == pl.entries[lo].key; ++hi) {}
+                launch(pl.entries[lo].kind, pl.entries[lo].round, d_jobs + lo, uint32_t(hi - lo), &pl.jobs[lo]);
+            }
+        }
+        if (err == hipSuccess) err = hipMemcpyAsync(root_host, pl.root, side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
+        const hipError_t done = hipStreamSynchronize(t->stream);   // the plan and d_jobs are freed on return: after an error too, nothing queued may still touch them
+        if (err == hipSuccess) err = done;
+        return err == hipSuccess ? RS_OK : hip_fail(err, ws_levels ? "rs_best_response (level plan)" : "rs_best_response");
     }
 };
-
-static int tree_depth(const std::vector<rs_tree_node> &nodes, int id) {
-    const rs_tree_node &n = nodes[size_t(id)];
-    int d = 0;
-    for (int a = 0; a < n.n_children; ++a) d = std::max(d, tree_depth(nodes, n.children[a]));
-    return d + (n.kind == RS_NODE_ACTION ? 1 : 0);   // only action nodes take a level of child buffers
-}
 
 // run-outs of an initial board in the enumeration order of the lanes: the first new card most significant, cards ascending among those still in the deck
 static size_t enumerate_runouts(const uint8_t *board0, int n_board0, std::vector<uint8_t> *out) {
@@ -1990,7 +1979,7 @@ int br_execute(BrRun *prepared, int mode, double *out) {
         } else {
             int max_a = 1;
             for (const rs_tree_node &n : run.tree->nodes) max_a = std::max(max_a, n.n_children);
-            const int depth = tree_depth(run.tree->nodes, 0);
+            const int depth = run.max_depth;   // only action nodes take a level of child buffers
             const size_t per = size_t(max_a) * run.n_pad_max;
             if (run.ws.alloc(size_t(2) * size_t(depth) * per + run.n_pad_max, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
             run.ws_levels = false;
@@ -2001,27 +1990,17 @@ int br_execute(BrRun *prepared, int mode, double *out) {
             run.d_root = run.ws + size_t(2) * size_t(depth) * per;
         }
     }
-    const bool levels = run.ws_levels;
-    double *ws = run.ws;
-    int rc = RS_OK;
-    run.last_level_plan = levels;
+    run.last_level_plan = run.ws_levels;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
-    for (int p = 0; p < 2 && run.err == hipSuccess && rc == RS_OK; ++p) {
+    for (int p = 0; p < 2; ++p) {
         run.p = p;
-        double *d_root = run.d_root;
-        if (levels) rc = run.run_levels(ws, &d_root);
-        else run.walk(0, run.side[1 - p].d_init_q, d_root, 0);
-        run.last_launches += levels ? run.n_launches : 0;
-        if (rc == RS_OK && run.err == hipSuccess) run.err = hipMemcpyAsync(root.data(), d_root, run.side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
-        if (rc == RS_OK && run.err == hipSuccess) run.err = hipStreamSynchronize(t->stream);
+        if (int rc = run.run_traverser(root.data())) return rc;
+        run.last_launches += run.ws_levels ? run.n_launches : 0;
         double total = 0.0;
         for (uint32_t l = 0; l < run.side[p].n; ++l) total += root[l];   // ascending, like the oracle
         out[p] = total;
     }
-    if (rc != RS_OK || run.err != hipSuccess) (void)hipStreamSynchronize(t->stream);   // on error drain the stream before the caller frees what queued kernels may still touch
-    if (rc != RS_OK) return rc;
-    if (run.err != hipSuccess) return hip_fail(run.err, "rs_best_response");
     return RS_OK;
 }
 

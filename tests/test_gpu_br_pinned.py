@@ -7,7 +7,7 @@
     (info sets of 1, 8, 9, 64, 65 lanes side by side; lanes at 32 x clusters - 1, at it and one above; empty clusters; one cluster holding every lane; one-hand ranges).
   * numeric edges of the strategy sums through final_sigma: i32 at 2^31-1, around 2^24 and negative; f32 sums that overflow, +inf, NaN, -0.0, subnormals; binary16 at
     65 504, +inf, subnormals.  NaN results are compared by NaN-ness, everything else by bits.
-Which kernel forms a case launches depends on its sizes AND its cluster layout (rs_br.hip br_prepare / run_levels); the trainer cases assert br_launches(), and NOTES.md records the
+Which kernel forms a case launches depends on its sizes AND its cluster layout (rs_br.hip br_prepare / BrRun::own_kind); the trainer cases assert br_launches(), and NOTES.md records the
 kernels that one traced run of every case of the second group launched."""
 import os
 
@@ -101,12 +101,15 @@ def load_oracle(tr, otab, tree):
     return sums
 
 
-def trainer_against_oracle(tr, tree, ot, sizes, dtype, board0, ranges, cids, nodes, modes=MODES, with_np_br=True):
+def trainer_against_oracle(tr, tree, ot, sizes, dtype, board0, ranges, cids, nodes, modes=MODES, with_np_br=True, launches=None):
     otab = orc.OracleDealTable(ot, sizes, dtype=ODT[dtype])
     sums = load_oracle(tr, otab, tree)
     got = {}
     for mode in modes:
         got[mode] = tr.best_response(mode)
+        if launches is not None:                                     # the level plan's launches of this call: both traversers
+            n = tr.br_launches(bool(mode & L.BR_SORTED))
+            assert n == launches[mode], (mode, n, launches[mode])
         same(got[mode], otab.best_response_rounds(board0, ranges[0], ranges[1], cids, mode), ("trainer against the oracle", mode))
     if with_np_br:
         sig = {i: nbr.final_strategy(S) for i, S in sums.items()}
@@ -125,6 +128,15 @@ TRAINER_CASES = {
     "turn_lossless_i32_depth_first": ("4d5dAs3c", 33, 40, (), "i32", True),
     "flop_bucketed_f16": ("7h8hQc", 12, 15, (0, 1), "f16", False),
     "flop_lossless_i32": ("7h8hQc", 14, 11, (), "i32", False),
+}
+
+# br_launches() after each mode's call in the level-plan cases: the launches of both traversers.  Which nodes share a launch is host logic alone (tree depth, kind, round, the
+# 16 384-leaf slices), so the counts are exact.  Recorded on the GPU at commit afa54d2, before the level plan and the depth-first walk shared one job table and one launcher.
+TRAINER_LAUNCHES = {
+    "flop_bucketed_f16": dict(zip(MODES, (43, 48, 43, 48))),
+    "flop_lossless_i32": dict(zip(MODES, (44, 49, 44, 49))),
+    "river_lossless_i32": dict(zip(MODES, (9, 11, 9, 11))),
+    "turn_bucketed_f32": dict(zip(MODES, (24, 28, 24, 28))),
 }
 
 
@@ -161,7 +173,7 @@ def test_trainer_best_response_equals_oracle_and_np_br(name):
                 got = trainer_against_oracle(tr, tree, ot, sizes, dtype, board0, ranges, cids, nodes)
                 assert tr.br_launches() == -1
         else:
-            got = trainer_against_oracle(tr, tree, ot, sizes, dtype, board0, ranges, cids, nodes)
+            got = trainer_against_oracle(tr, tree, ot, sizes, dtype, board0, ranges, cids, nodes, launches=TRAINER_LAUNCHES[name])
             assert tr.br_launches() > 0                              # the level plan ran
         return got
 
@@ -337,7 +349,7 @@ def test_thread_per_info_set_in_max_mode_under_the_level_plan_with_8_and_9_lanes
     """k_br_own_jobs and its 8-lane fast path in BR_MAX mode under the LEVEL plan -- the route every bucketed abstraction takes in exploitability().  300 hands a side
     from the turn; the river info sets are runs of 8 and 9 lanes cut from a random order of all dealt lanes, so every one spans distant run-outs and all 48 run-outs form ONE
     component (asserted): more than the 11 264 // 300 = 37 run-outs a group may hold, so build_groups gives up for both players; the lanes (14 400) are fewer than 32 x info
-    sets (asserted), so neither the columns nor the wave form is asked and rs_br.hip's run_levels takes the thread per info set in both modes.  (Where a round IS taken by
+    sets (asserted), so neither the columns nor the wave form is asked and rs_br.hip's own_kind takes the thread per info set in both modes.  (Where a round IS taken by
     groups, only BR_MAX goes by groups; BR_AVERAGE falls through to the same thread-per-info-set kernel.)"""
     rng = np.random.Generator(np.random.PCG64(89))
     h = pick_ranges(rng, TURN, 300, 300)

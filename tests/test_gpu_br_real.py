@@ -152,6 +152,11 @@ def test_average_with_real_is_refused():
         assert e.value.code == L.ERR_INVALID and "RS_BR_REAL" in str(e.value)
 
 
+# br_launches() of test_through_the_trainer's level plan after the abstract and after the real-game call, by showdown mode: host logic alone decides them, so they are
+# exact.  Recorded on the GPU at commit afa54d2, before the level plan and the depth-first walk shared one job table and one launcher.
+TRAINER_LAUNCHES = {0: (24, 23), L.BR_SORTED: (24, 23)}
+
+
 def test_through_the_trainer():
     """a bucketed turn-start trainer (turn_bucketed_f32 of the pinned tests): the trainer's real-game call equals the table-level call with ids computed in Python,
     exploitability(real=True) is half its sum, the kept objects and their workspace serve both kinds of call (br_bytes does not move), the value follows the table"""
@@ -170,10 +175,11 @@ def test_through_the_trainer():
     first = {}
     for extra in (0, L.BR_SORTED):
         absv = tr.best_response(L.BR_MAX | extra)
+        assert tr.br_launches(bool(extra)) == TRAINER_LAUNCHES[extra][0]
         held = tr.br_bytes()
         first[extra] = tr.best_response(REAL | extra)
         assert tr.br_bytes() == held                                       # the workspace is shared
-        assert tr.br_launches(bool(extra)) > 0
+        assert tr.br_launches(bool(extra)) == TRAINER_LAUNCHES[extra][1]
         same(first[extra], tr.infosets.best_response_rounds(tree, board0, ranges[0], ranges[1], cids, REAL | extra), ("trainer against the table-level call", extra))
         never_below(first[extra], absv)
         assert tr.exploitability(sorted_showdowns=bool(extra), real=True) == first[extra].sum() / 2.0
