@@ -445,8 +445,8 @@ size_t rs_solver_workspace_bytes(const rs_solver *solver);
 int rs_jit_available(void);   /* 1 if libhiprtc.so can be loaded (needed for fuse_subtrees) */
 int rs_solver_n_launches(const rs_solver *solver, int traverser);
 /* which kernel forms the solver chose (rs_kernel_forms): bit 0 = deal sweeps walk the batch in last-round-cluster order (deal_order), bit 1 = some round subtree
-   stores delta rows (delta_rows), bit 2 = both traversers' lane sweeps run as one pair launch (pair_sweeps; rs_solver_n_launches then counts them under traverser 0);
-   negative = bad solver */
+   stores delta rows (delta_rows), bit 2 = both traversers' lane sweeps run as one pair launch (pair_sweeps; rs_solver_n_launches then counts them under traverser 0),
+   bit 3 = that pair kernel is the split form (two threads of a workgroup share a lane's subtree, cut below its root); negative = bad solver */
 int rs_solver_forms(const rs_solver *solver);
 
 /* ---- card-abstraction plumbing in front of get-infoset (host only; card_abstraction.rs) -----------------------------

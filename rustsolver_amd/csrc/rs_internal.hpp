@@ -308,6 +308,7 @@ struct Knobs {
     int rows = kUnset;              // RS_JIT_ROWS / delta_rows: 1 on / 0 off (delta rows by list position + one summing pass per round)
     int direct_rows = kUnset;       // RS_JIT_DIRECT_ROWS / direct_rows: 1 on / 0 off
     int waves = kUnset;             // RS_JIT_WAVES: pair kernels, waves per SIMD the register allocation is held to
+    int split = kUnset;             // RS_JIT_SPLIT: 0 = pair kernels keep one thread per lane vector for the whole subtree (default: split where the partition rule allows)
     int pair = kUnset;              // pair_sweeps: 1 on / 0 off (lane solvers with one chance-free subtree kernel per traverser walk both traversers in one launch)
     // test-only: forms the engine picks by size, forced onto small inputs
     int rows_chunk = kUnset;        // RS_JIT_ROWS_CHUNK: list entries one workgroup of the summing pass takes (small values: several chunks per row)
@@ -374,6 +375,8 @@ struct JitSubtree {
     size_t off_fan = 0, off_inv = 0, off_cvec = 0;                                        // lane sweeps: deals below the ENUM chance node the kernel walks itself
     std::vector<int> boundary_roots;   // tree id of every next-round root below this subtree, in the order of butil[] / breach[]
     bool pair = false;                 // a pair kernel (JitPair) whose two walks index nodes, leaves and constants alike: entry(jobs[2], flags, out0, out1)
+    bool split = false;                // ... in split form (rs_jit.cpp): half of the workgroup's threads walk part A, the others part B, threads / 2 lane vectors per trip
+    int split_cells[2] = {0, 0}, split_nodes[2] = {0, 0};   // carried regret cells and action nodes of part A and part B
     size_t off_dcfr = 0;               // discounted variant (JitPair::dcfr): JArgs.dc[2], two DcfrSide behind everything the plain kernel's descriptor holds
 };
 // staged rows (rs_device.hpp stage_rows): the shadow rows of a round subtree as the generated kernel needs to know them -- structure only, no addresses
@@ -385,6 +388,7 @@ struct JitStage {
 // pair kernels (lane sweeps of a chance-free subtree): what traverser 1's walk is generated from.  The kernel's JArgs are TWO blobs of the single kernels' layout,
 // traverser 0's then traverser 1's; `ok` says whether both walks index nodes, leaves and constants alike (else there is no pair kernel)
 constexpr int kPairWaves = 1;   // ... and the waves per SIMD their registers are held to (RS_JIT_WAVES overrides; 1 = the compiler's choice)
+constexpr int kSplitWaves = 2;  // ... of the split form: each thread carries one part's regrets
 constexpr int kPairLanes = 2;   // lanes per thread of the pair kernels (RS_JIT_LANES overrides): NOTES.md, pair sweeps
 struct JitPair {
     const std::vector<char> *has_own = nullptr;

@@ -271,6 +271,7 @@ struct rs_solver : rs::SolverDevice {
     // traverser-0 plan first (solver_settle_held: table_settle, rs_sync, rs_stream, destroy, another solver's sweep on the table).
     struct Pair {
         bool on = false;
+        bool split = false;             // the kernel is the split form (rs_jit.cpp): threads / 2 lane vectors per workgroup trip
         rs::JitLaunch jit;              // two argument blobs: traverser 0's plan's, traverser 1's (the seed pointer of the first moved to d_seed_state[3])
         double bytes = 0.0;             // algorithmic bytes without the root utilities; + 4 per lane for each one written
         size_t lanes = 0;

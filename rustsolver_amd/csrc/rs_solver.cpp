@@ -246,7 +246,8 @@ int issue_pair(rs_solver *s, float *u0, float *u1) {
     rs_solver::Pair &P = s->pair;
     if (s->params.opp_mode == RS_OPP_SAMPLE) RS_HIP(launch_next_seed_pair(s->d_seed_state, t->stream), "k_next_seed_pair");
     prof_begin(t, RS_K_TREE, P.bytes + 4.0 * double(P.lanes) * ((u0 ? 1.0 : 0.0) + (u1 ? 1.0 : 0.0)));
-    size_t blocks = std::min<size_t>(std::max<size_t>((size_t(P.jit.max_n_vec) + P.jit.threads - 1) / P.jit.threads, 1), 256 * 16);
+    const size_t per_trip = P.split ? P.jit.threads / 2 : P.jit.threads;   // split form: two threads per lane vector
+    size_t blocks = std::min<size_t>(std::max<size_t>((size_t(P.jit.max_n_vec) + per_trip - 1) / per_trip, 1), 256 * 16);
     if (s->knobs.max_blocks != kUnset) blocks = std::max<size_t>(1, std::min<size_t>(blocks, size_t(std::max(1, s->knobs.max_blocks))));
     const void *d_blob = P.jit.d_blob;
     int flags = s->params.mode & ~RS_UPD_ARITH_MASK;
@@ -980,6 +981,7 @@ static void setup_pair(rs_solver *s) {
     P.jit.src_off[2] = js.src_body;
     P.jit.stride = js.args_size;
     P.jit.threads = js.threads;
+    P.split = js.split;   // its exchange area is static LDS of the kernel (3 floats per lane and root child of part A): nothing to size at the launch
     P.jit.n_jobs = 2;
     P.jit.max_n_vec = J0.max_n_vec * uint32_t(4 / js.lanes);   // the single kernels' vectors are 4 lanes wide
     P.jit.blob = J0.blob;
@@ -1670,7 +1672,7 @@ int rs_solver_exchange_bytes(const rs_solver *s, uint64_t *bytes, uint64_t *swee
     *sweeps = s->dp_sweeps;
     return RS_OK;
 }
-int rs_solver_forms(const rs_solver *s) { return s ? ((s->ordered ? 1 : 0) | (s->rows ? 2 : 0) | (s->pair.on ? 4 : 0)) : RS_ERR_INVALID; }
+int rs_solver_forms(const rs_solver *s) { return s ? ((s->ordered ? 1 : 0) | (s->rows ? 2 : 0) | (s->pair.on ? 4 : 0) | (s->pair.on && s->pair.split ? 8 : 0)) : RS_ERR_INVALID; }
 int rs_solver_walk_counts(rs_solver *s, int traverser, uint64_t *out) {
     if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!s || !s->table || !out || traverser < 0 || traverser > 1) return fail(RS_ERR_INVALID, "rs_solver_walk_counts: bad argument");

@@ -599,6 +599,11 @@ class MCCFRTrainer:
         return bool(L.load().rs_solver_forms(self._h) & 4)
 
     @property
+    def split_pair(self):
+        """the pair launch is the split form: two threads of a workgroup share a lane's subtree, cut below its root (rs_solver_forms bit 3)"""
+        return bool(L.load().rs_solver_forms(self._h) & 8)
+
+    @property
     def delta_rows(self):
         """deal sweeps store their deltas by list position and sum them in one pass per sweep (rs_kernel_forms.delta_rows)"""
         return bool(L.load().rs_solver_forms(self._h) & 2)
