@@ -47,7 +47,8 @@ extern "C" {
                                  rs_solver_exchange_bytes (diagnostics), data-parallel sweeps keep direct rows;
                                  still 6: Discounted CFR (rs_dcfr_params, rs_dcfr_params_default, rs_dcfr_factors, rs_discount_dcfr, rs_train_dcfr, rs_solver_dcfr_fused,
                                  rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning;
-                                 still 6: RS_BR_REAL (a mode bit of rs_best_response, rs_best_response_rounds, rs_deal_trainer_best_response) -- modes without it mean what they meant */
+                                 still 6: RS_BR_REAL (a mode bit of rs_best_response, rs_best_response_rounds, rs_deal_trainer_best_response) -- modes without it mean what they meant;
+                                 still 6: full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT, a mode bit of the same three -- additions only */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -229,6 +230,9 @@ enum { RS_BR_REAL = 0x200 };     /* OR into RS_BR_MAX (optionally with RS_BR_SOR
                                     the same per-deal units: (out[0] + out[1]) / 2 is the exploitability of the average profile in the real game -- never below the abstract
                                     number, equal to it where every (prefix, hand) pair is a cluster of its own, and the one to compare abstractions by.  RS_BR_AVERAGE | RS_BR_REAL: RS_ERR_INVALID
                                     (the average strategy lives in the abstraction) */
+enum { RS_BR_CURRENT = 0x400 };  /* OR into any of the modes above: where the walk reads a strategy it reads the CURRENT one, Infoset::get_strategy of the regrets
+                                    (infoset.rs:83-102), instead of get_final_strategy of the strategy sums -- the opponent always, the traverser too under RS_BR_AVERAGE.  The
+                                    exploitability and the value of the last iterate: what RM+ and Discounted CFR users look at.  Every table type; RS_BR_MAX | RS_BR_REAL | RS_BR_CURRENT allowed */
 int rs_best_response(rs_table *table, const rs_tree *tree, const uint8_t *board, const uint8_t *hands_p0, size_t n_hands_p0, const uint32_t *cluster_p0,
                      const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *cluster_p1, int mode, double *out /*[2]*/);
 /* The same over MULTI-ROUND trees (flop or turn start).  A lane is (run-out b, hand h): generate_hand (cfr.rs:100-143) completes the board to five cards first --
@@ -279,6 +283,38 @@ typedef struct rs_dcfr_params {
 int rs_dcfr_params_default(rs_dcfr_params *out);   /* 1.5, 0, 2, interval 1, cap UINT64_MAX, t0 0, fused RS_FORM_DEFAULT */
 int rs_dcfr_factors(double alpha, double beta, double gamma, uint64_t p, float out[3]);   /* pos, neg, sum */
 int rs_discount_dcfr(rs_table *table, float d_pos, float d_neg, float d_sum);
+
+/* ---- full-width CFR over hand ranges (an extension) ----------------------------------------------
+ * Chance-enumerated, vector-form CFR of the game rs_best_response_rounds measures -- same arguments, same lanes (run-out, hand), same deal weights, leaves and cluster
+ * tables -- on that walk: the opponent plays get_strategy of its regrets, the traverser's own reach goes down beside the opponent's, and at the traverser's nodes every
+ * info set c with a dealt lane takes, over its lanes in ascending order from 0.0 (f64),
+ *   S[a] = sum of the children's values,  P = sum of the own reach,  U = sum_a sigma[a] * S[a],
+ *   regret[a][c] = (float)(regret[a][c] + (S[a] - U))     (RS_UPD_RMPLUS: a result that is not > 0 becomes 0)
+ *   strategy_sum[a][c] = (float)(strategy_sum[a][c] + P * sigma[a]),
+ * sigma = get_strategy of the row before the write; info sets without a dealt lane and the opponent's rows keep their cells.  An iteration is traverser 0's sweep, then
+ * traverser 1's (which sees player 0's new regrets).  Every sum has one order: the tables are a function of the inputs alone, whichever kernel form or tree order ran.
+ * RS_F32 tables only (RS_ERR_UNSUPPORTED otherwise: per-deal probabilities times pots have no integer scale).  The object keeps the prepared game and, from the first
+ * sweep on, the walk's workspace; the table and the tree must outlive it.  A sweep writes the table: a training loop's working copy is settled first and kept shadow
+ * records are rebuilt before the next sampled sweep, as after rs_table_upload.
+ * rs_range_cfr_iterate: one traverser's sweep; *value = the traverser's value per deal under the current profile; synchronises.
+ * rs_range_cfr_train: `iterations` iterations; with dcfr, a tick after iteration t (counted from dcfr->t0) when t % interval == 0 and t <= cap:
+ *   rs_discount_dcfr(rs_dcfr_factors(alpha, beta, gamma, t / interval)) -- bit-identical to the same sweeps and ticks issued one by one; `fused` is not read.
+ * rs_range_cfr_bytes: device bytes held (the game-only half + the workspace).  rs_range_cfr_launches: kernel launches of the last sweep under the level plan, -1 after a
+ * depth-first one (or before any). */
+typedef struct rs_range_cfr rs_range_cfr;
+typedef struct rs_range_cfr_params {
+    int32_t mode;        /* 0 or RS_UPD_RMPLUS */
+    int32_t sorted;      /* RS_FORM_*: rank-order showdown leaves (default on) or the pair loop */
+    int32_t reserved[2];
+} rs_range_cfr_params;
+int rs_range_cfr_create(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                        const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds,
+                        const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
+void rs_range_cfr_destroy(rs_range_cfr *s);
+int rs_range_cfr_iterate(rs_range_cfr *s, int traverser, double *value /* may be NULL */);
+int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_params *dcfr /* NULL = no ticks */, double *values /* [2], last iteration's, may be NULL */);
+size_t rs_range_cfr_bytes(const rs_range_cfr *s);
+int rs_range_cfr_launches(const rs_range_cfr *s);
 
 /* ---- iterate: MCCFRTrainer (cfr.rs) ------------------------------------------------------------
  * Lane model: lane (board b, cluster c) is one scalar cfr() traversal (cfr.rs:481-627)
@@ -587,6 +623,11 @@ int rs_deal_trainer_set_dcfr(rs_deal_trainer *trainer, const rs_dcfr_params *par
 int rs_deal_trainer_last_br(const rs_deal_trainer *trainer, float *out /*[2]*/, uint64_t *iterations);
 int rs_deal_trainer_calc_br(rs_deal_trainer *trainer, float *out /*[2]*/);
 int rs_deal_trainer_best_response(rs_deal_trainer *trainer, int mode, double *out /*[2]*/);
+/* rs_range_cfr_train on the trainer's own tree, ranges, board and cached cluster tables (the game rs_deal_trainer_best_response measures; RS_F32 trainers).  The prepared
+ * game and its workspace stay with the trainer (counted by rs_deal_trainer_br_bytes, given back by rs_deal_trainer_br_release).  Does not advance
+ * rs_deal_trainer_iterations. */
+int rs_deal_trainer_range_cfr(rs_deal_trainer *trainer, uint64_t iterations, const rs_range_cfr_params *params /* NULL = defaults */,
+                              const rs_dcfr_params *dcfr /* NULL = no ticks */, double *values /* [2], may be NULL */);
 /* The best-response objects a trainer keeps between calls (one per showdown mode: the game-only index, and the walk's workspace -- a buffer per tree edge while that stays
  * below 16 GB, two per tree depth otherwise): the device bytes they hold, a call that gives the workspaces back (the next best response allocates them again), and the kernel
  * launches the last call made (-1: the depth-first walk ran, one or two launches per tree node). */

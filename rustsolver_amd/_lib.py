@@ -23,6 +23,7 @@ OPP_FULL, OPP_SAMPLE = 0, 1
 BR_MAX, BR_AVERAGE = 0, 1   # rs_best_response modes
 BR_SORTED = 0x100           # | into the mode: showdowns by rank order (O(n log n) per run-out), sums in a fixed order of their own
 BR_REAL = 0x200             # | into BR_MAX: the best response in the real game (info set = board cards seen + own hole cards) against the abstracted average strategy
+BR_CURRENT = 0x400          # | into any mode: the strategies read are the CURRENT ones (get_strategy of the regrets) instead of the average ones
 DIST_EMD, DIST_L2 = 0, 1
 K_UPDATE, K_NODE_UTIL, K_REACH, K_CHANCE, K_DISCOUNT, K_STRATEGY, K_TREE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 
@@ -84,6 +85,10 @@ class DealTrainerParams(C.Structure):
 class DcfrParams(C.Structure):   # rs_dcfr_params
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("interval", C.c_uint64), ("cap", C.c_uint64), ("t0", C.c_uint64),
                 ("fused", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RangeCfrParams(C.Structure):   # rs_range_cfr_params
+    _fields_ = [("mode", C.c_int32), ("sorted", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Profile(C.Structure):
@@ -229,6 +234,13 @@ SYMBOLS = {
     "rs_deal_trainer_last_br": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     "rs_deal_trainer_calc_br": (C.c_int, [_P, _P]),
     "rs_deal_trainer_best_response": (C.c_int, [_P, C.c_int, _P]),
+    "rs_deal_trainer_range_cfr": (C.c_int, [_P, C.c_uint64, C.POINTER(RangeCfrParams), C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
+    "rs_range_cfr_create": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeCfrParams), _PP]),
+    "rs_range_cfr_destroy": (None, [_P]),
+    "rs_range_cfr_iterate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    "rs_range_cfr_train": (C.c_int, [_P, C.c_uint64, C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
+    "rs_range_cfr_bytes": (C.c_size_t, [_P]),
+    "rs_range_cfr_launches": (C.c_int, [_P]),
     "rs_deal_trainer_br_bytes": (C.c_size_t, [_P]),
     "rs_deal_trainer_br_release": (C.c_int, [_P]),
     "rs_deal_trainer_br_launches": (C.c_int, [_P, C.c_int]),

@@ -9,6 +9,8 @@
 //    abstracted game (and, mode RS_BR_AVERAGE, the value of the average strategy profile itself), in vector form over the two hand
 //    ranges of a single-round game on a full board -- the configuration the reference ships (options::default_flop()).  Reach and
 //    value vectors live on the device as f64; every sum runs in a fixed order, so the CPU oracle reproduces the result bit for bit.
+//  * rs_range_cfr_*: full-width CFR over the hand ranges on the same walk (the opponent plays the current strategy, the traverser's own nodes keep their info sets' sums as
+//    regrets): three more job kinds of the best response's job table and launcher.  RS_BR_CURRENT hands the readers the regret array.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -61,6 +63,26 @@ __device__ __forceinline__ void final_sigma(const void *ssum, size_t cell_off, u
     }
     const float uni = 1.0f / (float)n_actions;
     for (uint32_t a = 0; a < n_actions; a++) sig[a] = (norm > 0.0f) ? ((r[a] > (V)0) ? (float)r[a] / norm : 0.0f) : uni;
+}
+
+// Infoset::get_strategy (infoset.rs:83-102) of ONE lane of a node's REGRET rows: the same text over the other array (positive cells over their f32 sum in index order,
+// uniform where none is positive; regret_match<A, float> of rs_device.hpp on f32 cells), so the readers above take the regret array where they are asked for the
+// current strategy (RS_BR_CURRENT, the full-width sweep's reach)
+// The full-width sweep's kernels call this form: unrolled to RS_MAX_ACTIONS with the action count as a predicate, so that r[] and sig[] stay registers (indexed by a
+// run-time count they become scratch on gfx950); r[] hands the regret row back, entries from n_actions on are 0 / unused.
+template <int DT>
+__device__ __forceinline__ void current_sigma(const void *regrets, size_t cell_off, uint32_t pitch, uint32_t n_actions, uint32_t lane,
+                                              typename Elem<DT>::val (&r)[RS_MAX_ACTIONS], float (&sig)[RS_MAX_ACTIONS]) {
+    using V = typename Elem<DT>::val;
+    float norm = 0.0f;
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++) {
+        r[a] = (uint32_t)a < n_actions ? Elem<DT>::at(regrets, cell_off + (size_t)a * pitch + lane) : (V)0;
+        if (r[a] > (V)0) norm += (float)r[a];
+    }
+    const float uni = 1.0f / (float)n_actions;
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++) sig[a] = (norm > 0.0f) ? ((r[a] > (V)0) ? (float)r[a] / norm : 0.0f) : uni;
 }
 
 struct BrNodeRow {   // one action node's strategy_sum block
@@ -1189,9 +1211,167 @@ __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards_jobs(const uint
     br_terminal_boards_body(mask_p, score_p, pw, n_p, mask_o, score_o, j.q, n_o, bmask, j.uncontested, j.value, j.v);
 }
 
+// ---- the full-width sweep (rs_range_cfr_*): vector-form CFR over both ranges and every run-out on this walk, f32 tables ----------------------------------------------
+// The opponent plays get_strategy of its regrets (the reach kernels above, handed the regret array), leaves and opponent nodes on the way up are the best response's.  New:
+// the traverser's OWN reach pi goes down beside q (the strategy sums want it), and its own nodes keep the per-info-set sums RS_BR_MAX only compares:
+//     S[a][c] = sum of vch[a][lane] over the info set's lanes, list order, from 0.0          U[c] = sum_a (double)sigma[a][c] * S[a][c], a ascending from 0.0
+//     P[c]    = sum of pi[lane] over the same lanes in the same order
+//     regret[a][c] = (float)((double)regret[a][c] + (S[a][c] - U[c]))   (RS_UPD_RMPLUS: a result that is not > 0.0f becomes 0.0f, visit_f32's rule)
+//     ssum[a][c]   = (float)((double)ssum[a][c] + P[c] * (double)sigma[a][c])
+//     v[lane]      = sum_a (double)sigma[a][c(lane)] * vch[a][lane], a ascending from 0.0       (RS_BR_AVERAGE's expression with the current strategy)
+// sigma read from the regret row before it is written; every row written once per sweep.  Every addition has ONE order whatever form or tree order runs it.
+// own node on the way down: pi_a[lane] = pi[lane] * sigma(cluster(lane), a).  (A lane that is no deal looks cluster 0 up, as the opponent's reach does: no list holds it.)
+__device__ __forceinline__ void br_own_reach_lane(const void *__restrict__ regrets, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t h, uint32_t n_pad,
+                                                  const double *__restrict__ pi, double *__restrict__ pi_out /*[A][n_pad]*/) {
+    float r[RS_MAX_ACTIONS], sig[RS_MAX_ACTIONS];
+    current_sigma<kDT_F32>(regrets, row.cell_off, row.pitch, row.n_actions, cid[h], r, sig);
+    const double ph = pi[h];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < row.n_actions) pi_out[(size_t)a * n_pad + h] = ph * (double)sig[a];
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_own_reach(const void *__restrict__ regrets, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
+                                                           const double *__restrict__ pi, double *__restrict__ pi_out) {
+    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
+    if (h < n) br_own_reach_lane(regrets, row, cid, h, n_pad, pi, pi_out);
+}
+// (level plan) sliced over the XCDs by hand as k_br_opp_reach_jobs: the regret rows are gathered by cluster id just as the strategy sums are there
+__global__ __launch_bounds__(kBrBlock) void k_br_own_reach_jobs(const void *__restrict__ regrets, const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad, uint32_t n_hands) {
+    const BrJob j = jobs[blockIdx.y];
+    const uint32_t xcd = blockIdx.x & 7u, w = blockIdx.x >> 3, per = (n_hands + 7u) / 8u, lo = xcd * per;
+    if (lo >= n_hands) return;
+    const uint32_t hs = min(per, n_hands - lo), idx = w * kBrBlock + threadIdx.x, b = idx / hs;
+    const uint32_t h = b * n_hands + lo + (idx - b * hs);
+    if (h >= n || b >= n / n_hands) return;
+    br_own_reach_lane(regrets, j.row, j.cid, h, n_pad, j.q, j.q_out);
+}
+
+// the row writes of one info set: U from the sums, then regret and strategy-sum cells of every action
+__device__ __forceinline__ void br_cfr_store(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, uint32_t c, const float (&r)[RS_MAX_ACTIONS],
+                                             const float (&sig)[RS_MAX_ACTIONS], const double (&s)[RS_MAX_ACTIONS], double P, int rmplus) {
+    double U = 0.0;
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < row.n_actions) U += (double)sig[a] * s[a];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < row.n_actions) {
+            const size_t at = row.cell_off + (size_t)a * row.pitch + c;
+            float nr = (float)((double)r[a] + (s[a] - U));
+            if (rmplus && !(nr > 0.0f)) nr = 0.0f;
+            regrets[at] = nr;
+            ssum[at] = (float)((double)ssum[at] + P * (double)sig[a]);
+        }
+}
+// own node on the way up, one THREAD per info set: the list in steps of 8 lanes -- their ids once, then the pi and every (action, lane) value of the step in flight
+// together (br_own_body's short-list trick; a river info set of a bucketed abstraction is one step), the additions in list order.  One pass: the step's lanes get their v
+// while their values are in registers.
+__device__ __forceinline__ void br_cfr_own_body(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start /*[n_clusters + 2]*/,
+                                                const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
+                                                const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
+    for (uint32_t i = start[n_clusters] + blockIdx.x * kBrBlock + threadIdx.x; i < start[n_clusters + 1]; i += gridDim.x * kBrBlock) v[order[i]] = 0.0;   // no deal: worth 0
+    const uint32_t c = blockIdx.x * kBrBlock + threadIdx.x;
+    if (c >= n_clusters) return;
+    const uint32_t lo = start[c], hi = start[c + 1];
+    if (lo == hi) return;   // no dealt lane: the cells stay
+    float r[RS_MAX_ACTIONS], sig[RS_MAX_ACTIONS];
+    current_sigma<kDT_F32>(regrets, row.cell_off, row.pitch, row.n_actions, c, r, sig);
+    double s[RS_MAX_ACTIONS];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++) s[a] = 0.0;
+    double P = 0.0;
+    for (uint32_t i = lo; i < hi; i += 8) {
+        uint32_t idx[8];
+        double tp[8], va[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) idx[k] = i + k < hi ? order[i + k] : order[lo];
+#pragma unroll
+        for (int k = 0; k < 8; k++) tp[k] = pi[idx[k]], va[k] = 0.0;
+#pragma unroll
+        for (int a = 0; a < RS_MAX_ACTIONS; a++)
+            if ((uint32_t)a < row.n_actions) {
+                const double *ra = vch + (size_t)a * n_pad;
+                double t[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) t[k] = ra[idx[k]];
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    if (i + k < hi) {
+                        s[a] += t[k];
+                        va[k] += (double)sig[a] * t[k];
+                    }
+            }
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (i + k < hi) {
+                P += tp[k];
+                v[idx[k]] = va[k];
+            }
+    }
+    br_cfr_store(regrets, ssum, row, c, r, sig, s, P, rmplus);
+}
+// ... one WAVE per info set, where info sets hold many lanes (br_wave_per_info_set): 64 gathers per step and row, the additions one after the other in list order out of
+// the neighbours' registers (br_own_wave_body), so every lane holds the thread form's sums, bit for bit; lane 0 writes the rows
+__device__ __forceinline__ void br_cfr_own_wave_body(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start,
+                                                     const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
+                                                     const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * kBrBlock + threadIdx.x) >> 6, n_waves = gridDim.x * (kBrBlock >> 6);
+    for (uint32_t i = start[n_clusters] + blockIdx.x * kBrBlock + threadIdx.x; i < start[n_clusters + 1]; i += gridDim.x * kBrBlock) v[order[i]] = 0.0;
+    for (uint32_t c = wave; c < n_clusters; c += n_waves) {
+        const uint32_t lo = start[c], hi = start[c + 1];
+        if (lo == hi) continue;
+        float r[RS_MAX_ACTIONS], sig[RS_MAX_ACTIONS];
+        current_sigma<kDT_F32>(regrets, row.cell_off, row.pitch, row.n_actions, c, r, sig);
+        double s[RS_MAX_ACTIONS];
+#pragma unroll
+        for (int a = 0; a < RS_MAX_ACTIONS; a++) s[a] = 0.0;
+        double P = 0.0;
+        for (uint32_t i = lo; i < hi; i += 64) {
+            const uint32_t cnt = min(64u, hi - i);   // wave-uniform
+            const uint32_t h = order[lane < cnt ? i + lane : lo];
+            const double tp = lane < cnt ? pi[h] : 0.0;
+            double va = 0.0;
+#pragma unroll
+            for (int a = 0; a < RS_MAX_ACTIONS; a++)
+                if ((uint32_t)a < row.n_actions) {
+                    const double t = lane < cnt ? vch[(size_t)a * n_pad + h] : 0.0;
+                    va += (double)sig[a] * t;
+                    const int t_lo = __double2loint(t), t_hi = __double2hiint(t);
+                    double acc = s[a];
+                    for (uint32_t k = 0; k < cnt; ++k) acc += __hiloint2double(__builtin_amdgcn_readlane(t_hi, (int)k), __builtin_amdgcn_readlane(t_lo, (int)k));
+                    s[a] = acc;
+                }
+            const int p_lo = __double2loint(tp), p_hi = __double2hiint(tp);
+            for (uint32_t k = 0; k < cnt; ++k) P += __hiloint2double(__builtin_amdgcn_readlane(p_hi, (int)k), __builtin_amdgcn_readlane(p_lo, (int)k));
+            if (lane < cnt) v[h] = va;
+        }
+        if (lane == 0) br_cfr_store(regrets, ssum, row, c, r, sig, s, P, rmplus);
+    }
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start,
+                                                         const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
+                                                         const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
+    br_cfr_own_body(regrets, ssum, row, start, order, n_clusters, n_pad, vch, pi, rmplus, v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_jobs(float *__restrict__ regrets, float *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n_pad, int rmplus) {
+    const BrJob j = jobs[blockIdx.y];
+    br_cfr_own_body(regrets, ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, j.q, rmplus, j.v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start,
+                                                              const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
+                                                              const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
+    br_cfr_own_wave_body(regrets, ssum, row, start, order, n_clusters, n_pad, vch, pi, rmplus, v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave_jobs(float *__restrict__ regrets, float *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n_pad,
+                                                                   int rmplus) {
+    const BrJob j = jobs[blockIdx.y];
+    br_cfr_own_wave_body(regrets, ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, j.q, rmplus, j.v);
+}
+
 // What a node asks of the device.  The kinds stand in the order of their launches within a tree depth -- reach on the way down, values on the way up -- which traces and
 // br_launches() show.  A new own-node form is a body, a kind here, a line in BrRun::own_kind and a case in BrRun::launch.
-enum BrKind { kBrReachGrouped, kBrReach, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnThread, kBrSum, kBrKinds };
+// (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up)
+enum BrKind { kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread, kBrSum, kBrKinds };
 // launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
 static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal; }
 // P, Pc, O and Q of br_terminal_sorted_body
@@ -1233,6 +1413,10 @@ struct BrRun {
     int mode = RS_BR_MAX;
     bool sorted = false;           // RS_BR_SORTED: showdowns by rank order
     bool real = false;             // RS_BR_REAL (this call): the traverser's info sets are (prefix, hand), its own nodes go to k_br_own_real_*
+    bool current = false;          // RS_BR_CURRENT (this call): get_strategy of the regrets where the walk reads a strategy
+    bool cfr = false;              // the object is a full-width solver's (br_cfr_sweep): pi buffers in the workspace, own nodes go to k_br_cfr_own*
+    int cfr_rmplus = 0;            // ... RS_UPD_RMPLUS of the sweep in flight
+    double *d_pi0[2] = {nullptr, nullptr};    // ... the traverser's own reach at the root: 1.0 on every lane
     uint32_t per_prefix[RS_MAX_ROUNDS] = {1, 1, 1};   // run-outs under a prefix of round r
     int p = 0;
     uint32_t NB = 1;
@@ -1240,6 +1424,7 @@ struct BrRun {
     BrSide side[2];
     std::vector<DevBuf<char>> allocs;
     std::vector<double *> q_level, v_level;   // per tree depth: [max actions][n_pad] children buffers
+    std::vector<double *> pi_level;           // ... and the traverser's own reach (full-width sweep)
     double *d_root = nullptr;                 // [n_pad_max]: the root values of the traverser's lanes (depth-first walk)
     bool last_level_plan = false;             // what the last br_execute ran, and its launches (level plan)
     int last_launches = 0;
@@ -1250,6 +1435,7 @@ struct BrRun {
         ws.reset();
         q_level.clear();
         v_level.clear();
+        pi_level.clear();
         d_root = nullptr;
     }
     size_t n_pad_max = 0;
@@ -1288,19 +1474,21 @@ struct BrRun {
         const BrSide &me = side[pl], &op = side[1 - pl];
         size_t doubles = me.n_pad;   // the root vector
         for (const rs_tree_node &n : tree->nodes)
-            if (n.kind == RS_NODE_ACTION && n.n_children > 0) doubles += size_t(n.n_children) * (size_t(me.n_pad) + (int(n.player) != pl ? size_t(op.n_pad) : 0));
+            if (n.kind == RS_NODE_ACTION && n.n_children > 0)   // children's values; an opponent node their reach as well, an own node of the full-width sweep their pi
+                doubles += size_t(n.n_children) * (size_t(me.n_pad) + (int(n.player) != pl ? size_t(op.n_pad) : (cfr ? size_t(me.n_pad) : 0)));
         return doubles * sizeof(double);
     }
 
     // which kernel takes the traverser's own nodes of round r / the opponent's: groups and columns are the level plan's only
     BrKind own_kind(int r) const {
         const BrSide &me = side[p];
+        if (cfr) return br_wave_per_info_set(me.n, me.n_clusters[r]) ? kBrOwnCfrWave : kBrOwnCfrThread;   // (no groups, no columns: a follow-up once a profile asks)
         if (real) return kBrOwnReal;   // whatever the abstraction's lists would have asked for
         if (ws_levels && mode == RS_BR_MAX && me.grouped[r]) return kBrOwnGrouped;
         if (ws_levels && me.d_tord[r]) return kBrOwnCols;
         return br_wave_per_info_set(me.n, me.n_clusters[r]) ? kBrOwnWave : kBrOwnThread;
     }
-    BrKind reach_kind(int r) const { return ws_levels && side[1 - p].grouped[r] ? kBrReachGrouped : kBrReach; }
+    BrKind reach_kind(int r) const { return !cfr && ws_levels && side[1 - p].grouped[r] ? kBrReachGrouped : kBrReach; }
 
     // One traverser's pass as jobs in the order of their launches: reach by ascending depth, the leaves, values by descending depth, within a depth by kind (and round, where
     // the kind is launched per round).  A run of equal `key` is one launch of the level plan.
@@ -1313,6 +1501,7 @@ struct BrRun {
         std::vector<Entry> entries;
         std::vector<BrJob> jobs;           // jobs[i] is entries[i]'s
         std::vector<int> job_at, sum_at;   // per tree node: its job (leaf, own node, an opponent node's reach) and an opponent node's sum job, -1 = none
+        std::vector<int> own_reach_at;     // ... an own node's reach job (full-width sweep)
         double *root = nullptr;            // where the root's values arrive
     };
     // host only: gives every node its buffers and fills the jobs
@@ -1326,11 +1515,12 @@ struct BrRun {
             return s;
         };
         pl.root = ws_levels ? slot(me.n_pad) : d_root;
-        std::vector<const double *> q_in(N, nullptr);
+        std::vector<const double *> q_in(N, nullptr), pi_in(N, nullptr);
         std::vector<double *> v_out(N, nullptr);
         std::vector<int> folds(N, -1);   // an own node whose kernel adds up the rows below an opponent's child itself (by groups, real game; level plan): its job
         v_out[0] = pl.root;
         q_in[0] = op.d_init_q;
+        pi_in[0] = d_pi0[p];
         std::vector<BrPlan::Entry> entries;   // in the tree's order; gathered into pl in launch order below
         std::vector<BrJob> jobs;
         auto add = [&](BrKind kind, int r, size_t id, const BrJob &j) {
@@ -1352,6 +1542,7 @@ struct BrRun {
             if (n.kind != RS_NODE_ACTION) {   // chance nodes pass through (cfr.rs:306-313)
                 if (n.n_children > 0) {
                     q_in[size_t(n.children[0])] = q_in[id];
+                    pi_in[size_t(n.children[0])] = pi_in[id];
                     v_out[size_t(n.children[0])] = v_out[id];
                 }
                 continue;
@@ -1376,6 +1567,18 @@ struct BrRun {
                     j.kmax = me.kmax[r];
                 }
                 if (ws_levels && (kind == kBrOwnGrouped || kind == kBrOwnReal)) folds[id] = int(jobs.size());
+                if (cfr) {   // its children's pi on the way down; the update reads the pi that came in
+                    double *pch = ws_levels ? slot(size_t(n.n_children) * me.n_pad) : pi_level[size_t(d)];
+                    BrJob jr{};
+                    jr.row = j.row;
+                    jr.cid = me.d_cid[r];
+                    jr.q = pi_in[id];
+                    jr.q_out = pch;
+                    jr.n_children = j.n_children;
+                    add(kBrReachOwn, r, id, jr);
+                    j.q = pi_in[id];
+                    for (int a = 0; a < n.n_children; ++a) pi_in[size_t(n.children[a])] = pch + size_t(a) * me.n_pad;
+                }
                 add(kind, r, id, j);
                 for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = q_in[id];
             } else {
@@ -1398,7 +1601,7 @@ struct BrRun {
                         }
                 }
                 if (!taken) add(kBrSum, r, id, j);
-                for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = qch + size_t(a) * op.n_pad;
+                for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = qch + size_t(a) * op.n_pad, pi_in[size_t(n.children[a])] = pi_in[id];
             }
             for (int a = 0; a < n.n_children; ++a) v_out[size_t(n.children[a])] = vch + size_t(a) * me.n_pad;
         }
@@ -1408,11 +1611,12 @@ struct BrRun {
         std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return entries[a].key < entries[b].key; });
         pl.job_at.assign(N, -1);
         pl.sum_at.assign(N, -1);
+        pl.own_reach_at.assign(N, -1);
         pl.entries.reserve(perm.size());
         pl.jobs.reserve(perm.size());
         for (uint32_t i : perm) {
             const BrPlan::Entry &e = entries[i];
-            (e.kind == kBrSum ? pl.sum_at : pl.job_at)[size_t(e.node)] = int(pl.jobs.size());
+            (e.kind == kBrSum ? pl.sum_at : (e.kind == kBrReachOwn ? pl.own_reach_at : pl.job_at))[size_t(e.node)] = int(pl.jobs.size());
             pl.entries.push_back(e);
             pl.jobs.push_back(jobs[i]);
         }
@@ -1428,7 +1632,8 @@ struct BrRun {
         if (err != hipSuccess) return;
         const BrSide &me = side[p], &op = side[1 - p];
         const hipStream_t s = t->stream;
-        const void *ssum = t->d_ssum.get();
+        const void *ssum = (current || cfr) ? t->d_regrets.get() : t->d_ssum.get();   // what the strategy readers read: the average strategy's array or the current one's
+        float *const cfr_regrets = reinterpret_cast<float *>(t->d_regrets.get()), *const cfr_ssum = reinterpret_cast<float *>(t->d_ssum.get());   // the full-width update's
         const dim3 block(kBrBlock);
         auto most = [&](auto field) {   // the grid is sized by the largest of the launch's jobs
             uint32_t m = 0;
@@ -1453,6 +1658,11 @@ struct BrRun {
             }
             const auto k = RS_BR_PICK(t->dtype, k_br_opp_reach_jobs);
             hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((op.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, op.n, op.n_pad, op.n_hands);
+            break;
+        }
+        case kBrReachOwn: {
+            if (!d_jobs) hipLaunchKernelGGL(k_br_own_reach, dim3(grid1(me.n)), block, 0, s, ssum, j.row, j.cid, me.n, me.n_pad, j.q, j.q_out);
+            else hipLaunchKernelGGL(k_br_own_reach_jobs, dim3(8u * grid1(NB * ((me.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, me.n, me.n_pad, me.n_hands);
             break;
         }
         case kBrLeaf: {
@@ -1530,6 +1740,20 @@ struct BrRun {
             else hipLaunchKernelGGL(k_br_own_real_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
             break;
         }
+        case kBrOwnCfrWave: {
+            if (!d_jobs)
+                hipLaunchKernelGGL(k_br_cfr_own_wave, dim3(br_wave_blocks(j.n_clusters)), block, 0, s, cfr_regrets, cfr_ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch,
+                                   j.q, cfr_rmplus, j.v);
+            else hipLaunchKernelGGL(k_br_cfr_own_wave_jobs, dim3(br_wave_blocks(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
+            break;
+        }
+        case kBrOwnCfrThread: {
+            if (!d_jobs)
+                hipLaunchKernelGGL(k_br_cfr_own, dim3(grid1(j.n_clusters)), block, 0, s, cfr_regrets, cfr_ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch, j.q,
+                                   cfr_rmplus, j.v);
+            else hipLaunchKernelGGL(k_br_cfr_own_jobs, dim3(grid1(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
+            break;
+        }
         case kBrOwnThread: {
             if (!d_jobs) {
                 hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own), dim3(grid1(j.n_clusters)), block, 0, s, ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch, mode, j.v);
@@ -1558,6 +1782,7 @@ struct BrRun {
         auto one = [&](int at) { launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, nullptr, 1, &pl.jobs[size_t(at)]); };
         const bool own = n.kind == RS_NODE_ACTION && int(n.player) == p;
         if (!own) one(pl.job_at[size_t(id)]);   // a leaf, or the reach of an opponent node's children
+        else if (pl.own_reach_at[size_t(id)] >= 0) one(pl.own_reach_at[size_t(id)]);   // full-width sweep: the traverser's own reach of its children
         if (n.kind == RS_NODE_TERMINAL) return;
         for (int a = 0; a < n.n_children; ++a) walk(pl, n.children[a]);
         one(own ? pl.job_at[size_t(id)] : pl.sum_at[size_t(id)]);
@@ -1945,51 +2170,62 @@ void br_release_workspace(BrRun *run) {
 }
 int br_last_launches(const BrRun *run) { return run && run->last_level_plan ? run->last_launches : -1; }
 
-static int br_check_mode(int mode /* without RS_BR_SORTED and RS_BR_REAL */, bool real) {
-    if (mode != RS_BR_MAX && mode != RS_BR_AVERAGE) return fail(RS_ERR_INVALID, "rs_best_response: mode is RS_BR_MAX or RS_BR_AVERAGE (| RS_BR_SORTED, RS_BR_MAX | RS_BR_REAL)");
+static int br_check_mode(int mode /* without RS_BR_SORTED, RS_BR_REAL and RS_BR_CURRENT */, bool real) {
+    if (mode != RS_BR_MAX && mode != RS_BR_AVERAGE)
+        return fail(RS_ERR_INVALID, "rs_best_response: mode is RS_BR_MAX or RS_BR_AVERAGE (| RS_BR_SORTED, | RS_BR_CURRENT, RS_BR_MAX | RS_BR_REAL)");
     if (real && mode != RS_BR_MAX)
         return fail(RS_ERR_INVALID, "rs_best_response: RS_BR_REAL goes with RS_BR_MAX (the average strategy lives in the abstraction: RS_BR_AVERAGE | RS_BR_REAL means nothing)");
+    return RS_OK;
+}
+
+// the walk's workspace: allocated by the first walk and kept with the object (see br_execute)
+static int br_ensure_workspace(BrRun &run) {
+    if (run.ws) return RS_OK;
+    rs_table *t = run.t;
+    (void)t;
+    const size_t need = std::max(run.level_plan_bytes(0), run.level_plan_bytes(1));
+    size_t free_b = 0, total_b = 0;
+    const bool levels = !knobs_resolve(nullptr).br_depth_first && need <= kBrLevelPlanBytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
+    (void)hipGetLastError();
+    if (levels && run.ws.alloc(need / sizeof(double), &run.dev_bytes) == hipSuccess) {
+        run.ws_levels = true;
+    } else {
+        int max_a = 1;
+        for (const rs_tree_node &n : run.tree->nodes) max_a = std::max(max_a, n.n_children);
+        const int depth = run.max_depth;   // only action nodes take a level of child buffers
+        const size_t per = size_t(max_a) * run.n_pad_max, each = run.cfr ? 3 : 2;   // reach and values; the full-width sweep's own reach
+        if (run.ws.alloc(each * size_t(depth) * per + run.n_pad_max, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
+        run.ws_levels = false;
+        for (int l = 0; l < depth; ++l) {
+            run.q_level.push_back(run.ws + (each * size_t(l)) * per);
+            run.v_level.push_back(run.ws + (each * size_t(l) + 1) * per);
+            if (run.cfr) run.pi_level.push_back(run.ws + (each * size_t(l) + 2) * per);
+        }
+        run.d_root = run.ws + each * size_t(depth) * per;
+    }
     return RS_OK;
 }
 
 // the walk: both traversers against the table as it stands
 int br_execute(BrRun *prepared, int mode, double *out) {
     if (!prepared || !out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
-    const bool real = (mode & RS_BR_REAL) != 0;
-    mode &= ~RS_BR_REAL;
+    const bool real = (mode & RS_BR_REAL) != 0, current = (mode & RS_BR_CURRENT) != 0;
+    mode &= ~(RS_BR_REAL | RS_BR_CURRENT);
     if (int rc = br_check_mode(mode, real)) return rc;
     BrRun &run = *prepared;
+    if (run.cfr) return fail(RS_ERR_INVALID, "rs_best_response: the prepared game belongs to a full-width solver");
     rs_table *t = run.t;
     if (int rc = table_settle(t)) return rc;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     run.mode = mode;
     run.real = real;
+    run.current = current;
     run.err = hipSuccess;
     // The level plan wants a buffer per tree edge (full 1 176-combo ranges from a flop on the 706-node tree: 59 GB, and an allocation of that size takes seconds; 200 combos: 10 GB)
     // and buys launches, not kernel time (4 300 -> 66 per call; at full ranges both orders spend 0.24-0.27 s in their kernels): it is taken while it fits kBrLevelPlanBytes and half
     // of the free memory, else the depth-first walk runs with its two buffers per tree depth.  The workspace is allocated by the first call and KEPT with the object
     // (br_workspace_bytes / br_release_workspace: a trainer holds one object per showdown mode).
-    if (!run.ws) {
-        const size_t need = std::max(run.level_plan_bytes(0), run.level_plan_bytes(1));
-        size_t free_b = 0, total_b = 0;
-        const bool levels = !knobs_resolve(nullptr).br_depth_first && need <= kBrLevelPlanBytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
-        (void)hipGetLastError();
-        if (levels && run.ws.alloc(need / sizeof(double), &run.dev_bytes) == hipSuccess) {
-            run.ws_levels = true;
-        } else {
-            int max_a = 1;
-            for (const rs_tree_node &n : run.tree->nodes) max_a = std::max(max_a, n.n_children);
-            const int depth = run.max_depth;   // only action nodes take a level of child buffers
-            const size_t per = size_t(max_a) * run.n_pad_max;
-            if (run.ws.alloc(size_t(2) * size_t(depth) * per + run.n_pad_max, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
-            run.ws_levels = false;
-            for (int l = 0; l < depth; ++l) {
-                run.q_level.push_back(run.ws + size_t(2 * l) * per);
-                run.v_level.push_back(run.ws + size_t(2 * l + 1) * per);
-            }
-            run.d_root = run.ws + size_t(2) * size_t(depth) * per;
-        }
-    }
+    if (int rc = br_ensure_workspace(run)) return rc;
     run.last_level_plan = run.ws_levels;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
@@ -2004,6 +2240,127 @@ int br_execute(BrRun *prepared, int mode, double *out) {
     return RS_OK;
 }
 
+// ---- the full-width sweep on a prepared game ---------------------------------------------------------------------------------------------------------------------
+// One traverser's sweep over the table as it stands; *value = the sum of the root's values, ascending (the traverser's value per deal under the current profile).
+// It WRITES the table: a training loop's working copy is settled first and kept shadow records are invalidated (rs_table.epoch), as every other writer does.
+int br_cfr_mark(BrRun *prepared) {
+    if (!prepared) return fail(RS_ERR_INVALID, "rs_range_cfr: NULL argument");
+    if (prepared->ws) return fail(RS_ERR_INVALID, "rs_range_cfr: the prepared game has walked already");
+    if (prepared->t->dtype != RS_F32)
+        return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr: RS_F32 tables only (the sums are per-deal probabilities times pots: no integer scale, and binary16 cells are out of scope)");
+    prepared->cfr = true;
+    return RS_OK;
+}
+int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
+    if (!prepared || !prepared->cfr) return fail(RS_ERR_INVALID, "rs_range_cfr: NULL argument");
+    if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_iterate: traverser is 0 or 1");
+    BrRun &run = *prepared;
+    rs_table *t = run.t;
+    if (int rc = table_settle(t, true)) return rc;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    run.mode = RS_BR_AVERAGE;
+    run.real = run.current = false;
+    run.cfr_rmplus = rmplus ? 1 : 0;
+    run.err = hipSuccess;
+    for (int p = 0; p < 2; ++p)
+        if (!run.d_pi0[p]) {
+            const std::vector<double> ones(run.side[p].n, 1.0);
+            run.d_pi0[p] = run.upload(ones);
+            if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr: the root reach");
+        }
+    if (int rc = br_ensure_workspace(run)) return rc;
+    run.last_level_plan = run.ws_levels;
+    run.last_launches = 0;
+    std::vector<double> root(run.n_pad_max);
+    run.p = traverser;
+    ++t->epoch;   // whatever happens below, rows may have been written
+    if (int rc = run.run_traverser(root.data())) return rc;
+    run.last_launches = run.ws_levels ? run.n_launches : 0;
+    double total = 0.0;
+    for (uint32_t l = 0; l < run.side[traverser].n; ++l) total += root[l];   // ascending, as br_execute
+    if (value) *value = total;
+    return RS_OK;
+}
+
+}  // namespace rs
+
+struct rs_range_cfr {
+    rs::BrRun *run = nullptr;
+    rs_table *table = nullptr;
+    int mode = 0;
+};
+
+extern "C" {
+
+int rs_range_cfr_create(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                        size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_cfr_params *params, rs_range_cfr **out) {
+    if (!out) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
+    *out = nullptr;
+    if (!t) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate): the index kernels go to the table's stream
+    const int mode = params ? params->mode : 0;
+    if (mode != 0 && mode != RS_UPD_RMPLUS) return fail(RS_ERR_INVALID, "rs_range_cfr_create: params->mode is 0 or RS_UPD_RMPLUS");
+    if (params && (params->sorted < RS_FORM_DEFAULT || params->sorted > RS_FORM_OFF)) return fail(RS_ERR_INVALID, "rs_range_cfr_create: params->sorted is an RS_FORM_* value");
+    if (t->dtype != RS_F32)
+        return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_create: RS_F32 tables only (the sums are per-deal probabilities times pots: no integer scale, and binary16 cells are out of scope)");
+    rs::BrRun *run = nullptr;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, !params || params->sorted != RS_FORM_OFF, &run)) return rc;
+    if (int rc = rs::br_cfr_mark(run)) {
+        rs::br_free(run);
+        return rc;
+    }
+    rs_range_cfr *s = new (std::nothrow) rs_range_cfr;
+    if (!s) {
+        rs::br_free(run);
+        return fail(RS_ERR_OOM, "rs_range_cfr_create");
+    }
+    s->run = run;
+    s->table = t;
+    s->mode = mode;
+    *out = s;
+    return RS_OK;
+}
+void rs_range_cfr_destroy(rs_range_cfr *s) {
+    if (!s) return;
+    rs::br_free(s->run);
+    delete s;
+}
+int rs_range_cfr_iterate(rs_range_cfr *s, int traverser, double *value) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_iterate: NULL argument");
+    return rs::br_cfr_sweep(s->run, traverser, s->mode == RS_UPD_RMPLUS, value);
+}
+int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_params *dcfr, double *values) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_train: NULL argument");
+    return rs::br_cfr_train(s->run, s->table, s->mode == RS_UPD_RMPLUS, iterations, dcfr, values);
+}
+size_t rs_range_cfr_bytes(const rs_range_cfr *s) { return s ? rs::br_held_bytes(s->run) : 0; }
+int rs_range_cfr_launches(const rs_range_cfr *s) { return s ? rs::br_last_launches(s->run) : -1; }
+
+}  // extern "C"
+
+namespace rs {
+
+// iterations of (traverser 0's sweep, traverser 1's); with Discounted CFR a tick after iteration t (counted from dcfr->t0) when t % interval == 0 and t <= cap
+int br_cfr_train(BrRun *run, rs_table *t, int rmplus, uint64_t iterations, const rs_dcfr_params *dcfr, double *values) {
+    if (dcfr) {
+        if (dcfr->interval == 0) return fail(RS_ERR_INVALID, "rs_range_cfr_train: dcfr->interval must be > 0");
+        float probe[3];
+        if (int rc = rs_dcfr_factors(dcfr->alpha, dcfr->beta, dcfr->gamma, 1, probe)) return rc;
+    }
+    uint64_t it = dcfr ? dcfr->t0 : 0;
+    for (uint64_t k = 0; k < iterations; ++k) {
+        for (int p = 0; p < 2; ++p)
+            if (int rc = br_cfr_sweep(run, p, rmplus, values && k + 1 == iterations ? values + p : nullptr)) return rc;
+        ++it;
+        if (dcfr && it <= dcfr->cap && it % dcfr->interval == 0) {
+            float f[3];
+            if (int rc = rs_dcfr_factors(dcfr->alpha, dcfr->beta, dcfr->gamma, it / dcfr->interval, f)) return rc;
+            if (int rc = rs_discount_dcfr(t, f[0], f[1], f[2])) return rc;
+        }
+    }
+    return RS_OK;
+}
+
 }  // namespace rs
 
 extern "C" {
@@ -2013,7 +2370,7 @@ int rs_best_response_rounds(rs_table *t, const rs_tree *tree, const uint8_t *boa
     if (!out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
-    if (int rc = rs::br_check_mode(mode & ~RS_BR_REAL, (mode & RS_BR_REAL) != 0)) return rc;
+    if (int rc = rs::br_check_mode(mode & ~(RS_BR_REAL | RS_BR_CURRENT), (mode & RS_BR_REAL) != 0)) return rc;
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
     const int rc = rs::br_execute(run, mode, out);

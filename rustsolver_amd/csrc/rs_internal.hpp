@@ -136,6 +136,9 @@ int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVE
 void br_free(BrRun *prepared);
 size_t br_held_bytes(const BrRun *prepared);        // device bytes the object holds: the game-only half + the walk's workspace (kept from the first br_execute on)
 void br_release_workspace(BrRun *prepared);         // gives the workspace back; the next br_execute allocates it again
+int br_cfr_mark(BrRun *prepared);                    // before its first walk: the prepared game is a full-width solver's (RS_F32 tables; pi buffers in its workspace)
+int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value /* may be NULL */);   // one traverser's full-width sweep; writes the table
+int br_cfr_train(BrRun *prepared, rs_table *t, int rmplus, uint64_t iterations, const rs_dcfr_params *dcfr, double *values);
 int br_last_launches(const BrRun *prepared);        // launches of the last br_execute when it ran the level plan, else -1
 // compact jobs [first, first + n) scan one source for n sibling roots (k_compact_siblings): n <= 16, no cluster ranges
 struct CompactGroup {

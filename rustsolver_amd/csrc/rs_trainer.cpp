@@ -34,6 +34,7 @@ struct rs_deal_trainer {
     std::vector<uint32_t> br_cluster[RS_MAX_ROUNDS][2];   // cluster ids of every (board prefix, hand) of every round: they never change, computed at the first best response
     bool br_cluster_ready = false;                        // ... and valid only once every (round, player) has been filled
     rs::BrRun *br_prepared[2] = {nullptr, nullptr};       // [pair loop, rank-order showdowns]: the game-only half of rs_best_response_rounds, kept between calls
+    rs::BrRun *cfr_prepared[2] = {nullptr, nullptr};      // ... and of rs_deal_trainer_range_cfr, with its own (larger) workspace
     // train()'s prune schedule (cfr.rs:213-221): with a finite prune_threshold the solver runs in RS_UPD_PRUNE mode from the start and every
     // traverser visit honours the deal's flag byte -- all zero (= unpruned, bit for bit) until a batch reaches beyond the threshold
     DevBuf<uint8_t> d_prune;           // [pitch] flags of the live batch
@@ -74,6 +75,8 @@ void rs_deal_trainer_destroy(rs_deal_trainer *tr) {
     if (!tr) return;
     for (int k = 0; k < 2; ++k)
         if (tr->br_prepared[k]) rs::br_free(tr->br_prepared[k]);
+    for (int k = 0; k < 2; ++k)
+        if (tr->cfr_prepared[k]) rs::br_free(tr->cfr_prepared[k]);
     if (tr->deal_stream) (void)hipStreamSynchronize(tr->deal_stream);   // a sort dealt ahead may still be writing the solver's records
     if (tr->solver) rs_solver_destroy(tr->solver);
     if (tr->table) (void)rs_sync(tr->table);   // nothing on the table's stream uses the trainer's buffers any more
@@ -434,13 +437,13 @@ int rs_deal_trainer_calc_br(rs_deal_trainer *tr, float *out) {
     if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_calc_br: NULL argument");
     return rs_calc_br(tr->table, tr->tree, out);
 }
+}  // extern "C"
+
 // the trainer's own game: board = the cards of board_mask in ascending order (cfr.rs:108-115), cluster ids through get_cluster
-// (hole cards first, then the board: cfr.rs:357-365)
-int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
-    if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_best_response: NULL argument");
-    const int n_board0 = __builtin_popcountll(tr->params.board_mask);
+// (hole cards first, then the board: cfr.rs:357-365) -- as rs_best_response_rounds takes it: board[5] (n_board0 cards of it), and ptrs[r * 2 + p] into the cached cluster tables (filled at the first call)
+static int trainer_game(rs_deal_trainer *tr, uint8_t (&board)[5], int &n_board0, const uint32_t *(&ptrs)[RS_MAX_ROUNDS * 2]) {
+    n_board0 = __builtin_popcountll(tr->params.board_mask);
     if (n_board0 < 3 || n_board0 > 5 || tr->n_rounds > 6 - n_board0) return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_best_response: a board of 3..5 cards and at most one betting round per street");
-    uint8_t board[5];
     int nb = 0;
     for (int c = 0; c < 52; ++c)
         if (tr->params.board_mask >> c & 1) board[nb++] = uint8_t(c);
@@ -451,7 +454,6 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     const int K = 5 - n_board0, D = 52 - n_board0;
     // the ids are a function of ranges, board and abstractions, all fixed for the trainer's life: computed once.  They are built into locals and handed to the trainer only
     // when EVERY (round, player) succeeded -- a failing get_cluster must not leave a half-filled cache behind that the next call would take for the real thing
-    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
     std::vector<uint32_t> cluster[RS_MAX_ROUNDS][2];
     for (int r = 0; r < tr->n_rounds && !tr->br_cluster_ready; ++r) {
         size_t per_prefix = 1;
@@ -488,6 +490,17 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     }
     for (int r = 0; r < tr->n_rounds; ++r)
         for (int p = 0; p < 2; ++p) ptrs[r * 2 + p] = tr->br_cluster[r][p].data();
+    return RS_OK;
+}
+
+extern "C" {
+
+int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
+    if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_best_response: NULL argument");
+    uint8_t board[5];
+    int n_board0 = 0;
+    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
+    if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
     const int which = (mode & RS_BR_SORTED) ? 1 : 0;
     if (!tr->br_prepared[which])
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
@@ -496,18 +509,44 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     return rs::br_execute(tr->br_prepared[which], mode & ~RS_BR_SORTED, out);
 }
 
+// full-width CFR on the trainer's own game (rs_range_cfr_train): a prepared game of its own per showdown form, beside the best response's two
+int rs_deal_trainer_range_cfr(rs_deal_trainer *tr, uint64_t iterations, const rs_range_cfr_params *params, const rs_dcfr_params *dcfr, double *values) {
+    if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: trainer is NULL");
+    const int mode = params ? params->mode : 0;
+    if (mode != 0 && mode != RS_UPD_RMPLUS) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: params->mode is 0 or RS_UPD_RMPLUS");
+    if (params && (params->sorted < RS_FORM_DEFAULT || params->sorted > RS_FORM_OFF)) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: params->sorted is an RS_FORM_* value");
+    if (tr->params.table_dtype != RS_F32) return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_range_cfr: RS_F32 trainers only (rs_range_cfr_create)");
+    uint8_t board[5];
+    int n_board0 = 0;
+    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
+    if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
+    const int which = (params && params->sorted == RS_FORM_OFF) ? 0 : 1;
+    if (!tr->cfr_prepared[which]) {
+        rs::BrRun *run = nullptr;
+        if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
+                                    which == 1, &run))
+            return rc;
+        if (int rc = rs::br_cfr_mark(run)) {
+            rs::br_free(run);
+            return rc;
+        }
+        tr->cfr_prepared[which] = run;
+    }
+    return rs::br_cfr_train(tr->cfr_prepared[which], tr->table, mode == RS_UPD_RMPLUS, iterations, dcfr, values);
+}
+
 // what the best-response objects a trainer keeps between calls hold on the device (the game-only index of both showdown modes + the walks' workspaces), and a way to give
 // the workspaces back (the next call allocates them again)
 size_t rs_deal_trainer_br_bytes(const rs_deal_trainer *tr) {
     size_t b = 0;
     if (tr)
-        for (int k = 0; k < 2; ++k) b += rs::br_held_bytes(tr->br_prepared[k]);
+        for (int k = 0; k < 2; ++k) b += rs::br_held_bytes(tr->br_prepared[k]) + rs::br_held_bytes(tr->cfr_prepared[k]);   // (the full-width sweep's objects as well)
     return b;
 }
 int rs_deal_trainer_br_release(rs_deal_trainer *tr) {
     if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_br_release: trainer is NULL");
-    for (int k = 0; k < 2; ++k) rs::br_release_workspace(tr->br_prepared[k]);
+    for (int k = 0; k < 2; ++k) rs::br_release_workspace(tr->br_prepared[k]), rs::br_release_workspace(tr->cfr_prepared[k]);
     return RS_OK;
 }
 int rs_deal_trainer_br_launches(const rs_deal_trainer *tr, int sorted) {   // launches of the last best-response call (level plan), -1: depth-first walk or no call yet

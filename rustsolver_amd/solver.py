@@ -364,10 +364,11 @@ class InfosetTable:
         L.check(L.load().rs_calc_br(self._h, tree._h, _vp(out)))
         return out
 
-    def best_response(self, tree, board, hands0, cluster0, hands1, cluster1, mode=L.BR_MAX):
+    def best_response(self, tree, board, hands0, cluster0, hands1, cluster1, mode=L.BR_MAX, current=False):
         """value per deal of each player against the other's average strategy: mode BR_MAX a best response inside the abstraction,
         BR_MAX | BR_REAL a best response in the real game (every hand decides for itself), BR_AVERAGE its own average strategy;
-        exploitability = best_response(...).sum() / 2"""
+        exploitability = best_response(...).sum() / 2.  current: against (and, BR_AVERAGE, with) the CURRENT strategy, get_strategy of the regrets (BR_CURRENT)"""
+        mode |= L.BR_CURRENT if current else 0
         b = np.ascontiguousarray(board, dtype=np.uint8)
         h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
         h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
@@ -378,8 +379,9 @@ class InfosetTable:
         L.check(L.load().rs_best_response(self._h, tree._h, _vp(b), _vp(h0), len(h0), _vp(c0), _vp(h1), len(h1), _vp(c1), mode, _vp(out)))
         return out
 
-    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX):
-        """multi-round best response (rs_best_response_rounds): clusters[r][p] = uint32 [prefixes of round r][n_hands_p] dense ids"""
+    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX, current=False):
+        """multi-round best response (rs_best_response_rounds): clusters[r][p] = uint32 [prefixes of round r][n_hands_p] dense ids; current: BR_CURRENT"""
+        mode |= L.BR_CURRENT if current else 0
         b = np.ascontiguousarray(board0, dtype=np.uint8)
         h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
         h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
@@ -783,9 +785,18 @@ class DealTrainer:
         L.check(L.load().rs_deal_trainer_calc_br(self._h, _vp(out)))
         return out
 
-    def best_response(self, mode=L.BR_MAX):
+    def best_response(self, mode=L.BR_MAX, current=False):
         out = np.zeros(2, dtype=np.float64)
-        L.check(L.load().rs_deal_trainer_best_response(self._h, mode, _vp(out)))
+        L.check(L.load().rs_deal_trainer_best_response(self._h, mode | (L.BR_CURRENT if current else 0), _vp(out)))
+        return out
+
+    def train_full_width(self, iterations, rmplus=False, dcfr=None, sorted_showdowns=True):
+        """rs_deal_trainer_range_cfr: `iterations` iterations of full-width, chance-enumerated CFR over both ranges on the trainer's own game and table (F32 trainers).
+        dcfr: None, True (the paper's 1.5, 0, 2, a tick per iteration) or an rs_dcfr_params from dcfr_params(...).  Returns the two players' values per deal under the
+        current profile at the last iteration.  Does not advance iterations()."""
+        out = np.zeros(2, dtype=np.float64)
+        L.check(L.load().rs_deal_trainer_range_cfr(self._h, int(iterations), C.byref(_range_cfr_params(rmplus, sorted_showdowns)), _dcfr_arg(dcfr),
+                                                   out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def br_bytes(self):
@@ -798,11 +809,11 @@ class DealTrainer:
     def br_launches(self, sorted_showdowns=True):
         return int(L.load().rs_deal_trainer_br_launches(self._h, int(sorted_showdowns)))
 
-    def exploitability(self, sorted_showdowns=True, real=False):
+    def exploitability(self, sorted_showdowns=True, real=False, current=False):
         """(BR value of player 0 + BR value of player 1) / 2 against the current average strategies, per deal, in pot units of the leaves.  sorted_showdowns: the leaves by
         rank order (RS_BR_SORTED: O(n log n) per run-out, equal to the pair loop of cfr.rs:323-347 within f64 rounding).  real: the responder plays the real game
         (RS_BR_REAL: an info set is the board seen so far and its own two cards) instead of the abstraction -- never the smaller number, and the one to compare abstractions by"""
-        return float(self.best_response(L.BR_MAX | (L.BR_SORTED if sorted_showdowns else 0) | (L.BR_REAL if real else 0)).sum() / 2.0)
+        return float(self.best_response(L.BR_MAX | (L.BR_SORTED if sorted_showdowns else 0) | (L.BR_REAL if real else 0), current=current).sum() / 2.0)
 
     def _download(self, ptr, dtype, count):
         out = np.empty(count, dtype=dtype)
@@ -830,6 +841,77 @@ class DealTrainer:
             self.infosets._h = None
             L.load().rs_deal_trainer_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _range_cfr_params(rmplus, sorted_showdowns):
+    p = L.RangeCfrParams()
+    p.mode = L.UPD_RMPLUS if rmplus else 0
+    p.sorted = L.FORM_ON if sorted_showdowns else L.FORM_OFF
+    return p
+
+
+def _dcfr_arg(dcfr):
+    if dcfr is None or dcfr is False:
+        return None
+    return C.byref(dcfr_params() if dcfr is True else dcfr)
+
+
+class RangeCFR:
+    """Full-width CFR over hand ranges (rs_range_cfr): chance-enumerated, vector-form sweeps of the game best_response_rounds measures, on an F32 table -- the same
+    arguments: board0 (3, 4 or 5 cards), the two ranges, clusters[r][p] = uint32 [prefixes of round r][n_hands_p].  The table and the tree must outlive the object.
+    The update rule (plain or regret matching+) is a property of the C object: one is created at construction (`rmplus`), the other on the first call that asks for it."""
+
+    def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True):
+        self.table, self.tree = table, tree
+        self._b = np.ascontiguousarray(board0, dtype=np.uint8)
+        self._h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
+        self._h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
+        self._cl = [np.ascontiguousarray(clusters[r][p], dtype=np.uint32) for r in range(len(clusters)) for p in (0, 1)]
+        self._sorted, self._rmplus, self._hs = bool(sorted_showdowns), bool(rmplus), {}
+        self._handle(self._rmplus)
+
+    def _handle(self, rmplus):
+        rmplus = self._rmplus if rmplus is None else bool(rmplus)
+        if rmplus not in self._hs:
+            arr = (C.c_void_p * len(self._cl))(*[k.ctypes.data for k in self._cl])
+            h = C.c_void_p()
+            L.check(L.load().rs_range_cfr_create(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1), arr,
+                                                 len(self._cl) // 2, C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
+            self._hs[rmplus] = h
+        self._last = self._hs[rmplus]
+        return self._last
+
+    def iterate(self, traverser, rmplus=None):
+        """one traverser's sweep; returns its value per deal under the current profile"""
+        v = C.c_double(0.0)
+        L.check(L.load().rs_range_cfr_iterate(self._handle(rmplus), int(traverser), C.byref(v)))
+        return v.value
+
+    def train(self, iterations, rmplus=None, dcfr=None):
+        """`iterations` iterations (traverser 0, then 1); dcfr: None, True (1.5, 0, 2, a tick per iteration) or dcfr_params(...).  Returns the last iteration's two values."""
+        out = np.zeros(2, dtype=np.float64)
+        L.check(L.load().rs_range_cfr_train(self._handle(rmplus), int(iterations), _dcfr_arg(dcfr), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    @property
+    def nbytes(self):
+        """device bytes held: the prepared game and, from the first sweep on, the workspace"""
+        return sum(int(L.load().rs_range_cfr_bytes(h)) for h in self._hs.values())
+
+    def launches(self):
+        """kernel launches of the last sweep under the level plan, -1 after a depth-first one"""
+        return int(L.load().rs_range_cfr_launches(self._last))
+
+    def destroy(self):
+        for h in getattr(self, "_hs", {}).values():
+            L.load().rs_range_cfr_destroy(h)
+        self._hs = {}
 
     def __del__(self):
         try:
