@@ -1,9 +1,11 @@
 """GPU (-m gpu): full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT against the numpy restatement tests/np_range_cfr.py.
 
 Every comparison with the restatement is TEACHER-FORCED: its tables are uploaded, the device does one sweep, and the result is compared with the restatement's own next
-state -- rounding cannot build up.  A cell passes if it is within one f32 ulp of the restatement's or within ATOL absolutely (tests/test_range_cfr_cpu.py shows that
-two orders of the same sums are never further apart); at most 0.5 % of a case's cells may differ at all; cells a sweep must not touch are bit-equal to what was uploaded.
-The shapes are the smallest at which each branch of rs_br.hip's new kernels can go wrong (BrRun::own_kind: a wave per info set from 32 lanes per cluster on)."""
+state -- rounding cannot build up.  A cell passes if it is of the restatement's class (finite, +inf, -inf, NaN) and, where finite, within one f32 ulp of the restatement's
+or within ATOL absolutely (test_range_cfr_cpu.compare_cells; on well-behaved tables that file holds two orders of the same sums to one ulp with no ATOL, on edge
+tables to this rule); at most 0.5 % of a case's cells may differ at all; cells a sweep must not touch are bit-equal to what was uploaded.
+The shapes are the smallest at which each branch of rs_br.hip's new kernels can go wrong (BrRun::own_kind: a wave per info set from 32 lanes per cluster on);
+tests/test_gpu_range_cfr_edges.py goes on to list lengths at the kernels' steps, wide nodes, three rounds and tables of edge values."""
 import numpy as np
 import pytest
 
@@ -13,9 +15,9 @@ from oracle import np_br as nbr
 from oracle import np_restate as npr
 from rustsolver_amd import _lib as L
 from rustsolver_amd import abstraction as ab
-from test_gpu_br_pinned import GDT, MODES, TRAINER_CASES, close, depth_first, python_cluster_ids
+from test_gpu_br_pinned import GDT, MODES, TRAINER_CASES, close, depth_first, edge_sums, python_cluster_ids
 from test_np_br_cpu import ATOL, RIVER, RTOL, TURN, combos_of, lane_cids, pick_ranges, random_cids, sizes_of
-from test_range_cfr_cpu import RIVER_TREE, TURN_TREE, random_tables, ulps_apart
+from test_range_cfr_cpu import RIVER_TREE, TURN_TREE, adopt_tree, compare_cells, random_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +76,8 @@ def make_case(name):
 
 
 CASES = ["river_lanes", "river_wave_35", "river_runs_8_9", "turn_imperfect_recall", "turn_lanes", "river_unused_cluster", "turn_one_hand", "turn_no_opponent"]
+# the form of the LAST round's own nodes per player (wave per info set?).  turn_lanes' first round (9 and 7 info sets over 48 run-outs) is in the wave form all the
+# same; test_gpu_range_cfr_edges.FORMS keys the forms per (round, player)
 WAVE = {"river_wave_35": (True, True), "turn_imperfect_recall": (True, True), "river_lanes": (False, False), "turn_lanes": (False, False), "river_runs_8_9": (False, False)}
 
 
@@ -82,7 +86,11 @@ class Device:
 
     def __init__(self, board0, h, cids, sizes, tree, dtype=L.F32):
         self.board0, self.h, self.cids = board0, h, cids
-        self.n_actions, self.tree = rs.build_game_tree(rs.Options(n_board_cards=len(board0), bet_sizes=tree[0], raise_sizes=tree[1]))
+        if max(len(x) for x in tree[0] + tree[1]) <= L.MAX_SIZES:
+            self.n_actions, self.tree = rs.build_game_tree(rs.Options(n_board_cards=len(board0), bet_sizes=tree[0], raise_sizes=tree[1]))
+        else:                                        # rs_options holds no more sizes per round: the restated tree, adopted
+            self.tree = adopt_tree(npr.build_tree(n_board_cards=len(board0), bet_sizes=tree[0], raise_sizes=tree[1])[0])
+            self.n_actions = self.tree.n_action_nodes
         self.table = rs.create_infosets(self.n_actions, self.tree, sizes, [1] * len(cids), dtype=dtype)
         self.solvers = {}
 
@@ -117,8 +125,8 @@ def same_tables(a, b):
 
 
 def compare_sweep(nodes, game, cids, p, before, got, want, what):
-    """cells of `got` (device) against `want` (restatement) after one sweep of traverser p from `before`; returns (cells, cells that differ at all)"""
-    cells = differ = 0
+    """cells of `got` (device) against `want` (restatement) after one sweep of traverser p from `before`; returns (cells, cells that differ at all, largest ulp distance of two cells further apart than ATOL)"""
+    cells = differ = worst = 0
     for nd in nodes:
         if nd["kind"] != "action":
             continue
@@ -130,12 +138,11 @@ def compare_sweep(nodes, game, cids, p, before, got, want, what):
         for k in (0, 1):
             g, w, b = got[k][i], want[k][i], before[k][i]
             assert g[:, ~used].tobytes() == b[:, ~used].tobytes(), (what, "a cell the sweep must not touch changed", i, k)
-            d = ulps_apart(g[:, used], w[:, used])
-            ok = (d <= 1) | (np.abs(g[:, used].astype(np.float64) - w[:, used].astype(np.float64)) <= ATOL)
-            assert ok.all(), (what, i, k, int(d.max()))
+            d, far = compare_cells(g[:, used], w[:, used], (what, i, k))
             cells += d.size
             differ += int((d > 0).sum())
-    return cells, differ
+            worst = max(worst, int(far.max()) if d.size else 0)
+    return cells, differ, worst
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -165,7 +172,7 @@ def test_one_sweep_equals_the_restatement(name):
                     got_value = dev.solver(rmplus, sorted_showdowns).iterate(p)
                     got = dev.download()
                     assert np.isclose(got_value, value, rtol=RTOL, atol=ATOL), (what, got_value, value)
-                    c, d = compare_sweep(nodes, game, cids, p, before, got, want, what)
+                    c, d, _ = compare_sweep(nodes, game, cids, p, before, got, want, what)
                     cells, differ = cells + c, differ + d
                     if sorted_showdowns:             # determinism: the same call from the same tables
                         dev.upload(*before)
@@ -326,7 +333,7 @@ def test_deal_trainer_trains_full_width_on_its_own_game():
         got = tables()
         for p, (b, w) in enumerate(((mid, after0), (after0, want))):         # traverser p's nodes are written by sweep p alone
             own = [nd for nd in nodes if nd["kind"] == "action" and nd["player"] == p]
-            c, d = compare_sweep(own, game, cids, p, b, got, w, ("trainer", it, p))
+            c, d, _ = compare_sweep(own, game, cids, p, b, got, w, ("trainer", it, p))
             cells, differ = cells + c, differ + d
     assert cells > 0 and differ <= 0.005 * cells, (differ, cells)
     assert tr.iterations == done
@@ -340,10 +347,9 @@ def test_deal_trainer_trains_full_width_on_its_own_game():
     tr.destroy()
 
 
-@pytest.mark.parametrize("name", sorted(TRAINER_CASES))
-def test_br_current_reads_get_strategy_of_the_regrets(name):
-    """random regrets on the trainer's table: all four modes | RS_BR_CURRENT against np_br fed with get_strategy of the regrets; the modes without the bit return the same
-    bits before and after"""
+def br_current_case(name, draw):
+    """regrets from draw(rng, shape, dtype) on the trainer's table: all four modes | RS_BR_CURRENT against np_br fed with get_strategy of the regrets as stored; the modes
+    without the bit return the same bits before and after.  Returns the values with the bit"""
     tr, tree, nodes, board0, ranges, cids, sizes, dtype = trainer_game(name)
     tr.train(2)
     tr.status()
@@ -351,19 +357,17 @@ def test_br_current_reads_get_strategy_of_the_regrets(name):
     sig = {}
     for nd in tree.action_nodes():
         R, S = tr.infosets.download_node(nd.index)
-        if dtype == "i32":
-            Rn = rng.integers(-1000, 1000, R.shape).astype(np.int32)
-        else:
-            Rn = np.round(rng.standard_normal(R.shape) * 30.0, 1).astype(np.float32)
-        tr.infosets.upload_node(nd.index, Rn, S)
+        tr.infosets.upload_node(nd.index, draw(rng, R.shape, dtype), S)
         Rn, _ = tr.infosets.download_node(nd.index)              # as stored (binary16 cells round)
-        sig[nd.index] = npr.get_strategy(Rn) if dtype == "i32" else npr.get_strategy_f32(Rn)
+        with np.errstate(over="ignore", invalid="ignore"):
+            sig[nd.index] = npr.get_strategy(Rn) if dtype == "i32" else npr.get_strategy_f32(Rn)
     plain = {m: tr.best_response(m) for m in MODES}
     game = nbr.Game(board0, ranges)
     want = {"max": nbr.best_response(nodes, sig.__getitem__, board0, ranges, cids, "max", None, game),
             "avg": nbr.best_response(nodes, sig.__getitem__, board0, ranges, cids, "avg", None, game)}
+    out = {}
     for m in MODES:
-        got = tr.best_response(m | L.BR_CURRENT)
+        got = out[m] = tr.best_response(m | L.BR_CURRENT)
         close(got, want["avg" if m & 0xff == L.BR_AVERAGE else "max"], (name, m))
         assert tr.best_response(m, current=True).tobytes() == got.tobytes()
         assert got.tobytes() != plain[m].tobytes()
@@ -373,3 +377,25 @@ def test_br_current_reads_get_strategy_of_the_regrets(name):
     for m in MODES:
         assert tr.best_response(m).tobytes() == plain[m].tobytes()
     tr.destroy()
+    return out
+
+
+def random_regrets(rng, shape, dtype):
+    if dtype == "i32":
+        return rng.integers(-1000, 1000, shape).astype(np.int32)
+    return np.round(rng.standard_normal(shape) * 30.0, 1).astype(np.float32)
+
+
+@pytest.mark.parametrize("name", sorted(TRAINER_CASES))
+def test_br_current_reads_get_strategy_of_the_regrets(name):
+    """random regrets on the trainer's table: all four modes | RS_BR_CURRENT against np_br fed with get_strategy of the regrets; the modes without the bit return the same
+    bits before and after"""
+    br_current_case(name, random_regrets)
+
+
+@pytest.mark.parametrize("name", sorted(TRAINER_CASES))
+def test_br_current_reads_get_strategy_of_edge_regrets(name):
+    """the regret reader where test_gpu_br_pinned.edge_sums pins the strategy-sum reader: i32 cells around 2^24, at INT_MAX and INT_MIN (`as f32`), f32 columns whose
+    positive sum overflows (they play nothing), binary16 cells of 65 504 added in f32, subnormals, -0.0 and NaN (not positive).  No +inf cell: every value is finite"""
+    out = br_current_case(name, edge_sums)
+    assert all(np.isfinite(v).all() for v in out.values()), out
