@@ -1147,14 +1147,19 @@ __global__ __launch_bounds__(kBrBlock) void k_br_opp_reach(const void *__restric
 // (level plan) The strategy-sum rows are gathered by cluster id, and a lossless abstraction numbers its clusters hand by hand: workgroups go round the eight XCDs in turn, so
 // workgroup x takes hands of slice x % 8 only (every run-out of them) -- an XCD's L2 then sees an eighth (with the suit-swapped twins: a quarter) of the node's rows instead of
 // all of them (the river's 7.7 MB per node against 4 MB of L2: 250 MB fetched per node, profiles/r05_br.md).  gridDim.x = 8 * ceil(run-outs * ceil(n_hands / 8) / kBrBlock).
+// The thread's lane h of the n = run-outs * n_hands; false: it has none (the slice is empty -- fewer than eight hands -- or the thread is past its end).
+__device__ __forceinline__ bool br_xcd_sliced_lane(uint32_t n, uint32_t n_hands, uint32_t &h) {
+    const uint32_t xcd = blockIdx.x & 7u, w = blockIdx.x >> 3, per = (n_hands + 7u) / 8u, lo = xcd * per;
+    if (lo >= n_hands) return false;
+    const uint32_t hs = min(per, n_hands - lo), idx = w * kBrBlock + threadIdx.x, b = idx / hs;
+    h = b * n_hands + lo + (idx - b * hs);
+    return h < n && b < n / n_hands;
+}
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_opp_reach_jobs(const void *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad, uint32_t n_hands) {
     const BrJob j = jobs[blockIdx.y];
-    const uint32_t xcd = blockIdx.x & 7u, w = blockIdx.x >> 3, per = (n_hands + 7u) / 8u, lo = xcd * per;
-    if (lo >= n_hands) return;
-    const uint32_t hs = min(per, n_hands - lo), idx = w * kBrBlock + threadIdx.x, b = idx / hs;
-    const uint32_t h = b * n_hands + lo + (idx - b * hs);
-    if (h >= n || b >= n / n_hands) return;
+    uint32_t h;
+    if (!br_xcd_sliced_lane(n, n_hands, h)) return;
     float sig[RS_MAX_ACTIONS];
     final_sigma<DT>(ssum, j.row.cell_off, j.row.pitch, j.row.n_actions, j.cid[h], sig);
     const double qh = j.q[h];
@@ -1238,11 +1243,8 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_reach(const void *__restric
 // (level plan) sliced over the XCDs by hand as k_br_opp_reach_jobs: the regret rows are gathered by cluster id just as the strategy sums are there
 __global__ __launch_bounds__(kBrBlock) void k_br_own_reach_jobs(const void *__restrict__ regrets, const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad, uint32_t n_hands) {
     const BrJob j = jobs[blockIdx.y];
-    const uint32_t xcd = blockIdx.x & 7u, w = blockIdx.x >> 3, per = (n_hands + 7u) / 8u, lo = xcd * per;
-    if (lo >= n_hands) return;
-    const uint32_t hs = min(per, n_hands - lo), idx = w * kBrBlock + threadIdx.x, b = idx / hs;
-    const uint32_t h = b * n_hands + lo + (idx - b * hs);
-    if (h >= n || b >= n / n_hands) return;
+    uint32_t h;
+    if (!br_xcd_sliced_lane(n, n_hands, h)) return;
     br_own_reach_lane(regrets, j.row, j.cid, h, n_pad, j.q, j.q_out);
 }
 
@@ -1809,6 +1811,7 @@ struct BrRun {
         if (err == hipSuccess) err = done;
         return err == hipSuccess ? RS_OK : hip_fail(err, ws_levels ? "rs_best_response (level plan)" : "rs_best_response");
     }
+    int traverse(int traverser, std::vector<double> &root, double *total);
 };
 
 // run-outs of an initial board in the enumeration order of the lanes: the first new card most significant, cards ascending among those still in the deck
@@ -2181,8 +2184,6 @@ static int br_check_mode(int mode /* without RS_BR_SORTED, RS_BR_REAL and RS_BR_
 // the walk's workspace: allocated by the first walk and kept with the object (see br_execute)
 static int br_ensure_workspace(BrRun &run) {
     if (run.ws) return RS_OK;
-    rs_table *t = run.t;
-    (void)t;
     const size_t need = std::max(run.level_plan_bytes(0), run.level_plan_bytes(1));
     size_t free_b = 0, total_b = 0;
     const bool levels = !knobs_resolve(nullptr).br_depth_first && need <= kBrLevelPlanBytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
@@ -2206,6 +2207,21 @@ static int br_ensure_workspace(BrRun &run) {
     return RS_OK;
 }
 
+// One traverser's pass over the table as it stands, in the tree order of the workspace (allocated here by the first pass): its launches are added to last_launches (level
+// plan), *total is the sum of the root's values, ascending like the oracle's.  root holds n_pad_max doubles.
+int BrRun::traverse(int traverser, std::vector<double> &root, double *total) {
+    if (int rc = br_ensure_workspace(*this)) return rc;
+    last_level_plan = ws_levels;
+    p = traverser;
+    if (cfr) ++t->epoch;   // whatever happens below, rows may have been written
+    if (int rc = run_traverser(root.data())) return rc;
+    last_launches += ws_levels ? n_launches : 0;
+    double sum = 0.0;
+    for (uint32_t l = 0; l < side[p].n; ++l) sum += root[l];
+    *total = sum;
+    return RS_OK;
+}
+
 // the walk: both traversers against the table as it stands
 int br_execute(BrRun *prepared, int mode, double *out) {
     if (!prepared || !out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
@@ -2225,18 +2241,10 @@ int br_execute(BrRun *prepared, int mode, double *out) {
     // and buys launches, not kernel time (4 300 -> 66 per call; at full ranges both orders spend 0.24-0.27 s in their kernels): it is taken while it fits kBrLevelPlanBytes and half
     // of the free memory, else the depth-first walk runs with its two buffers per tree depth.  The workspace is allocated by the first call and KEPT with the object
     // (br_workspace_bytes / br_release_workspace: a trainer holds one object per showdown mode).
-    if (int rc = br_ensure_workspace(run)) return rc;
-    run.last_level_plan = run.ws_levels;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
-    for (int p = 0; p < 2; ++p) {
-        run.p = p;
-        if (int rc = run.run_traverser(root.data())) return rc;
-        run.last_launches += run.ws_levels ? run.n_launches : 0;
-        double total = 0.0;
-        for (uint32_t l = 0; l < run.side[p].n; ++l) total += root[l];   // ascending, like the oracle
-        out[p] = total;
-    }
+    for (int p = 0; p < 2; ++p)
+        if (int rc = run.traverse(p, root, &out[p])) return rc;
     return RS_OK;
 }
 
@@ -2268,16 +2276,10 @@ int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
             run.d_pi0[p] = run.upload(ones);
             if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr: the root reach");
         }
-    if (int rc = br_ensure_workspace(run)) return rc;
-    run.last_level_plan = run.ws_levels;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
-    run.p = traverser;
-    ++t->epoch;   // whatever happens below, rows may have been written
-    if (int rc = run.run_traverser(root.data())) return rc;
-    run.last_launches = run.ws_levels ? run.n_launches : 0;
     double total = 0.0;
-    for (uint32_t l = 0; l < run.side[traverser].n; ++l) total += root[l];   // ascending, as br_execute
+    if (int rc = run.traverse(traverser, root, &total)) return rc;
     if (value) *value = total;
     return RS_OK;
 }
