@@ -48,7 +48,8 @@ extern "C" {
                                  still 6: Discounted CFR (rs_dcfr_params, rs_dcfr_params_default, rs_dcfr_factors, rs_discount_dcfr, rs_train_dcfr, rs_solver_dcfr_fused,
                                  rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning;
                                  still 6: RS_BR_REAL (a mode bit of rs_best_response, rs_best_response_rounds, rs_deal_trainer_best_response) -- modes without it mean what they meant;
-                                 still 6: full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT, a mode bit of the same three -- additions only */
+                                 still 6: full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT, a mode bit of the same three -- additions only;
+                                 still 6: the node report (rs_node_report_size, rs_node_report, rs_deal_trainer_node_report) -- additions only */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -246,6 +247,28 @@ int rs_best_response(rs_table *table, const rs_tree *tree, const uint8_t *board,
 int rs_best_response_rounds(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
                             const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, int mode, double *out /*[2]*/);
 size_t rs_br_runouts(const uint8_t *board0, int n_board0, uint8_t *out_cards /* [NB][5], may be NULL */);
+
+/* ---- node report: per-hand values, reach and mass at chosen tree nodes (an extension) -----------------
+ * The range and EV view of a node, and the inputs of a subgame re-solve: what RS_BR_AVERAGE's walk of rs_best_response_rounds -- same arguments, lanes (run-out b, hand h),
+ * deal weights, leaves and cluster tables -- holds at the requested action nodes for ONE traverser p, both players playing the strategy the mode names: RS_BR_AVERAGE
+ * (get_final_strategy of the strategy sums) or RS_BR_AVERAGE | RS_BR_CURRENT (get_strategy of the regrets), RS_BR_SORTED optional; every other mode is RS_ERR_INVALID.
+ * The traverser's own reach pi (1.0 at the root, times sigma[a][cluster of the lane] at its own nodes) goes down beside the opponent's reach q.  For a node n of round r,
+ * acted by either player, the rows are indexed by (prefix f of round r, hand h of p); a pair whose hand holds a card of the prefix has 0.0 in every row:
+ *   cfv[a][f][h]  the sum of child a's value row over the run-outs of prefix f, ascending from 0.0, lanes that are no deal not added (RS_BR_REAL's fold).  At an
+ *                 opponent's node child a's row already carries the opponent's probability of a;
+ *   v[f][h]       the same fold of the node's own value row: sum_a sigma[a] * vch[a] (a ascending from 0.0) at an own node, the children summed in action order at an
+ *                 opponent's;
+ *   mass[f][h]    the same fold of pw[lane] * (sum of q_n[b][h_o] over the opponent hands that share no card with h or the run-out), q_n the opponent's reach at n: an
+ *                 uncontested leaf of value 1.0 evaluated at the node, in the leaf order of the showdown mode.  cfv[a] / mass is the action's value in chips given that the
+ *                 hand is there;
+ *   own[f][h]     pi on the lowest run-out of the prefix on which (b, h) is a deal (pi is constant over them), 0.0 if there is none.
+ * f64; every sum has one order, whichever tree order or kernel form ran.  `nodes` are tree node ids (rs_tree_get_node); RS_ERR_INVALID for an id that is out of range, no
+ * action node or repeated, and for an out_doubles that is too small.  Node k's block starts at offsets[k] doubles and holds (A + 3) rows [prefixes of its round][n_hands of the
+ * traverser]: cfv[0 .. A), v, mass, own.  rs_node_report_size returns the total number of doubles (0 with rs_last_error set on bad arguments).  Every table type; a training
+ * loop's working copy is settled first; writes nothing to the table; a refused call leaves `out` alone; synchronises. */
+size_t rs_node_report_size(const rs_tree *tree, int n_board0, size_t n_hands_traverser, const int32_t *nodes, size_t n_nodes, uint64_t *offsets /* [n_nodes], may be NULL */);
+int rs_node_report(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
+                   const uint32_t *const *cluster, int n_rounds, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
 
 /* One traverser visit of every lane of `node` (cfr.rs:370-466 / :571-623):
  *   sigma = get_strategy(); util = sum_a utils[a]*sigma[a]; regrets / strategy_sum updated with
@@ -631,6 +654,9 @@ int rs_deal_trainer_range_cfr(rs_deal_trainer *trainer, uint64_t iterations, con
 /* The best-response objects a trainer keeps between calls (one per showdown mode: the game-only index, and the walk's workspace -- a buffer per tree edge while that stays
  * below 16 GB, two per tree depth otherwise): the device bytes they hold, a call that gives the workspaces back (the next best response allocates them again), and the kernel
  * launches the last call made (-1: the depth-first walk ran, one or two launches per tree node). */
+/* rs_node_report on the trainer's own tree, ranges, board and cached cluster tables.  The prepared game and the workspace are the objects rs_deal_trainer_best_response
+ * keeps for the showdown mode (counted by rs_deal_trainer_br_bytes, given back by rs_deal_trainer_br_release); a workspace that lacks the report's rows grows. */
+int rs_deal_trainer_node_report(rs_deal_trainer *trainer, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
 size_t rs_deal_trainer_br_bytes(const rs_deal_trainer *trainer);
 int rs_deal_trainer_br_release(rs_deal_trainer *trainer);
 int rs_deal_trainer_br_launches(const rs_deal_trainer *trainer, int sorted);

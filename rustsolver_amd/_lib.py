@@ -254,6 +254,9 @@ SYMBOLS = {
     "rs_showdown_sign": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rs_best_response_rounds": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "rs_br_runouts": (C.c_size_t, [_P, C.c_int, _P]),
+    "rs_node_report_size": (C.c_size_t, [_P, C.c_int, C.c_size_t, _P, C.c_size_t, _P]),
+    "rs_node_report": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
+    "rs_deal_trainer_node_report": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
     "rs_kmeans_init_s": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "rs_kmeans_pick_restart": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     "rs_kmeans_reassign": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -602,6 +602,8 @@ struct BrJob {
     uint32_t sum_n[RS_MAX_ACTIONS];          // from sum_src[a]) -- added up while the rows are staged instead of written by k_br_sum_jobs and read again; 0: child a's row is vch + a * n_pad
     const uint32_t *tord, *perm;   // own node by columns (k_br_own_cols_jobs): [kmax][n_sets] the k-th lane of the i-th info set, and which cluster that info set is
     uint32_t n_sets, kmax;
+    // a report job (kBrReport) reads its node's vch and v, q = the traverser's own reach that came in, sum_src[0] = the node's mass row (written by the kBrMass job before it,
+    // a leaf job: q = the opponent's reach at the node, uncontested, value 1.0), and writes q_out = the node's block of the call's output buffer
 };
 // The level plan's form (round 5): ONE workgroup per run-out takes every leaf of the tree in turn.  What the leaves share -- the run-out's rank order, the holders of every
 // card, where each of the traverser's hands stands in that order, its weight -- is read ONCE (25 KB per run-out and side; the one-leaf kernel above read it again at each of the
@@ -1226,26 +1228,31 @@ __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards_jobs(const uint
 //     v[lane]      = sum_a (double)sigma[a][c(lane)] * vch[a][lane], a ascending from 0.0       (RS_BR_AVERAGE's expression with the current strategy)
 // sigma read from the regret row before it is written; every row written once per sweep.  Every addition has ONE order whatever form or tree order runs it.
 // own node on the way down: pi_a[lane] = pi[lane] * sigma(cluster(lane), a).  (A lane that is no deal looks cluster 0 up, as the opponent's reach does: no list holds it.)
+// The node report (rs_node_report) takes pi down the same way on every table type, handed the array its mode reads: get_strategy and get_final_strategy are one text.
+template <int DT>
 __device__ __forceinline__ void br_own_reach_lane(const void *__restrict__ regrets, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t h, uint32_t n_pad,
                                                   const double *__restrict__ pi, double *__restrict__ pi_out /*[A][n_pad]*/) {
-    float r[RS_MAX_ACTIONS], sig[RS_MAX_ACTIONS];
-    current_sigma<kDT_F32>(regrets, row.cell_off, row.pitch, row.n_actions, cid[h], r, sig);
+    typename Elem<DT>::val r[RS_MAX_ACTIONS];
+    float sig[RS_MAX_ACTIONS];
+    current_sigma<DT>(regrets, row.cell_off, row.pitch, row.n_actions, cid[h], r, sig);
     const double ph = pi[h];
 #pragma unroll
     for (int a = 0; a < RS_MAX_ACTIONS; a++)
         if ((uint32_t)a < row.n_actions) pi_out[(size_t)a * n_pad + h] = ph * (double)sig[a];
 }
+template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_own_reach(const void *__restrict__ regrets, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
                                                            const double *__restrict__ pi, double *__restrict__ pi_out) {
     const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
-    if (h < n) br_own_reach_lane(regrets, row, cid, h, n_pad, pi, pi_out);
+    if (h < n) br_own_reach_lane<DT>(regrets, row, cid, h, n_pad, pi, pi_out);
 }
 // (level plan) sliced over the XCDs by hand as k_br_opp_reach_jobs: the regret rows are gathered by cluster id just as the strategy sums are there
+template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_own_reach_jobs(const void *__restrict__ regrets, const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad, uint32_t n_hands) {
     const BrJob j = jobs[blockIdx.y];
     uint32_t h;
     if (!br_xcd_sliced_lane(n, n_hands, h)) return;
-    br_own_reach_lane(regrets, j.row, j.cid, h, n_pad, j.q, j.q_out);
+    br_own_reach_lane<DT>(regrets, j.row, j.cid, h, n_pad, j.q, j.q_out);
 }
 
 // the row writes of one info set: U from the sums, then regret and strategy-sum cells of every action
@@ -1370,12 +1377,102 @@ __global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave_jobs(float *__rest
     br_cfr_own_wave_body(regrets, ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, j.q, rmplus, j.v);
 }
 
+// ---- the node report (rs_node_report): per (prefix of the node's round, hand) what RS_BR_AVERAGE's walk holds at a requested node ------------------------------------
+// k_br_own_real_cols / _last's fold with the sums kept instead of compared: A + 2 lane rows -- the children's values vch[a], the node's own value row, the mass row (an
+// uncontested leaf of value 1.0 on the node's q: the kBrMass job before this one) -- are added up over the run-outs of the pair's prefix, ascending from 0.0, lanes that are
+// no deal not added; the last row is the traverser's own reach pi on the pair's first deal.  out: [A + 3][n_pairs], rows cfv[0 .. A), v, mass, own.
+// Under RS_BR_AVERAGE no own node folds its opponent children (BrPlan's `folds`), so every child row and the node's own row stand written when the report runs: plain rows.
+// A workgroup takes 64 neighbouring pairs (neighbouring threads neighbouring hands) and its four waves share the ROWS: each row's additions stay sequential down the
+// run-outs, eight loads in flight.  Nothing is indexed by the action: a row is a pointer picked under a predicate, the sums never meet.
+__device__ __forceinline__ const double *br_report_row(uint32_t row, uint32_t n_actions, uint32_t n_pad, const double *__restrict__ vch, const double *__restrict__ v,
+                                                       const double *__restrict__ mass) {
+    return row < n_actions ? vch + (size_t)row * n_pad : (row == n_actions ? v : mass);
+}
+__device__ __forceinline__ void br_report_cols_body(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs, uint32_t pp,
+                                                    uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v,
+                                                    const double *__restrict__ mass, const double *__restrict__ pi, double *__restrict__ out) {
+    const uint32_t x = threadIdx.x & 63u, w = threadIdx.x >> 6, pair = blockIdx.x * kBrRealPairs + x;
+    if (pair >= n_pairs) return;
+    const uint32_t f = pair / n_hands, h = pair - f * n_hands;
+    const uint64_t mine = mask_p[h];
+    const uint64_t *__restrict__ bm = bmask + (size_t)f * pp;
+    const uint32_t lane0 = f * pp * n_hands + h;   // run-out k of the pair: lane0 + k * n_hands (below n < 2^31)
+    for (uint32_t row = w; row < n_actions + 3; row += kBrRealWaves) {
+        if (row == n_actions + 2) {   // own: pi is constant over the deals of a prefix, the lowest run-out speaks; 0.0 where the pair is no deal at all
+            double own = 0.0;
+            for (uint32_t k = 0; k < pp; k++)
+                if (!(mine & bm[k])) {
+                    own = pi[lane0 + k * n_hands];
+                    break;
+                }
+            out[(size_t)row * n_pairs + pair] = own;
+            continue;
+        }
+        const double *__restrict__ src = br_report_row(row, n_actions, n_pad, vch, v, mass);
+        double acc = 0.0;
+        for (uint32_t k = 0; k < pp; k += kBrRealFlight) {
+            bool deal[kBrRealFlight];
+            double t[kBrRealFlight];
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++) {
+                const uint32_t kk = min(k + q, pp - 1);
+                deal[q] = k + q < pp && !(mine & bm[kk]);
+                t[q] = src[lane0 + kk * n_hands];
+            }
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++)
+                if (deal[q]) acc += t[q];   // ascending run-outs, one after the other
+        }
+        out[(size_t)row * n_pairs + pair] = acc;
+    }
+}
+// the last round (one run-out per prefix): a pair is a lane, the fold one addition to 0.0 -- element-wise, every row read once and written once
+__device__ __forceinline__ void br_report_last_body(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
+                                                    uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v, const double *__restrict__ mass,
+                                                    const double *__restrict__ pi, double *__restrict__ out) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    const uint32_t b = lane / n_hands, h = lane - b * n_hands;
+    const bool deal = !(mask_p[h] & bmask[b]);
+    double t[RS_MAX_ACTIONS + 3];
+#pragma unroll
+    for (int row = 0; row < RS_MAX_ACTIONS + 2; row++)   // every row's value on its way before the first store
+        t[row] = (uint32_t)row < n_actions + 2 ? br_report_row((uint32_t)row, n_actions, n_pad, vch, v, mass)[lane] : 0.0;
+    const double own = pi[lane];
+#pragma unroll
+    for (int row = 0; row < RS_MAX_ACTIONS + 2; row++)
+        if ((uint32_t)row < n_actions + 2) out[(size_t)row * n + lane] = deal ? 0.0 + t[row] : 0.0;
+    out[(size_t)(n_actions + 2) * n + lane] = deal ? own : 0.0;
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_report_cols(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
+                                                             uint32_t pp, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v,
+                                                             const double *__restrict__ mass, const double *__restrict__ pi, double *__restrict__ out) {
+    br_report_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, n_actions, vch, v, mass, pi, out);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_report_cols_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
+                                                                  uint32_t pp, uint32_t n_pad, const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_report_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, jp->n_children, jp->vch, jp->v, jp->sum_src[0], jp->q, jp->q_out);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_report_last(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
+                                                             uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v, const double *__restrict__ mass,
+                                                             const double *__restrict__ pi, double *__restrict__ out) {
+    br_report_last_body(mask_p, bmask, n_hands, n, n_pad, n_actions, vch, v, mass, pi, out);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_report_last_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
+                                                                  uint32_t n_pad, const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_report_last_body(mask_p, bmask, n_hands, n, n_pad, jp->n_children, jp->vch, jp->v, jp->sum_src[0], jp->q, jp->q_out);
+}
+
 // What a node asks of the device.  The kinds stand in the order of their launches within a tree depth -- reach on the way down, values on the way up -- which traces and
 // br_launches() show.  A new own-node form is a body, a kind here, a line in BrRun::own_kind and a case in BrRun::launch.
-// (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up)
-enum BrKind { kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread, kBrSum, kBrKinds };
+// (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up; the node report: kBrReachOwn on the way down, and after the value
+// job of a requested node kBrMass -- the leaf kernels on the node's q -- and kBrReport)
+enum BrKind { kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread, kBrSum, kBrMass,
+              kBrReport, kBrKinds };
 // launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
-static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal; }
+static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal || k == kBrReport; }
 // P, Pc, O and Q of br_terminal_sorted_body
 static size_t br_sorted_leaf_lds(uint32_t n_o) { return (size_t(n_o) * 2 + 52 * kBrCardHolders + 65) * sizeof(double); }
 // a wave per info set (k_br_own_wave_jobs), where info sets hold many lanes
@@ -1418,10 +1515,18 @@ struct BrRun {
     bool current = false;          // RS_BR_CURRENT (this call): get_strategy of the regrets where the walk reads a strategy
     bool cfr = false;              // the object is a full-width solver's (br_cfr_sweep): pi buffers in the workspace, own nodes go to k_br_cfr_own*
     int cfr_rmplus = 0;            // ... RS_UPD_RMPLUS of the sweep in flight
-    double *d_pi0[2] = {nullptr, nullptr};    // ... the traverser's own reach at the root: 1.0 on every lane
+    double *d_pi0[2] = {nullptr, nullptr};    // ... the traverser's own reach at the root: 1.0 on every lane (the node report's as well)
+    const std::vector<int> *report_slot = nullptr;   // the node report in flight (br_report): per tree node its place in the request, -1 = not asked for
+    const uint64_t *report_off = nullptr;     // ... where every requested node's block starts in d_report
+    double *d_report = nullptr;               // ... the call's output buffer on the device
+    bool ws_pi = false;                       // the workspace has the own-reach rows (a full-width solver's, or one a report has walked on)
+    size_t ws_mass_rows = 0;                  // ... and this many mass rows in the level plan (one per depth otherwise)
+    std::vector<double *> mass_level;         // ... per tree depth (depth-first walk)
+    bool takes_pi() const { return cfr || report_slot; }   // the traverser's own reach goes down beside q
     uint32_t per_prefix[RS_MAX_ROUNDS] = {1, 1, 1};   // run-outs under a prefix of round r
     int p = 0;
     uint32_t NB = 1;
+    int n_board0 = 5;              // cards of the initial board
     uint64_t *d_bmask = nullptr;
     BrSide side[2];
     std::vector<DevBuf<char>> allocs;
@@ -1438,6 +1543,9 @@ struct BrRun {
         q_level.clear();
         v_level.clear();
         pi_level.clear();
+        mass_level.clear();
+        ws_pi = false;
+        ws_mass_rows = 0;
         d_root = nullptr;
     }
     size_t n_pad_max = 0;
@@ -1472,12 +1580,12 @@ struct BrRun {
             if (n.kind == RS_NODE_ACTION) max_depth = std::max(max_depth, depth_of[id] + 1);
         }
     }
-    size_t level_plan_bytes(int pl) const {   // workspace of traverser pl's pass
+    size_t level_plan_bytes(int pl, bool pi, size_t mass_rows) const {   // workspace of traverser pl's pass
         const BrSide &me = side[pl], &op = side[1 - pl];
-        size_t doubles = me.n_pad;   // the root vector
+        size_t doubles = me.n_pad + mass_rows * me.n_pad;   // the root vector; a mass row per node a report asks for
         for (const rs_tree_node &n : tree->nodes)
-            if (n.kind == RS_NODE_ACTION && n.n_children > 0)   // children's values; an opponent node their reach as well, an own node of the full-width sweep their pi
-                doubles += size_t(n.n_children) * (size_t(me.n_pad) + (int(n.player) != pl ? size_t(op.n_pad) : (cfr ? size_t(me.n_pad) : 0)));
+            if (n.kind == RS_NODE_ACTION && n.n_children > 0)   // children's values; an opponent node their reach as well, an own node their pi (full-width sweep, node report)
+                doubles += size_t(n.n_children) * (size_t(me.n_pad) + (int(n.player) != pl ? size_t(op.n_pad) : (pi ? size_t(me.n_pad) : 0)));
         return doubles * sizeof(double);
     }
 
@@ -1503,7 +1611,8 @@ struct BrRun {
         std::vector<Entry> entries;
         std::vector<BrJob> jobs;           // jobs[i] is entries[i]'s
         std::vector<int> job_at, sum_at;   // per tree node: its job (leaf, own node, an opponent node's reach) and an opponent node's sum job, -1 = none
-        std::vector<int> own_reach_at;     // ... an own node's reach job (full-width sweep)
+        std::vector<int> own_reach_at;     // ... an own node's reach job (full-width sweep, node report)
+        std::vector<int> mass_at, report_at;   // ... a requested node's mass and report jobs (node report)
         double *root = nullptr;            // where the root's values arrive
     };
     // host only: gives every node its buffers and fills the jobs
@@ -1569,7 +1678,7 @@ struct BrRun {
                     j.kmax = me.kmax[r];
                 }
                 if (ws_levels && (kind == kBrOwnGrouped || kind == kBrOwnReal)) folds[id] = int(jobs.size());
-                if (cfr) {   // its children's pi on the way down; the update reads the pi that came in
+                if (takes_pi()) {   // its children's pi on the way down; the update (the report) reads the pi that came in
                     double *pch = ws_levels ? slot(size_t(n.n_children) * me.n_pad) : pi_level[size_t(d)];
                     BrJob jr{};
                     jr.row = j.row;
@@ -1606,6 +1715,23 @@ struct BrRun {
                 for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = qch + size_t(a) * op.n_pad, pi_in[size_t(n.children[a])] = pi_in[id];
             }
             for (int a = 0; a < n.n_children; ++a) v_out[size_t(n.children[a])] = vch + size_t(a) * me.n_pad;
+            if (report_slot && (*report_slot)[id] >= 0) {   // after the node's value job (kinds sort behind kBrSum within the node's step): its buffers are alive in both orders
+                double *mass = ws_levels ? slot(me.n_pad) : mass_level[size_t(d)];
+                BrJob jm{};
+                jm.q = q_in[id];
+                jm.v = mass;
+                jm.uncontested = 1;
+                jm.value = 1.0;
+                add(kBrMass, r, id, jm);
+                BrJob jr{};
+                jr.vch = vch;
+                jr.v = v_out[id];
+                jr.n_children = uint32_t(n.n_children);
+                jr.q = pi_in[id];
+                jr.sum_src[0] = mass;
+                jr.q_out = d_report + report_off[size_t((*report_slot)[id])];
+                add(kBrReport, r, id, jr);
+            }
         }
         // into launch order; within a launch the nodes keep the tree's order
         std::vector<uint32_t> perm(entries.size());
@@ -1614,11 +1740,14 @@ struct BrRun {
         pl.job_at.assign(N, -1);
         pl.sum_at.assign(N, -1);
         pl.own_reach_at.assign(N, -1);
+        pl.mass_at.assign(N, -1);
+        pl.report_at.assign(N, -1);
         pl.entries.reserve(perm.size());
         pl.jobs.reserve(perm.size());
         for (uint32_t i : perm) {
             const BrPlan::Entry &e = entries[i];
-            (e.kind == kBrSum ? pl.sum_at : (e.kind == kBrReachOwn ? pl.own_reach_at : pl.job_at))[size_t(e.node)] = int(pl.jobs.size());
+            std::vector<int> &at_of = e.kind == kBrSum ? pl.sum_at : (e.kind == kBrReachOwn ? pl.own_reach_at : (e.kind == kBrMass ? pl.mass_at : (e.kind == kBrReport ? pl.report_at : pl.job_at)));
+            at_of[size_t(e.node)] = int(pl.jobs.size());
             pl.entries.push_back(e);
             pl.jobs.push_back(jobs[i]);
         }
@@ -1663,10 +1792,14 @@ struct BrRun {
             break;
         }
         case kBrReachOwn: {
-            if (!d_jobs) hipLaunchKernelGGL(k_br_own_reach, dim3(grid1(me.n)), block, 0, s, ssum, j.row, j.cid, me.n, me.n_pad, j.q, j.q_out);
-            else hipLaunchKernelGGL(k_br_own_reach_jobs, dim3(8u * grid1(NB * ((me.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, me.n, me.n_pad, me.n_hands);
+            if (!d_jobs) hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own_reach), dim3(grid1(me.n)), block, 0, s, ssum, j.row, j.cid, me.n, me.n_pad, j.q, j.q_out);
+            else {
+                const auto k = RS_BR_PICK(t->dtype, k_br_own_reach_jobs);
+                hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((me.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, me.n, me.n_pad, me.n_hands);
+            }
             break;
         }
+        case kBrMass:   // the mass row of a requested node: the leaf kernels of the run's showdown mode on the node's q
         case kBrLeaf: {
             // (small ranges keep a workgroup per (run-out, leaf): the loop's scans are unrolled for 1 326 hands whatever the range holds -- 200 combos: 0.047 against 0.059 s per call)
             const uint32_t most_hands = std::max(me.n_hands, op.n_hands);
@@ -1769,6 +1902,17 @@ struct BrRun {
             if (!d_jobs) hipLaunchKernelGGL(k_br_sum, dim3(grid1(me.n)), block, 0, s, j.vch, j.n_children, me.n, me.n_pad, j.v);
             else hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), block, 0, s, d_jobs, me.n, me.n_pad);
             break;
+        case kBrReport: {
+            const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
+            const dim3 cols_grid((n_pairs + kBrRealPairs - 1) / kBrRealPairs, nj);
+            if (pp == 1 && !d_jobs)
+                hipLaunchKernelGGL(k_br_report_last, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v, j.sum_src[0], j.q, j.q_out);
+            else if (pp == 1) hipLaunchKernelGGL(k_br_report_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
+            else if (!d_jobs)
+                hipLaunchKernelGGL(k_br_report_cols, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, j.n_children, j.vch, j.v, j.sum_src[0], j.q, j.q_out);
+            else hipLaunchKernelGGL(k_br_report_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
+            break;
+        }
         case kBrKinds:   // a count, no kind
             return;
         }
@@ -1788,6 +1932,10 @@ struct BrRun {
         if (n.kind == RS_NODE_TERMINAL) return;
         for (int a = 0; a < n.n_children; ++a) walk(pl, n.children[a]);
         one(own ? pl.job_at[size_t(id)] : pl.sum_at[size_t(id)]);
+        if (pl.report_at[size_t(id)] >= 0) {   // node report: while the depth's buffers are this node's
+            one(pl.mass_at[size_t(id)]);
+            one(pl.report_at[size_t(id)]);
+        }
     }
 
     // one traverser's pass: the plan, the launches in the tree order the workspace was made for (the level plan after one upload of its jobs), the root's values back
@@ -1801,7 +1949,7 @@ struct BrRun {
             err = d_jobs.alloc(pl.jobs.size());
             if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, pl.jobs.data(), pl.jobs.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
             for (size_t lo = 0, hi; lo < pl.jobs.size() && err == hipSuccess; lo = hi) {
-                const size_t most = pl.entries[lo].kind == kBrLeaf ? 16384 : pl.jobs.size();
+                const size_t most = pl.entries[lo].kind == kBrLeaf || pl.entries[lo].kind == kBrMass ? 16384 : pl.jobs.size();
                 for (hi = lo + 1; hi < pl.jobs.size() && hi - lo < most && pl.entries[hi].key == pl.entries[lo].key; ++hi) {}
                 launch(pl.entries[lo].kind, pl.entries[lo].round, d_jobs + lo, uint32_t(hi - lo), &pl.jobs[lo]);
             }
@@ -2069,6 +2217,7 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
     run.tree = tree;
     run.sorted = sorted;
     run.NB = uint32_t(NB);
+    run.n_board0 = n_board0;
     for (int r = 0; r < RS_MAX_ROUNDS; ++r) run.per_prefix[r] = uint32_t(per_prefix[r]);
     run.d_bmask = run.upload(bmask);
     uint8_t *d_boards = run.upload(cards);
@@ -2182,25 +2331,34 @@ static int br_check_mode(int mode /* without RS_BR_SORTED, RS_BR_REAL and RS_BR_
 }
 
 // the walk's workspace: allocated by the first walk and kept with the object (see br_execute)
-static int br_ensure_workspace(BrRun &run) {
+// A node report wants more than a best response's walk left behind -- the traverser's own reach rows, a mass row per requested node (level plan) or depth -- and trades a
+// workspace that lacks them for a larger one; the walks that follow run on that (they take less of it).
+static int br_ensure_workspace(BrRun &run, size_t mass_rows = 0) {
+    const bool pi = run.takes_pi();
+    if (run.ws && ((pi && !run.ws_pi) || (run.ws_levels && mass_rows > run.ws_mass_rows) || (!run.ws_levels && mass_rows && run.mass_level.empty()))) run.release_workspace();
     if (run.ws) return RS_OK;
-    const size_t need = std::max(run.level_plan_bytes(0), run.level_plan_bytes(1));
+    const size_t need = std::max(run.level_plan_bytes(0, pi, mass_rows), run.level_plan_bytes(1, pi, mass_rows));
     size_t free_b = 0, total_b = 0;
     const bool levels = !knobs_resolve(nullptr).br_depth_first && need <= kBrLevelPlanBytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
     (void)hipGetLastError();
     if (levels && run.ws.alloc(need / sizeof(double), &run.dev_bytes) == hipSuccess) {
         run.ws_levels = true;
+        run.ws_pi = pi;
+        run.ws_mass_rows = mass_rows;
     } else {
         int max_a = 1;
         for (const rs_tree_node &n : run.tree->nodes) max_a = std::max(max_a, n.n_children);
         const int depth = run.max_depth;   // only action nodes take a level of child buffers
-        const size_t per = size_t(max_a) * run.n_pad_max, each = run.cfr ? 3 : 2;   // reach and values; the full-width sweep's own reach
-        if (run.ws.alloc(each * size_t(depth) * per + run.n_pad_max, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
+        const size_t per = size_t(max_a) * run.n_pad_max, each = pi ? 3 : 2;   // reach and values; the traverser's own reach (full-width sweep, node report)
+        const size_t mass = mass_rows ? size_t(depth) * run.n_pad_max : 0;            // a report's mass row per depth
+        if (run.ws.alloc(each * size_t(depth) * per + run.n_pad_max + mass, &run.dev_bytes) != hipSuccess) return fail(RS_ERR_OOM, "rs_best_response: the walk's buffers");
         run.ws_levels = false;
+        run.ws_pi = pi;
         for (int l = 0; l < depth; ++l) {
             run.q_level.push_back(run.ws + (each * size_t(l)) * per);
             run.v_level.push_back(run.ws + (each * size_t(l) + 1) * per);
-            if (run.cfr) run.pi_level.push_back(run.ws + (each * size_t(l) + 2) * per);
+            if (pi) run.pi_level.push_back(run.ws + (each * size_t(l) + 2) * per);
+            if (mass) run.mass_level.push_back(run.ws + each * size_t(depth) * per + run.n_pad_max + size_t(l) * run.n_pad_max);
         }
         run.d_root = run.ws + each * size_t(depth) * per;
     }
@@ -2210,7 +2368,7 @@ static int br_ensure_workspace(BrRun &run) {
 // One traverser's pass over the table as it stands, in the tree order of the workspace (allocated here by the first pass): its launches are added to last_launches (level
 // plan), *total is the sum of the root's values, ascending like the oracle's.  root holds n_pad_max doubles.
 int BrRun::traverse(int traverser, std::vector<double> &root, double *total) {
-    if (int rc = br_ensure_workspace(*this)) return rc;
+    if (int rc = br_ensure_workspace(*this, report_slot ? size_t(std::count_if(report_slot->begin(), report_slot->end(), [](int k) { return k >= 0; })) : 0)) return rc;
     last_level_plan = ws_levels;
     p = traverser;
     if (cfr) ++t->epoch;   // whatever happens below, rows may have been written
@@ -2248,6 +2406,90 @@ int br_execute(BrRun *prepared, int mode, double *out) {
     return RS_OK;
 }
 
+// ---- the node report on a prepared game ---------------------------------------------------------------------------------------------------------------------------
+// the root reach of the traverser's own lanes: 1.0 (full-width sweep, node report)
+static int br_root_reach(BrRun &run, const char *what) {
+    for (int p = 0; p < 2; ++p)
+        if (!run.d_pi0[p]) {
+            const std::vector<double> ones(run.side[p].n, 1.0);
+            run.d_pi0[p] = run.upload(ones);
+            if (run.err != hipSuccess) return hip_fail(run.err, what);
+        }
+    return RS_OK;
+}
+// blocks of the requested nodes: offsets[k] doubles into the output, (A + 3) rows of [prefixes of the node's round][n_hands]; 0 and rs_last_error on bad arguments
+static size_t br_report_layout(const rs_tree *tree, int n_board0, size_t n_hands, const int32_t *nodes, size_t n_nodes, uint64_t *offsets) {
+    const auto bad = [](const std::string &why) {
+        (void)fail(RS_ERR_INVALID, "rs_node_report: " + why);
+        return size_t(0);
+    };
+    if (!tree || !nodes || n_nodes == 0) return bad("NULL argument or no nodes");
+    if (n_board0 < 3 || n_board0 > 5) return bad("the initial board has 3, 4 or 5 cards");
+    if (n_hands == 0 || n_hands > 1326) return bad("1..1326 hands in the traverser's range");
+    const int K = 5 - n_board0, D = 52 - n_board0;
+    std::vector<char> seen(tree->nodes.size(), 0);
+    size_t total = 0;
+    for (size_t k = 0; k < n_nodes; ++k) {
+        const int32_t id = nodes[k];
+        if (id < 0 || size_t(id) >= tree->nodes.size()) return bad("node id " + std::to_string(id) + " is out of range");
+        const rs_tree_node &n = tree->nodes[size_t(id)];
+        if (n.kind != RS_NODE_ACTION) return bad("node " + std::to_string(id) + " is not an action node");
+        if (seen[size_t(id)]) return bad("node " + std::to_string(id) + " is asked for twice");
+        seen[size_t(id)] = 1;
+        if (n.n_children < 1 || n.n_children > RS_MAX_ACTIONS || int(n.round_idx) > K) return bad("node " + std::to_string(id) + " has no place in a game from this board");
+        size_t prefixes = 1;
+        for (int i = 0; i < int(n.round_idx); ++i) prefixes *= size_t(D - i);
+        if (offsets) offsets[k] = uint64_t(total);
+        total += size_t(n.n_children + 3) * prefixes * n_hands;
+    }
+    return total;
+}
+
+static int br_report_check_mode(int mode /* without RS_BR_SORTED */, int traverser) {
+    if (mode != RS_BR_AVERAGE && mode != (RS_BR_AVERAGE | RS_BR_CURRENT))
+        return fail(RS_ERR_INVALID, "rs_node_report: the report is of the strategy profile itself: mode is RS_BR_AVERAGE (| RS_BR_CURRENT, | RS_BR_SORTED)");
+    if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_node_report: traverser is 0 or 1");
+    return RS_OK;
+}
+
+// One traverser's RS_BR_AVERAGE walk with its own reach taken down beside q, the report jobs of the requested nodes behind their value jobs; the output buffer lives on
+// the device for the call and comes back in one copy.  Everything that can refuse has refused before the first launch: a refused call leaves `out` alone.
+int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
+    if (!prepared || !out) return fail(RS_ERR_INVALID, "rs_node_report: NULL argument");
+    if (int rc = br_report_check_mode(mode, traverser)) return rc;
+    BrRun &run = *prepared;
+    if (run.cfr) return fail(RS_ERR_INVALID, "rs_node_report: the prepared game belongs to a full-width solver");
+    std::vector<uint64_t> offsets(n_nodes);
+    const size_t total = br_report_layout(run.tree, run.n_board0, run.side[traverser].n_hands, nodes, n_nodes, offsets.data());
+    if (!total) return RS_ERR_INVALID;
+    if (out_doubles < total) return fail(RS_ERR_INVALID, "rs_node_report: the output buffer is too small (rs_node_report_size doubles)");
+    std::vector<int> slot_of(run.tree->nodes.size(), -1);
+    for (size_t k = 0; k < n_nodes; ++k) slot_of[size_t(nodes[k])] = int(k);
+    rs_table *t = run.t;
+    if (int rc = table_settle(t)) return rc;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    run.mode = RS_BR_AVERAGE;
+    run.real = false;
+    run.current = (mode & RS_BR_CURRENT) != 0;
+    run.err = hipSuccess;
+    if (int rc = br_root_reach(run, "rs_node_report: the root reach")) return rc;
+    DevBuf<double> d_out;
+    RS_HIP(d_out.alloc(total), "rs_node_report: the output buffer");
+    run.report_slot = &slot_of;
+    run.report_off = offsets.data();
+    run.d_report = d_out;
+    run.last_launches = 0;
+    std::vector<double> root(run.n_pad_max);
+    double value = 0.0;
+    int rc = run.traverse(traverser, root, &value);   // synchronises: nothing queued touches d_out after it
+    run.report_slot = nullptr;
+    run.report_off = nullptr;
+    run.d_report = nullptr;
+    if (rc) return rc;
+    RS_HIP(hipMemcpy(out, d_out, total * sizeof(double), hipMemcpyDeviceToHost), "rs_node_report: the copy back");
+    return RS_OK;
+}
+
 // ---- the full-width sweep on a prepared game ---------------------------------------------------------------------------------------------------------------------
 // One traverser's sweep over the table as it stands; *value = the sum of the root's values, ascending (the traverser's value per deal under the current profile).
 // It WRITES the table: a training loop's working copy is settled first and kept shadow records are invalidated (rs_table.epoch), as every other writer does.
@@ -2270,12 +2512,7 @@ int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
     run.real = run.current = false;
     run.cfr_rmplus = rmplus ? 1 : 0;
     run.err = hipSuccess;
-    for (int p = 0; p < 2; ++p)
-        if (!run.d_pi0[p]) {
-            const std::vector<double> ones(run.side[p].n, 1.0);
-            run.d_pi0[p] = run.upload(ones);
-            if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr: the root reach");
-        }
+    if (int rc = br_root_reach(run, "rs_range_cfr: the root reach")) return rc;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
     double total = 0.0;
@@ -2376,6 +2613,27 @@ int rs_best_response_rounds(rs_table *t, const rs_tree *tree, const uint8_t *boa
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
     const int rc = rs::br_execute(run, mode, out);
+    rs::br_free(run);
+    return rc;
+}
+
+size_t rs_node_report_size(const rs_tree *tree, int n_board0, size_t n_hands_traverser, const int32_t *nodes, size_t n_nodes, uint64_t *offsets) {
+    return rs::br_report_layout(tree, n_board0, n_hands_traverser, nodes, n_nodes, offsets);
+}
+
+int rs_node_report(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                   size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out,
+                   size_t out_doubles) {
+    if (!out) return fail(RS_ERR_INVALID, "rs_node_report: NULL argument");
+    const bool sorted = (mode & RS_BR_SORTED) != 0;
+    mode &= ~RS_BR_SORTED;
+    if (int rc = rs::br_report_check_mode(mode, traverser)) return rc;
+    const size_t total = rs::br_report_layout(tree, n_board0, traverser == 0 ? n_hands_p0 : n_hands_p1, nodes, n_nodes, nullptr);   // before the game is prepared: a bad request costs nothing
+    if (!total) return RS_ERR_INVALID;
+    if (out_doubles < total) return fail(RS_ERR_INVALID, "rs_node_report: the output buffer is too small (rs_node_report_size doubles)");
+    rs::BrRun *run = nullptr;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
+    const int rc = rs::br_report(run, mode, traverser, nodes, n_nodes, out, out_doubles);
     rs::br_free(run);
     return rc;
 }

@@ -133,6 +133,8 @@ struct BrRun;
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
                const uint32_t *const *cluster, int n_rounds, bool sorted, BrRun **prepared);
 int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVERAGE */, double *out /* [2] */);
+// one traverser's node report (rs_node_report) on the prepared game; mode without RS_BR_SORTED.  A workspace that lacks the report's rows is traded for a larger one
+int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
 void br_free(BrRun *prepared);
 size_t br_held_bytes(const BrRun *prepared);        // device bytes the object holds: the game-only half + the walk's workspace (kept from the first br_execute on)
 void br_release_workspace(BrRun *prepared);         // gives the workspace back; the next br_execute allocates it again

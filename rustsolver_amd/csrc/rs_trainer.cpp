@@ -509,6 +509,21 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     return rs::br_execute(tr->br_prepared[which], mode & ~RS_BR_SORTED, out);
 }
 
+// rs_node_report on the trainer's own game, on the prepared game and workspace rs_deal_trainer_best_response keeps for the showdown mode
+int rs_deal_trainer_node_report(rs_deal_trainer *tr, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
+    if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_node_report: NULL argument");
+    uint8_t board[5];
+    int n_board0 = 0;
+    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
+    if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
+    const int which = (mode & RS_BR_SORTED) ? 1 : 0;
+    if (!tr->br_prepared[which])
+        if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
+                                    which == 1, &tr->br_prepared[which]))
+            return rc;
+    return rs::br_report(tr->br_prepared[which], mode & ~RS_BR_SORTED, traverser, nodes, n_nodes, out, out_doubles);
+}
+
 // full-width CFR on the trainer's own game (rs_range_cfr_train): a prepared game of its own per showdown form, beside the best response's two
 int rs_deal_trainer_range_cfr(rs_deal_trainer *tr, uint64_t iterations, const rs_range_cfr_params *params, const rs_dcfr_params *dcfr, double *values) {
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: trainer is NULL");

@@ -116,6 +116,31 @@ def tree_from_nodes(nodes):
     return GameTree(h)
 
 
+def _report_request(tree, n_board0, n_hands, nodes):
+    """a node report's request: the ids as int32, the blocks' offsets and the output buffer (rs_node_report_size); a bad request raises RsError before anything runs"""
+    ids = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+    offsets = np.zeros(max(len(ids), 1), dtype=np.uint64)
+    total = int(L.load().rs_node_report_size(tree._h, n_board0, n_hands, _vp(ids), len(ids), _vp(offsets)))
+    if total == 0:
+        raise L.RsError(L.ERR_INVALID, L.load().rs_last_error().decode("utf-8", "replace"))
+    return ids, offsets, np.zeros(total, dtype=np.float64)
+
+
+def _report_blocks(tree, n_hands, ids, offsets, out):
+    """{node: dict(cfv=[A][F][H], value=[F][H], mass=[F][H], own=[F][H])} from a node report's output buffer"""
+    res = {}
+    ends = list(offsets[1:len(ids)]) + [len(out)]
+    for k, node in enumerate(ids):
+        A = tree.nodes[int(node)].n_children
+        block = out[int(offsets[k]):int(ends[k])].reshape(A + 3, -1, n_hands)
+        res[int(node)] = dict(cfv=block[:A], value=block[A], mass=block[A + 1], own=block[A + 2])
+    return res
+
+
+def _report_mode(current, sorted_showdowns):
+    return L.BR_AVERAGE | (L.BR_CURRENT if current else 0) | (L.BR_SORTED if sorted_showdowns else 0)
+
+
 class DeviceBuffer:
     """A device allocation owned through the table's stream (rs_dmalloc / rs_dfree)."""
 
@@ -391,6 +416,24 @@ class InfosetTable:
         L.check(L.load().rs_best_response_rounds(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), mode,
                                                  out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True):
+        """per-hand values, reach and mass at the action nodes `nodes` (tree node ids) for one traverser, both players playing the average strategy (current: the current
+        one) in the game best_response_rounds measures (rs_node_report).  -> {node: dict(cfv=[A][F][H], value=[F][H], mass=[F][H], own=[F][H])}, float64, F the prefixes of
+        the node's round, H the traverser's hands: cfv[a] the action's counterfactual value, value the node's, mass the opponent range the hand faces (cfv / mass = chips
+        given that the hand is there), own the traverser's own probability of getting there"""
+        b = np.ascontiguousarray(board0, dtype=np.uint8)
+        h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
+        h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
+        keep = [np.ascontiguousarray(clusters[r][p], dtype=np.uint32) for r in range(len(clusters)) for p in (0, 1)]
+        arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        if traverser not in (0, 1):
+            raise L.RsError(L.ERR_INVALID, "rs_node_report: traverser is 0 or 1")
+        n_hands = len(h1) if traverser else len(h0)
+        ids, offsets, out = _report_request(tree, len(b), n_hands, nodes)
+        L.check(L.load().rs_node_report(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _report_mode(current, sorted_showdowns),
+                                        int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
+        return _report_blocks(tree, n_hands, ids, offsets, out)
 
     def update_node(self, node, action_utils, reach=None, scale=100.0, mode=L.UPD_CLAMP_I64):
         """One traverser visit of every lane (cfr.rs:370-466 / :571-623).  Returns node util [lanes]."""
@@ -713,6 +756,7 @@ class DealTrainer:
                                                 C.byref(h)))
         self._h = h
         self.n_deals = deals_per_batch
+        self._n_hands, self._n_board0 = (len(h0), len(h1)), bin(board_mask).count("1")
         self.infosets = InfosetTable(C.c_void_p(L.load().rs_deal_trainer_table(h)), owned=False)
 
     def train(self, n_batches):
@@ -789,6 +833,15 @@ class DealTrainer:
         out = np.zeros(2, dtype=np.float64)
         L.check(L.load().rs_deal_trainer_best_response(self._h, mode | (L.BR_CURRENT if current else 0), _vp(out)))
         return out
+
+    def node_report(self, traverser, nodes, current=False, sorted_showdowns=True):
+        """InfosetTable.node_report on the trainer's own tree, ranges, board and cluster tables (rs_deal_trainer_node_report), on the prepared game best_response() keeps"""
+        if traverser not in (0, 1):
+            raise L.RsError(L.ERR_INVALID, "rs_deal_trainer_node_report: traverser is 0 or 1")
+        n_hands = self._n_hands[traverser]
+        ids, offsets, out = _report_request(self.game_tree, self._n_board0, n_hands, nodes)
+        L.check(L.load().rs_deal_trainer_node_report(self._h, _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
+        return _report_blocks(self.game_tree, n_hands, ids, offsets, out)
 
     def train_full_width(self, iterations, rmplus=False, dcfr=None, sorted_showdowns=True):
         """rs_deal_trainer_range_cfr: `iterations` iterations of full-width, chance-enumerated CFR over both ranges on the trainer's own game and table (F32 trainers).
