@@ -49,7 +49,9 @@ extern "C" {
                                  rs_deal_trainer_set_dcfr) -- additions only, nothing that existed changes size or meaning;
                                  still 6: RS_BR_REAL (a mode bit of rs_best_response, rs_best_response_rounds, rs_deal_trainer_best_response) -- modes without it mean what they meant;
                                  still 6: full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT, a mode bit of the same three -- additions only;
-                                 still 6: the node report (rs_node_report_size, rs_node_report, rs_deal_trainer_node_report) -- additions only */
+                                 still 6: the node report (rs_node_report_size, rs_node_report, rs_deal_trainer_node_report) -- additions only;
+                                 still 6: weighted hand ranges (rs_range_weights, RS_DEAL_*, rs_best_response_weighted, rs_node_report_weighted, rs_range_cfr_create_weighted) --
+                                 additions only: the calls without weights take the code path they took */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -270,6 +272,39 @@ size_t rs_node_report_size(const rs_tree *tree, int n_board0, size_t n_hands_tra
 int rs_node_report(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
                    const uint32_t *const *cluster, int n_rounds, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
 
+/* ---- weighted hand ranges (an extension) -------------------------------------------------------------
+ * rs_best_response_rounds, rs_node_report and rs_range_cfr_create take a range as a list of combos: every hand counts the same.  The forms below take per-hand weights
+ * W0[h0], W1[h1] (f64, finite and > 0; a NULL row = 1.0 for every hand of that player) and one of two deal distributions.  A deal (b, h0, h1) exists when the run-out b, h0 and
+ * h1 share no card, as without weights.
+ *   RS_DEAL_SEQUENTIAL (0)  generate_hand (cfr.rs:100-143) with weighted draws: the run-out uniform over ordered completions, then player 0, then player 1 among what is left:
+ *                           P(b, h0, h1) = P(b) * W0[h0] / Z0(b) * W1[h1] / Z1(b, h0),  Z0(b) = the sum of W0 over player 0's hands that avoid b,
+ *                           Z1(b, h0) = the sum of W1 over player 1's hands that avoid b and h0.  Where Z1(b, h0) = 0 the lane weighs 0 and its share is lost, as without
+ *                           weights when no hand of player 1 fits.  With every weight 1.0 this is the unweighted distribution bit for bit: the sums are exact integers
+ *                           and (P(b) * W0[h0]) / (Z0(b) * Z1(b, h0)) is P(b) / (N0(b) * N1(b, h0)).
+ *   RS_DEAL_JOINT (1)       P(b, h0, h1) = W0[h0] * W1[h1] / Z over all deals,  Z = the sum over the lanes (b, h0) that are no blocked lane, in ascending lane order, of
+ *                           W0[h0] * Z1(b, h0): the product of two independent ranges with card removal -- what a re-solve from two reach vectors means (a node report's
+ *                           `own` row times the prior of each traverser -> the weights of the subtree's game from the node's board).
+ * Every sum runs over ascending hand (or lane) index from 0.0, hands that do not fit are not added: the results are a function of the inputs alone.  On the device player
+ * 0's lanes carry (P(b) * W0[h0]) / (Z0(b) * Z1(b, h0)) (joint: W0[h0] / Z; 0.0 where Z1 = 0), player 1's lanes W1[h1] on every run-out where they carry 1.0 without
+ * weights; no kernel of the walk changes.  The traverser's own reach pi still starts at 1.0: `own` of a node report stays a pure strategy reach and P of the full-width update
+ * the sum of pi -- prior weights are chance, not strategy.  out[], *value, cfv, v and mass keep their per-deal units under the new distribution.
+ * weights == NULL is the call without weights.  RS_ERR_INVALID for a weight that is NaN, infinite, zero or negative, a player's weight sum that is not finite, an unknown
+ * `deal` and a non-zero `reserved`: refused before anything is allocated or written (`out` and the table are left alone).  A hand that is not in the range is left out of
+ * the list, not given weight 0.  Duplicate combos stay allowed without RS_BR_SORTED (k copies of a hand = the hand with weight k) and refused with it.
+ * The rs_deal_trainer_* forms stay unweighted: the sampled trainer draws its deals uniformly, and weighted sampling on the dealing stream is a later feature. */
+enum { RS_DEAL_SEQUENTIAL = 0, RS_DEAL_JOINT = 1 };
+typedef struct rs_range_weights {
+    const double *w[2];   /* [n_hands_p], host; NULL = 1.0 for every hand of that player */
+    int32_t deal;         /* RS_DEAL_* */
+    int32_t reserved;     /* 0 */
+} rs_range_weights;
+int rs_best_response_weighted(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                              const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode,
+                              double *out /*[2]*/);
+int rs_node_report_weighted(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                            size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode, int traverser, const int32_t *nodes,
+                            size_t n_nodes, double *out, size_t out_doubles);
+
 /* One traverser visit of every lane of `node` (cfr.rs:370-466 / :571-623):
  *   sigma = get_strategy(); util = sum_a utils[a]*sigma[a]; regrets / strategy_sum updated with
  *   (scale*reach)*(utils[a]-util) and (scale*reach)*sigma[a] in the arithmetic of `mode`.
@@ -333,6 +368,9 @@ typedef struct rs_range_cfr_params {
 int rs_range_cfr_create(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
                         const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds,
                         const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
+int rs_range_cfr_create_weighted(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                                 const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds,
+                                 const rs_range_weights *weights /* NULL = rs_range_cfr_create */, const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
 void rs_range_cfr_destroy(rs_range_cfr *s);
 int rs_range_cfr_iterate(rs_range_cfr *s, int traverser, double *value /* may be NULL */);
 int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_params *dcfr /* NULL = no ticks */, double *values /* [2], last iteration's, may be NULL */);

@@ -24,6 +24,7 @@ BR_MAX, BR_AVERAGE = 0, 1   # rs_best_response modes
 BR_SORTED = 0x100           # | into the mode: showdowns by rank order (O(n log n) per run-out), sums in a fixed order of their own
 BR_REAL = 0x200             # | into BR_MAX: the best response in the real game (info set = board cards seen + own hole cards) against the abstracted average strategy
 BR_CURRENT = 0x400          # | into any mode: the strategies read are the CURRENT ones (get_strategy of the regrets) instead of the average ones
+DEAL_SEQUENTIAL, DEAL_JOINT = 0, 1   # rs_range_weights.deal (RS_DEAL_*)
 DIST_EMD, DIST_L2 = 0, 1
 K_UPDATE, K_NODE_UTIL, K_REACH, K_CHANCE, K_DISCOUNT, K_STRATEGY, K_TREE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 
@@ -89,6 +90,10 @@ class DcfrParams(C.Structure):   # rs_dcfr_params
 
 class RangeCfrParams(C.Structure):   # rs_range_cfr_params
     _fields_ = [("mode", C.c_int32), ("sorted", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class RangeWeights(C.Structure):   # rs_range_weights
+    _fields_ = [("w", C.c_void_p * 2), ("deal", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Profile(C.Structure):
@@ -236,6 +241,7 @@ SYMBOLS = {
     "rs_deal_trainer_best_response": (C.c_int, [_P, C.c_int, _P]),
     "rs_deal_trainer_range_cfr": (C.c_int, [_P, C.c_uint64, C.POINTER(RangeCfrParams), C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
     "rs_range_cfr_create": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeCfrParams), _PP]),
+    "rs_range_cfr_create_weighted": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(RangeCfrParams), _PP]),
     "rs_range_cfr_destroy": (None, [_P]),
     "rs_range_cfr_iterate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "rs_range_cfr_train": (C.c_int, [_P, C.c_uint64, C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
@@ -253,9 +259,12 @@ SYMBOLS = {
     "rs_update_min_dists": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, _P, C.c_int]),
     "rs_showdown_sign": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rs_best_response_rounds": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "rs_best_response_weighted": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.c_int, C.POINTER(C.c_double)]),
     "rs_br_runouts": (C.c_size_t, [_P, C.c_int, _P]),
     "rs_node_report_size": (C.c_size_t, [_P, C.c_int, C.c_size_t, _P, C.c_size_t, _P]),
     "rs_node_report": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
+    "rs_node_report_weighted": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.c_int, C.c_int, _P, C.c_size_t, _P,
+                                          C.c_size_t]),
     "rs_deal_trainer_node_report": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
     "rs_kmeans_init_s": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "rs_kmeans_pick_restart": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),

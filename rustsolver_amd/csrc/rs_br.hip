@@ -359,6 +359,55 @@ __global__ __launch_bounds__(kBrBlock) void k_br_weights(const uint64_t *__restr
     w0[lane] = cnt1 ? pb / ((double)cnt0[b] * (double)cnt1) : 0.0;
 }
 
+// ---- weighted ranges (rs_range_weights): the same two lane rows from per-hand weights -------------------------------------------------------------------------------
+// Z1(b, h0) = the sum of W1 over player 1's hands that avoid the run-out and h0, ascending from 0.0 (0.0 on a blocked lane).  One workgroup = up to 256 hands of player 0
+// on one run-out; player 1's masks and weights are staged in LDS once (at most 1 326 x 16 bytes), as br_terminal_boards_body stages the opponent's side.
+__global__ __launch_bounds__(kBrBlock) void k_br_weighted_z1(const uint64_t *__restrict__ mask0, uint32_t n0, const uint64_t *__restrict__ mask1,
+                                                             const double *__restrict__ w1, uint32_t n1, const uint64_t *__restrict__ bmask, double *__restrict__ z1) {
+    extern __shared__ unsigned char br_lds[];
+    double *lw = (double *)br_lds;
+    uint64_t *lm = (uint64_t *)(lw + n1);
+    const uint32_t b = blockIdx.y;
+    const uint64_t bm = bmask[b];
+    for (uint32_t g = threadIdx.x; g < n1; g += kBrBlock) {
+        lw[g] = w1[g];
+        lm[g] = mask1[g];
+    }
+    __syncthreads();
+    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
+    if (h >= n0) return;
+    const size_t lane = (size_t)b * n0 + h;
+    const uint64_t mine = mask0[h];
+    if (mine & bm) {
+        z1[lane] = 0.0;
+        return;
+    }
+    const uint64_t avoid = mine | bm;
+    double acc = 0.0;
+    for (uint32_t g = 0; g < n1; g++) {
+        if (lm[g] & avoid) continue;
+        acc += lw[g];
+    }
+    z1[lane] = acc;
+}
+// player 0's lane row from Z1, in place.  Sequential (z0 given): (pb * W0[h]) / (Z0(b) * Z1); joint (z0 null): W0[h] / Z, scale = Z; 0.0 where Z1 = 0 (blocked lanes are)
+__global__ __launch_bounds__(kBrBlock) void k_br_weighted_lanes(const double *__restrict__ w0, uint32_t n0, const double *__restrict__ z0, uint32_t NB, double scale,
+                                                                double *__restrict__ row) {
+    const size_t lane = (size_t)blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= (size_t)NB * n0) return;
+    const uint32_t b = (uint32_t)(lane / n0), h = (uint32_t)(lane - (size_t)b * n0);
+    const double z1 = row[lane];
+    double w = 0.0;
+    if (z1 > 0.0) w = z0 ? (scale * w0[h]) / (z0[b] * z1) : w0[h] / scale;
+    row[lane] = w;
+}
+// player 1's lane row: W1 on every run-out
+__global__ __launch_bounds__(kBrBlock) void k_br_tile_weights(const double *__restrict__ w1, uint32_t n1, uint32_t NB, double *__restrict__ row) {
+    const size_t lane = (size_t)blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= (size_t)NB * n1) return;
+    row[lane] = w1[lane % n1];
+}
+
 // terminal: v[b, hp] = pw[b, hp] * sum over the opponent's hands ho of the SAME run-out that share no card with hp or the run-out, ascending, of q[b, ho] * u;
 // u as the trainer's leaves (cfr.rs:314-348).  One workgroup = up to 256 hands of one run-out; the opponent's side of that run-out is staged in LDS.
 __device__ __forceinline__ void br_terminal_boards_body(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
@@ -2150,10 +2199,76 @@ static void build_columns(BrRun &run, BrSide &s, int r, const std::vector<uint32
     s.kmax[r] = kmax;
 }
 
+// The two lane rows of a game with weighted ranges (rs_range_weights; the header states both distributions).  Z0(b) on the host, Z1(b, h0) per lane on the device into
+// player 0's row, which k_br_weighted_lanes then turns into the lane factor in place; the joint distribution's Z is the host's sum, ascending from 0.0, over the row
+// copied back in between.  Failures land in run.err, like every other step of br_prepare.
+static void br_weighted_rows(BrRun &run, const rs_range_weights &weights, const std::vector<uint64_t> &mask0, const std::vector<uint64_t> &bmask, double pb) {
+    BrSide &s0 = run.side[0], &s1 = run.side[1];
+    hipStream_t stream = run.t->stream;
+    const size_t NB = run.NB, n0 = s0.n_hands, n1 = s1.n_hands;
+    std::vector<double> w0(n0, 1.0), w1(n1, 1.0);
+    if (weights.w[0]) w0.assign(weights.w[0], weights.w[0] + n0);
+    if (weights.w[1]) w1.assign(weights.w[1], weights.w[1] + n1);
+    const bool joint = weights.deal == RS_DEAL_JOINT;
+    double *d_w0 = run.upload(w0), *d_w1 = run.upload(w1), *d_z0 = nullptr;
+    if (!joint) {
+        std::vector<double> z0(NB, 0.0);
+        for (size_t b = 0; b < NB; ++b)
+            for (size_t h = 0; h < n0; ++h)
+                if ((mask0[h] & bmask[b]) == 0) z0[b] += w0[h];
+        d_z0 = run.upload(z0);
+    }
+    double *d_row0 = run.dalloc<double>(s0.n), *d_row1 = run.dalloc<double>(s1.n);
+    if (run.err != hipSuccess) return;
+    hipLaunchKernelGGL(k_br_weighted_z1, dim3(grid1(s0.n_hands), uint32_t(NB)), dim3(kBrBlock), n1 * (sizeof(double) + sizeof(uint64_t)), stream, s0.d_mask, s0.n_hands,
+                       s1.d_mask, d_w1, s1.n_hands, run.d_bmask, d_row0);
+    if ((run.err = hipGetLastError()) != hipSuccess) return;
+    double scale = pb;
+    if (joint) {
+        std::vector<double> z1(s0.n);
+        run.err = hipMemcpyAsync(z1.data(), d_row0, z1.size() * sizeof(double), hipMemcpyDeviceToHost, stream);
+        if (run.err == hipSuccess) run.err = hipStreamSynchronize(stream);
+        if (run.err != hipSuccess) return;
+        scale = 0.0;
+        for (size_t b = 0; b < NB; ++b)
+            for (size_t h = 0; h < n0; ++h)
+                if ((mask0[h] & bmask[b]) == 0) scale += w0[h] * z1[b * n0 + h];
+    }
+    hipLaunchKernelGGL(k_br_weighted_lanes, dim3(grid1(s0.n)), dim3(kBrBlock), 0, stream, d_w0, s0.n_hands, d_z0, uint32_t(NB), scale, d_row0);
+    if ((run.err = hipGetLastError()) != hipSuccess) return;
+    hipLaunchKernelGGL(k_br_tile_weights, dim3(grid1(s1.n)), dim3(kBrBlock), 0, stream, d_w1, s1.n_hands, uint32_t(NB), d_row1);
+    run.err = hipGetLastError();
+    s0.d_init_q = s0.d_pw = d_row0;
+    s1.d_init_q = s1.d_pw = d_row1;
+}
+
+// rs_range_weights as the header states them; NULL = no weights.  Touches nothing: the weighted entry points call it before anything is allocated or written
+int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t n_hands_p1) {
+    if (!weights) return RS_OK;
+    if (weights->deal != RS_DEAL_SEQUENTIAL && weights->deal != RS_DEAL_JOINT) return fail(RS_ERR_INVALID, "rs_range_weights: deal is RS_DEAL_SEQUENTIAL or RS_DEAL_JOINT");
+    if (weights->reserved != 0) return fail(RS_ERR_INVALID, "rs_range_weights: reserved must be 0");
+    const size_t n_hands[2] = {n_hands_p0, n_hands_p1};
+    for (int p = 0; p < 2; ++p) {
+        if (!weights->w[p]) continue;
+        if (n_hands[p] == 0 || n_hands[p] > 1326) return fail(RS_ERR_INVALID, "rs_best_response: 1..1326 hands per range");
+        double sum = 0.0;
+        for (size_t h = 0; h < n_hands[p]; ++h) {
+            const double w = weights->w[p][h];
+            if (!(w > 0.0) || !std::isfinite(w))
+                return fail(RS_ERR_INVALID, "rs_range_weights: weight " + std::to_string(h) + " of player " + std::to_string(p) +
+                                                " is not finite and > 0 (a hand that is not in the range is left out of the list)");
+            sum += w;
+        }
+        if (!std::isfinite(sum)) return fail(RS_ERR_INVALID, "rs_range_weights: the weights of player " + std::to_string(p) + " do not add up to a finite number");
+    }
+    return RS_OK;
+}
+
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
-               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, bool sorted, BrRun **prepared) {
+               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights, BrRun **prepared) {
     if (!t || !tree || !board0 || !hands_p0 || !hands_p1 || !cluster || !prepared) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     *prepared = nullptr;
+    if (int rc = br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc;
     if (tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_best_response: empty tree");
     if (n_board0 < 3 || n_board0 > 5) return fail(RS_ERR_INVALID, "rs_best_response: the initial board has 3, 4 or 5 cards (state.rs:59-64)");
     const int K = 5 - n_board0, D = 52 - n_board0;
@@ -2221,7 +2336,7 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
     for (int r = 0; r < RS_MAX_ROUNDS; ++r) run.per_prefix[r] = uint32_t(per_prefix[r]);
     run.d_bmask = run.upload(bmask);
     uint8_t *d_boards = run.upload(cards);
-    uint32_t *d_cnt0 = run.upload(cnt0);
+    uint32_t *d_cnt0 = weights ? nullptr : run.upload(cnt0);   // (weighted ranges: Z0 takes its place, br_weighted_rows)
     for (int p = 0; p < 2; ++p) {
         BrSide &s = run.side[p];
         s.n_hands = uint32_t(n_hands[p]);
@@ -2294,16 +2409,20 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
     // that avoid the full board, player 1's over those that avoid board and player 0: P = P(B) [disjoint] / (N0(B) N1(B, h0)); the whole weight rides on player 0's lane
     double pb = 1.0;
     for (int i = 0; i < K; ++i) pb /= double(D - i);
-    double *d_w0 = run.dalloc<double>(run.side[0].n);
-    if (run.err == hipSuccess) {
-        hipLaunchKernelGGL(k_br_weights, dim3(grid1(run.side[0].n)), dim3(kBrBlock), 0, t->stream, run.side[0].d_mask, run.side[0].n_hands, run.side[1].d_mask,
-                           run.side[1].n_hands, run.d_bmask, d_cnt0, uint32_t(NB), pb, d_w0);
-        run.err = hipGetLastError();
+    if (weights) {
+        br_weighted_rows(run, *weights, mask[0], bmask, pb);
+    } else {
+        double *d_w0 = run.dalloc<double>(run.side[0].n);
+        if (run.err == hipSuccess) {
+            hipLaunchKernelGGL(k_br_weights, dim3(grid1(run.side[0].n)), dim3(kBrBlock), 0, t->stream, run.side[0].d_mask, run.side[0].n_hands, run.side[1].d_mask,
+                               run.side[1].n_hands, run.d_bmask, d_cnt0, uint32_t(NB), pb, d_w0);
+            run.err = hipGetLastError();
+        }
+        std::vector<double> ones(run.side[1].n, 1.0);
+        double *d_ones = run.upload(ones);
+        run.side[0].d_init_q = run.side[0].d_pw = d_w0;
+        run.side[1].d_init_q = run.side[1].d_pw = d_ones;
     }
-    std::vector<double> ones(run.side[1].n, 1.0);
-    double *d_ones = run.upload(ones);
-    run.side[0].d_init_q = run.side[0].d_pw = d_w0;
-    run.side[1].d_init_q = run.side[1].d_pw = d_ones;
     // the walk's buffers are allocated by every call (br_execute) and freed when it returns: a kept object holds what depends on the game only
     run.n_pad_max = std::max(run.side[0].n_pad, run.side[1].n_pad);
     run.fill_depths();
@@ -2533,9 +2652,15 @@ extern "C" {
 
 int rs_range_cfr_create(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                         size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_cfr_params *params, rs_range_cfr **out) {
+    return rs_range_cfr_create_weighted(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, nullptr, params, out);
+}
+int rs_range_cfr_create_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                                 size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_range_cfr_params *params,
+                                 rs_range_cfr **out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
     *out = nullptr;
     if (!t) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
+    if (int rc_ = rs::br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc_;   // before the table is settled: a refused call writes nothing
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate): the index kernels go to the table's stream
     const int mode = params ? params->mode : 0;
     if (mode != 0 && mode != RS_UPD_RMPLUS) return fail(RS_ERR_INVALID, "rs_range_cfr_create: params->mode is 0 or RS_UPD_RMPLUS");
@@ -2543,7 +2668,9 @@ int rs_range_cfr_create(rs_table *t, const rs_tree *tree, const uint8_t *board0,
     if (t->dtype != RS_F32)
         return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_create: RS_F32 tables only (the sums are per-deal probabilities times pots: no integer scale, and binary16 cells are out of scope)");
     rs::BrRun *run = nullptr;
-    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, !params || params->sorted != RS_FORM_OFF, &run)) return rc;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, !params || params->sorted != RS_FORM_OFF, weights,
+                                &run))
+        return rc;
     if (int rc = rs::br_cfr_mark(run)) {
         rs::br_free(run);
         return rc;
@@ -2606,12 +2733,17 @@ extern "C" {
 
 int rs_best_response_rounds(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                             size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, int mode, double *out) {
+    return rs_best_response_weighted(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, nullptr, mode, out);
+}
+
+int rs_best_response_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                              size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode, double *out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
     if (int rc = rs::br_check_mode(mode & ~(RS_BR_REAL | RS_BR_CURRENT), (mode & RS_BR_REAL) != 0)) return rc;
     rs::BrRun *run = nullptr;
-    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run)) return rc;
     const int rc = rs::br_execute(run, mode, out);
     rs::br_free(run);
     return rc;
@@ -2624,6 +2756,13 @@ size_t rs_node_report_size(const rs_tree *tree, int n_board0, size_t n_hands_tra
 int rs_node_report(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                    size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out,
                    size_t out_doubles) {
+    return rs_node_report_weighted(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, nullptr, mode, traverser, nodes, n_nodes, out,
+                                   out_doubles);
+}
+
+int rs_node_report_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                            size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode, int traverser, const int32_t *nodes,
+                            size_t n_nodes, double *out, size_t out_doubles) {
     if (!out) return fail(RS_ERR_INVALID, "rs_node_report: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
@@ -2632,7 +2771,7 @@ int rs_node_report(rs_table *t, const rs_tree *tree, const uint8_t *board0, int 
     if (!total) return RS_ERR_INVALID;
     if (out_doubles < total) return fail(RS_ERR_INVALID, "rs_node_report: the output buffer is too small (rs_node_report_size doubles)");
     rs::BrRun *run = nullptr;
-    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, &run)) return rc;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run)) return rc;
     const int rc = rs::br_report(run, mode, traverser, nodes, n_nodes, out, out_doubles);
     rs::br_free(run);
     return rc;

@@ -131,7 +131,8 @@ struct CompactJob {
 // best response over run-outs (rs_br.hip): what depends on the game only is prepared once, the walk runs against the table as it stands
 struct BrRun;
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
-               const uint32_t *const *cluster, int n_rounds, bool sorted, BrRun **prepared);
+               const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights /* NULL = every hand counts the same */, BrRun **prepared);
+int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t n_hands_p1);   // RS_ERR_INVALID as the header lists; touches nothing
 int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVERAGE */, double *out /* [2] */);
 // one traverser's node report (rs_node_report) on the prepared game; mode without RS_BR_SORTED.  A workspace that lacks the report's rows is traded for a larger one
 int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);

@@ -504,7 +504,7 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     const int which = (mode & RS_BR_SORTED) ? 1 : 0;
     if (!tr->br_prepared[which])
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, &tr->br_prepared[which]))
+                                    which == 1, nullptr, &tr->br_prepared[which]))
             return rc;
     return rs::br_execute(tr->br_prepared[which], mode & ~RS_BR_SORTED, out);
 }
@@ -519,7 +519,7 @@ int rs_deal_trainer_node_report(rs_deal_trainer *tr, int mode, int traverser, co
     const int which = (mode & RS_BR_SORTED) ? 1 : 0;
     if (!tr->br_prepared[which])
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, &tr->br_prepared[which]))
+                                    which == 1, nullptr, &tr->br_prepared[which]))
             return rc;
     return rs::br_report(tr->br_prepared[which], mode & ~RS_BR_SORTED, traverser, nodes, n_nodes, out, out_doubles);
 }
@@ -539,7 +539,7 @@ int rs_deal_trainer_range_cfr(rs_deal_trainer *tr, uint64_t iterations, const rs
     if (!tr->cfr_prepared[which]) {
         rs::BrRun *run = nullptr;
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, &run))
+                                    which == 1, nullptr, &run))
             return rc;
         if (int rc = rs::br_cfr_mark(run)) {
             rs::br_free(run);

@@ -141,6 +141,66 @@ def _report_mode(current, sorted_showdowns):
     return L.BR_AVERAGE | (L.BR_CURRENT if current else 0) | (L.BR_SORTED if sorted_showdowns else 0)
 
 
+DEALS = {"sequential": L.DEAL_SEQUENTIAL, "joint": L.DEAL_JOINT}
+
+
+def drop_zero_weights(hands, clusters, weights):
+    """A hand of weight exactly 0.0 is by definition a hand that is not in the range (the C ABI takes weights > 0 only): drops those hands, their weights and their
+    columns of every cluster table.  hands = (hands0, hands1), clusters[r][p] = [prefixes of round r][n_hands_p], weights = None or (w0, w1), either None.
+    -> hands, clusters, weights as contiguous arrays (weights float64, None where None was given) and keep = per player the bool mask of the hands that stay (None where
+    no weights were given).  Pure: no device, no library; every other value of a weight (negative, NaN, ...) stays for the library to refuse."""
+    hands = [np.ascontiguousarray(h, dtype=np.uint8).reshape(-1, 2) for h in hands]
+    if weights is None:
+        weights = (None, None)
+    if len(weights) != 2:
+        raise ValueError("weights is a pair (weights of player 0, of player 1); either may be None")
+    w, keep = [None, None], [None, None]
+    for p in (0, 1):
+        if weights[p] is None:
+            continue
+        w[p] = np.ascontiguousarray(weights[p], dtype=np.float64).reshape(-1)
+        if len(w[p]) != len(hands[p]):
+            raise ValueError("one weight per hand: %d weights for the %d hands of player %d" % (len(w[p]), len(hands[p]), p))
+        keep[p] = w[p] != 0.0
+    cl = []
+    for row in clusters:
+        out = []
+        for p in (0, 1):
+            c = np.ascontiguousarray(row[p], dtype=np.uint32)
+            if keep[p] is not None and not keep[p].all():
+                c = np.ascontiguousarray(c.reshape(-1, len(keep[p]))[:, keep[p]])
+            out.append(c)
+        cl.append(out)
+    for p in (0, 1):
+        if keep[p] is not None and not keep[p].all():
+            hands[p], w[p] = np.ascontiguousarray(hands[p][keep[p]]), np.ascontiguousarray(w[p][keep[p]])
+    return hands, cl, w, keep
+
+
+def _range_weights(w, deal):
+    """rs_range_weights of drop_zero_weights' rows, or None for the call without weights; the rows must outlive the call"""
+    deal = DEALS[deal] if isinstance(deal, str) else int(deal)
+    if w[0] is None and w[1] is None and deal == L.DEAL_SEQUENTIAL:
+        return None
+    rw = L.RangeWeights()
+    for p in (0, 1):
+        rw.w[p] = None if w[p] is None else w[p].ctypes.data
+    rw.deal, rw.reserved = deal, 0
+    return C.byref(rw)
+
+
+def _restore_columns(res, keep):
+    """a node report's rows with all-0.0 columns for the hands drop_zero_weights took out of the traverser's range"""
+    if keep is None or keep.all():
+        return res
+    for blk in res.values():
+        for key, x in blk.items():
+            full = np.zeros(x.shape[:-1] + (len(keep),), dtype=x.dtype)
+            full[..., keep] = x
+            blk[key] = full
+    return res
+
+
 class DeviceBuffer:
     """A device allocation owned through the table's stream (rs_dmalloc / rs_dfree)."""
 
@@ -404,36 +464,37 @@ class InfosetTable:
         L.check(L.load().rs_best_response(self._h, tree._h, _vp(b), _vp(h0), len(h0), _vp(c0), _vp(h1), len(h1), _vp(c1), mode, _vp(out)))
         return out
 
-    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX, current=False):
-        """multi-round best response (rs_best_response_rounds): clusters[r][p] = uint32 [prefixes of round r][n_hands_p] dense ids; current: BR_CURRENT"""
+    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX, current=False, weights=None, deal="sequential"):
+        """multi-round best response (rs_best_response_rounds): clusters[r][p] = uint32 [prefixes of round r][n_hands_p] dense ids; current: BR_CURRENT.
+        weights = (w0, w1), either None: per-hand range weights (rs_best_response_weighted), a weight of 0.0 takes the hand out of the range; deal: "sequential"
+        (generate_hand with weighted draws) or "joint" (the product of the two ranges with card removal)"""
         mode |= L.BR_CURRENT if current else 0
         b = np.ascontiguousarray(board0, dtype=np.uint8)
-        h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
-        h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
-        keep = [np.ascontiguousarray(clusters[r][p], dtype=np.uint32) for r in range(len(clusters)) for p in (0, 1)]
+        (h0, h1), cl, w, _ = drop_zero_weights((hands0, hands1), clusters, weights)
+        keep = [c for row in cl for c in row]
         arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
         out = np.zeros(2, dtype=np.float64)
-        L.check(L.load().rs_best_response_rounds(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), mode,
-                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        L.check(L.load().rs_best_response_weighted(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), mode,
+                                                   out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True):
+    def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True, weights=None, deal="sequential"):
         """per-hand values, reach and mass at the action nodes `nodes` (tree node ids) for one traverser, both players playing the average strategy (current: the current
         one) in the game best_response_rounds measures (rs_node_report).  -> {node: dict(cfv=[A][F][H], value=[F][H], mass=[F][H], own=[F][H])}, float64, F the prefixes of
         the node's round, H the traverser's hands: cfv[a] the action's counterfactual value, value the node's, mass the opponent range the hand faces (cfv / mass = chips
-        given that the hand is there), own the traverser's own probability of getting there"""
+        given that the hand is there), own the traverser's own probability of getting there.  weights, deal: as best_response_rounds (rs_node_report_weighted); a hand of
+        weight 0.0 has 0.0 in every row"""
         b = np.ascontiguousarray(board0, dtype=np.uint8)
-        h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
-        h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
-        keep = [np.ascontiguousarray(clusters[r][p], dtype=np.uint32) for r in range(len(clusters)) for p in (0, 1)]
+        (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
+        keep = [c for row in cl for c in row]
         arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
         if traverser not in (0, 1):
             raise L.RsError(L.ERR_INVALID, "rs_node_report: traverser is 0 or 1")
         n_hands = len(h1) if traverser else len(h0)
         ids, offsets, out = _report_request(tree, len(b), n_hands, nodes)
-        L.check(L.load().rs_node_report(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _report_mode(current, sorted_showdowns),
-                                        int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
-        return _report_blocks(tree, n_hands, ids, offsets, out)
+        L.check(L.load().rs_node_report_weighted(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal),
+                                                 _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
+        return _restore_columns(_report_blocks(tree, n_hands, ids, offsets, out), kept[traverser])
 
     def update_node(self, node, action_utils, reach=None, scale=100.0, mode=L.UPD_CLAMP_I64):
         """One traverser visit of every lane (cfr.rs:370-466 / :571-623).  Returns node util [lanes]."""
@@ -920,12 +981,12 @@ class RangeCFR:
     arguments: board0 (3, 4 or 5 cards), the two ranges, clusters[r][p] = uint32 [prefixes of round r][n_hands_p].  The table and the tree must outlive the object.
     The update rule (plain or regret matching+) is a property of the C object: one is created at construction (`rmplus`), the other on the first call that asks for it."""
 
-    def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True):
+    def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True, weights=None, deal="sequential"):
         self.table, self.tree = table, tree
         self._b = np.ascontiguousarray(board0, dtype=np.uint8)
-        self._h0 = np.ascontiguousarray(hands0, dtype=np.uint8).reshape(-1, 2)
-        self._h1 = np.ascontiguousarray(hands1, dtype=np.uint8).reshape(-1, 2)
-        self._cl = [np.ascontiguousarray(clusters[r][p], dtype=np.uint32) for r in range(len(clusters)) for p in (0, 1)]
+        (self._h0, self._h1), cl, self._w, _ = drop_zero_weights((hands0, hands1), clusters, weights)   # weights, deal: as InfosetTable.best_response_rounds
+        self._cl = [c for row in cl for c in row]
+        self._deal = deal
         self._sorted, self._rmplus, self._hs = bool(sorted_showdowns), bool(rmplus), {}
         self._handle(self._rmplus)
 
@@ -934,8 +995,9 @@ class RangeCFR:
         if rmplus not in self._hs:
             arr = (C.c_void_p * len(self._cl))(*[k.ctypes.data for k in self._cl])
             h = C.c_void_p()
-            L.check(L.load().rs_range_cfr_create(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1), arr,
-                                                 len(self._cl) // 2, C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
+            L.check(L.load().rs_range_cfr_create_weighted(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1),
+                                                          arr, len(self._cl) // 2, _range_weights(self._w, self._deal),
+                                                          C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
             self._hs[rmplus] = h
         self._last = self._hs[rmplus]
         return self._last
