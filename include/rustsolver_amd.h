@@ -51,7 +51,10 @@ extern "C" {
                                  still 6: full-width CFR over hand ranges (rs_range_cfr_*, rs_deal_trainer_range_cfr) and RS_BR_CURRENT, a mode bit of the same three -- additions only;
                                  still 6: the node report (rs_node_report_size, rs_node_report, rs_deal_trainer_node_report) -- additions only;
                                  still 6: weighted hand ranges (rs_range_weights, RS_DEAL_*, rs_best_response_weighted, rs_node_report_weighted, rs_range_cfr_create_weighted) --
-                                 additions only: the calls without weights take the code path they took */
+                                 additions only: the calls without weights take the code path they took;
+                                 still 6: safe subgame re-solving: rs_tree_subtree, the re-solving gadget of a full-width solver (rs_range_cfr_set_gadget,
+                                 rs_range_cfr_gadget_get, rs_range_cfr_gadget_set) -- additions only: an object without a gadget builds the plan it built and returns the bits it
+                                 returned */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -116,6 +119,11 @@ typedef struct rs_options {             /* options.rs:10-28, the fields build_ga
 int rs_options_default(rs_options *out);                                   /* options::default_flop(), options.rs:52-81 */
 int rs_tree_build(const rs_options *options, rs_tree **out);               /* build_game_tree, tree_builder.rs:9 */
 int rs_tree_from_nodes(const rs_tree_node *nodes, int n_nodes, rs_tree **out); /* adopt a Tree<GameTreeNode> (tree.rs:14-17) */
+/* The subtree below an ACTION node (anything else, or an id out of range: RS_ERR_INVALID), as rs_tree_from_nodes adopts it: the nodes in the trunk's relative order with the
+ * root at 0 (parent -1), ActionNode.index renumbered 0..n_act in ascending order of the trunk's index, round_idx less the root's; the absolute `round` of chance and terminal
+ * nodes and a terminal's value / ttype / last_to_act are the trunk's.  node_map (may be NULL) holds rs_tree_n_nodes(tree) entries: node_map[i] = the trunk node id of the
+ * subtree's node i for i < rs_tree_n_nodes(*out), -1 in the unused tail.  The action-index map follows from it with rs_tree_get_node. */
+int rs_tree_subtree(const rs_tree *tree, int node, rs_tree **out, int32_t *node_map);
 void rs_tree_destroy(rs_tree *tree);
 int rs_tree_n_nodes(const rs_tree *tree);
 int rs_tree_n_action_nodes(const rs_tree *tree);                           /* the `n_actions` of tree_builder.rs:13 */
@@ -374,6 +382,28 @@ int rs_range_cfr_create_weighted(rs_table *table, const rs_tree *tree, const uin
 void rs_range_cfr_destroy(rs_range_cfr *s);
 int rs_range_cfr_iterate(rs_range_cfr *s, int traverser, double *value /* may be NULL */);
 int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_params *dcfr /* NULL = no ticks */, double *values /* [2], last iteration's, may be NULL */);
+/* ---- the re-solving gadget (Burch, Johanson, Bowling 2014: CFR-D) on a full-width solver: safe subgame re-solving ----
+ * The object's game is a subgame cut out of a trunk (rs_tree_subtree, its board the node's board).  P = resolver, O = 1 - P, n = O's hand count.  Above the tree's root O decides
+ * PER HAND (not per cluster: the alternative value is a per-hand number) between action 0 TERMINATE, which pays hand h alt[h] -- the value the hand had in the trunk, in chips
+ * per unit of the resolver's reach mass (a node report's value / mass) -- and action 1 FOLLOW, which enters the tree.  The gadget holds f32 rows regret[2][n] and ssum[2][n]
+ * in the OBJECT (the table, its descriptors and rs_create_infosets do not change), zero after set_gadget.  sigma = get_strategy of a hand's row (infoset.rs:83-102), as f64.
+ *   O's sweep: the walk leaves the root's value row vF[b][h]; m[b][h] = the uncontested leaf of value 1.0 on P's initial reach (the node report's mass row at the root);
+ *     vT[lane] = alt[h] * m[lane].  For every hand h with a dealt lane, over its dealt lanes (run-outs b whose cards h avoids) in ascending run-out order from 0.0:
+ *       S[0] = sum vT   S[1] = sum vF   Pi = the count of dealt lanes (O's own reach is 1.0 there)
+ *       U = sigma[0] * S[0] + sigma[1] * S[1]                             (a ascending from 0.0)
+ *       regret[a][h] = (float)(regret[a][h] + (S[a] - U))                  (RS_UPD_RMPLUS: a result that is not > 0 becomes 0)
+ *       ssum[a][h]   = (float)(ssum[a][h] + Pi * sigma[a])
+ *       v[lane] = sigma[0] * vT[lane] + sigma[1] * vF[lane]                (a ascending from 0.0; 0.0 where the lane is no deal)
+ *     *value = the sum of v as root rows are summed.  Hands without a dealt lane keep their cells.
+ *   P's sweep: O's reach at the tree's root is init_q[lane] * sigma[1][h]; the walk and the table updates are otherwise unchanged.  *value = the root row's sum plus the sum,
+ *     taken the same way, of the TERMINATE leaf's row: the uncontested leaf of value -1.0 on the reach (init_q[lane] * sigma[0][h]) * alt[h].  The gadget rows are not written.
+ *   rs_range_cfr_train's Discounted CFR ticks multiply the gadget rows with the same three factors, one f32 multiply per cell.
+ * rs_range_cfr_set_gadget: alt is a HOST array of n doubles; resolver not 0 / 1 or a NaN / infinite alt: RS_ERR_INVALID, nothing written.  Calling it again re-arms with the new alt
+ *   (and resolver) and zeroes the rows.  rs_range_cfr_gadget_get / _set copy the rows out / in ([2][n] floats each,
+ *   either may be NULL); RS_ERR_INVALID before set_gadget.  Both tree orders run the gadget through the same kernels and give the same bits. */
+int rs_range_cfr_set_gadget(rs_range_cfr *s, int resolver, const double *alt /* [n_hands of player 1 - resolver], HOST */);
+int rs_range_cfr_gadget_get(const rs_range_cfr *s, float *regrets /* [2][n] */, float *strategy_sum /* [2][n] */);
+int rs_range_cfr_gadget_set(rs_range_cfr *s, const float *regrets, const float *strategy_sum);
 size_t rs_range_cfr_bytes(const rs_range_cfr *s);
 int rs_range_cfr_launches(const rs_range_cfr *s);
 

@@ -111,6 +111,7 @@ SYMBOLS = {
     "rs_options_default": (C.c_int, [C.POINTER(OptionsC)]),
     "rs_tree_build": (C.c_int, [C.POINTER(OptionsC), _PP]),
     "rs_tree_from_nodes": (C.c_int, [C.POINTER(TreeNode), C.c_int, _PP]),
+    "rs_tree_subtree": (C.c_int, [_P, C.c_int, _PP, C.POINTER(C.c_int32)]),
     "rs_tree_destroy": (None, [_P]),
     "rs_tree_n_nodes": (C.c_int, [_P]),
     "rs_tree_n_action_nodes": (C.c_int, [_P]),
@@ -245,6 +246,9 @@ SYMBOLS = {
     "rs_range_cfr_destroy": (None, [_P]),
     "rs_range_cfr_iterate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "rs_range_cfr_train": (C.c_int, [_P, C.c_uint64, C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
+    "rs_range_cfr_set_gadget": (C.c_int, [_P, C.c_int, _P]),
+    "rs_range_cfr_gadget_get": (C.c_int, [_P, _P, _P]),
+    "rs_range_cfr_gadget_set": (C.c_int, [_P, _P, _P]),
     "rs_range_cfr_bytes": (C.c_size_t, [_P]),
     "rs_range_cfr_launches": (C.c_int, [_P]),
     "rs_deal_trainer_br_bytes": (C.c_size_t, [_P]),

@@ -11,6 +11,7 @@
 //    value vectors live on the device as f64; every sum runs in a fixed order, so the CPU oracle reproduces the result bit for bit.
 //  * rs_range_cfr_*: full-width CFR over the hand ranges on the same walk (the opponent plays the current strategy, the traverser's own nodes keep their info sets' sums as
 //    regrets): three more job kinds of the best response's job table and launcher.  RS_BR_CURRENT hands the readers the regret array.
+//  * rs_range_cfr_set_gadget: the re-solving gadget above the root of a full-width solver's tree (safe subgame re-solving): two more job kinds.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1514,12 +1515,110 @@ __global__ __launch_bounds__(kBrBlock) void k_br_report_last_jobs(const uint64_t
     br_report_last_body(mask_p, bmask, n_hands, n, n_pad, jp->n_children, jp->vch, jp->v, jp->sum_src[0], jp->q, jp->q_out);
 }
 
+// ---- the re-solving gadget (rs_range_cfr_set_gadget): a two-action node of the OPPONENT above the tree's root, one info set per opponent hand ------------------------
+// Action 0 TERMINATE pays the hand alt[h] times the root's mass row, action 1 FOLLOW enters the tree.  Its rows regret[2][n] / ssum[2][n] (f32) live with the solver
+// object.  Two actions, unrolled: nothing is indexed by an action, r0 / r1 and s0 / s1 are registers.
+// get_strategy (infoset.rs:83-102) of one hand's gadget row, in registers
+__device__ __forceinline__ void br_gadget_sigma(const float *__restrict__ regret, uint32_t n, uint32_t h, float &r0, float &r1, float &s0, float &s1) {
+    r0 = regret[h];
+    r1 = regret[(size_t)n + h];
+    float norm = 0.0f;
+    if (r0 > 0.0f) norm += r0;
+    if (r1 > 0.0f) norm += r1;
+    s0 = (norm > 0.0f) ? ((r0 > 0.0f) ? r0 / norm : 0.0f) : 0.5f;
+    s1 = (norm > 0.0f) ? ((r1 > 0.0f) ? r1 / norm : 0.0f) : 0.5f;
+}
+// the resolver's sweep, on the way down: the opponent's reach at the tree's root is init_q * sigma[FOLLOW], the TERMINATE leaf's reach (init_q * sigma[TERMINATE]) * alt
+__global__ __launch_bounds__(kBrBlock) void k_br_gadget_reach(const float *__restrict__ regret, const double *__restrict__ alt, uint32_t n_hands, uint32_t n,
+                                                              const double *__restrict__ init_q, double *__restrict__ q_follow, double *__restrict__ q_term) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    const uint32_t h = lane % n_hands;
+    float r0, r1, s0, s1;
+    br_gadget_sigma(regret, n_hands, h, r0, r1, s0, s1);
+    const double q = init_q[lane];
+    q_follow[lane] = q * (double)s1;
+    q_term[lane] = (q * (double)s0) * alt[h];
+}
+// the opponent's sweep, behind the root's value job: one THREAD per hand folds the root row vF (FOLLOW) and alt * mass (TERMINATE) over the run-outs, ascending from 0.0,
+// lanes that are no deal not added (br_report_cols_body's test), kBrRealFlight loads of each row in flight; sigma is known before the fold, so the lanes get their v while
+// their values are in registers; then the hand's four cells.  The last round (NB = 1) is the same lane text once: element-wise, as k_br_report_last is.
+// (A thread per hand rather than k_br_report_cols' workgroup of 64 hands with waves sharing rows: there are two rows, not A + 2, their sums meet in U, and the kernel runs
+// once per sweep over at most 1 326 hands -- neighbouring threads read neighbouring hands of a run-out either way.)
+__global__ __launch_bounds__(kBrBlock) void k_br_gadget_own(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t NB,
+                                                            float *__restrict__ regret, float *__restrict__ ssum, const double *__restrict__ alt,
+                                                            const double *__restrict__ mass, double *v, int rmplus) {
+    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
+    if (h >= n_hands) return;
+    const uint64_t mine = mask_p[h];
+    const double al = alt[h];
+    float r0, r1, s0, s1;
+    br_gadget_sigma(regret, n_hands, h, r0, r1, s0, s1);
+    double S0 = 0.0, S1 = 0.0, P = 0.0;
+    bool any = false;
+    auto take = [&](size_t lane, bool deal, double f, double m) {   // one lane of the hand, its two values in registers
+        if (!deal) {
+            v[lane] = 0.0;
+            return;
+        }
+        const double vt = al * m;
+        S0 += vt;   // ascending run-outs, one after the other
+        S1 += f;
+        P += 1.0;   // the opponent's own reach at the gadget is 1.0 on every lane
+        any = true;
+        double acc = 0.0;
+        acc += (double)s0 * vt;
+        acc += (double)s1 * f;
+        v[lane] = acc;
+    };
+    if (NB == 1) {   // the last round: element-wise, each row read once and written once
+        take(h, !(mine & bmask[0]), v[h], mass[h]);
+    } else {
+        for (uint32_t k = 0; k < NB; k += kBrRealFlight) {
+            bool in[kBrRealFlight], deal[kBrRealFlight];
+            double tf[kBrRealFlight], tm[kBrRealFlight];
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++) {
+                const uint32_t kk = min(k + q, NB - 1);
+                in[q] = k + q < NB;
+                deal[q] = in[q] && !(mine & bmask[kk]);
+                tf[q] = v[(size_t)kk * n_hands + h];
+                tm[q] = mass[(size_t)kk * n_hands + h];
+            }
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++)
+                if (in[q]) take((size_t)(k + q) * n_hands + h, deal[q], tf[q], tm[q]);
+        }
+    }
+    if (!any) return;   // no dealt lane: the cells stay
+    double U = 0.0;
+    U += (double)s0 * S0;
+    U += (double)s1 * S1;
+    float n0 = (float)((double)r0 + (S0 - U)), n1 = (float)((double)r1 + (S1 - U));
+    if (rmplus && !(n0 > 0.0f)) n0 = 0.0f;
+    if (rmplus && !(n1 > 0.0f)) n1 = 0.0f;
+    regret[h] = n0;
+    regret[(size_t)n_hands + h] = n1;
+    ssum[h] = (float)((double)ssum[h] + P * (double)s0);
+    ssum[(size_t)n_hands + h] = (float)((double)ssum[(size_t)n_hands + h] + P * (double)s1);
+}
+// a Discounted CFR tick on the gadget rows: rs_discount_dcfr's three factors, one f32 multiply per cell
+__global__ __launch_bounds__(kBrBlock) void k_br_gadget_discount(float *__restrict__ regret, float *__restrict__ ssum, uint32_t cells, float d_pos, float d_neg, float d_sum) {
+    const uint32_t i = blockIdx.x * kBrBlock + threadIdx.x;
+    if (i >= cells) return;
+    const float r = regret[i];
+    regret[i] = r * (r > 0.0f ? d_pos : d_neg);
+    ssum[i] = ssum[i] * d_sum;
+}
+
 // What a node asks of the device.  The kinds stand in the order of their launches within a tree depth -- reach on the way down, values on the way up -- which traces and
 // br_launches() show.  A new own-node form is a body, a kind here, a line in BrRun::own_kind and a case in BrRun::launch.
 // (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up; the node report: kBrReachOwn on the way down, and after the value
 // job of a requested node kBrMass -- the leaf kernels on the node's q -- and kBrReport)
-enum BrKind { kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread, kBrSum, kBrMass,
-              kBrReport, kBrKinds };
+// (the re-solving gadget: kBrGadgetReach in front of the root's reach on the resolver's sweep, its TERMINATE leaf a kBrMass job on the root; kBrMass and kBrGadgetOwn behind
+// the root's value job on the opponent's sweep)
+enum BrKind { kBrGadgetReach, kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread,
+              kBrSum, kBrMass, kBrReport, kBrGadgetOwn, kBrKinds };
 // launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
 static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal || k == kBrReport; }
 // P, Pc, O and Q of br_terminal_sorted_body
@@ -1571,6 +1670,11 @@ struct BrRun {
     bool ws_pi = false;                       // the workspace has the own-reach rows (a full-width solver's, or one a report has walked on)
     size_t ws_mass_rows = 0;                  // ... and this many mass rows in the level plan (one per depth otherwise)
     std::vector<double *> mass_level;         // ... per tree depth (depth-first walk)
+    // the re-solving gadget of a full-width solver (br_cfr_set_gadget): the resolver (-1 = none), alt[n], the f32 rows regret[2][n] and ssum[2][n] of the opponent's n hands,
+    // the opponent's two scaled reach rows (FOLLOW, TERMINATE) and per side one extra lane row: the mass row on the opponent's sweep, the TERMINATE leaf's on the resolver's
+    int gadget = -1;
+    double *d_g_alt = nullptr, *d_g_qf = nullptr, *d_g_qt = nullptr, *d_g_row[2] = {nullptr, nullptr};
+    float *d_g_regret = nullptr, *d_g_ssum = nullptr;
     bool takes_pi() const { return cfr || report_slot; }   // the traverser's own reach goes down beside q
     uint32_t per_prefix[RS_MAX_ROUNDS] = {1, 1, 1};   // run-outs under a prefix of round r
     int p = 0;
@@ -1662,6 +1766,7 @@ struct BrRun {
         std::vector<int> job_at, sum_at;   // per tree node: its job (leaf, own node, an opponent node's reach) and an opponent node's sum job, -1 = none
         std::vector<int> own_reach_at;     // ... an own node's reach job (full-width sweep, node report)
         std::vector<int> mass_at, report_at;   // ... a requested node's mass and report jobs (node report)
+        int gadget_reach_at = -1, gadget_mass_at = -1, gadget_own_at = -1;   // the gadget's jobs above the root (a full-width solver with a gadget)
         double *root = nullptr;            // where the root's values arrive
     };
     // host only: gives every node its buffers and fills the jobs
@@ -1688,6 +1793,30 @@ struct BrRun {
             entries.push_back({(uint32_t(step) * kBrKinds + kind) * RS_MAX_ROUNDS + uint32_t(br_per_round(kind) ? r : 0), kind, r, int(id)});
             jobs.push_back(j);
         };
+        if (cfr && gadget >= 0) {   // the gadget node above the root; its rows belong to the object, not to the workspace
+            BrJob jm{};
+            jm.v = d_g_row[p];
+            jm.uncontested = 1;
+            if (p == gadget) {   // the resolver's sweep: the opponent enters the tree with its FOLLOW share, the rest meets the TERMINATE leaf
+                BrJob jg{};
+                jg.q = op.d_init_q;
+                jg.q_out = d_g_qf;
+                jg.v = d_g_qt;
+                add(kBrGadgetReach, 0, 0, jg);
+                q_in[0] = d_g_qf;
+                jm.q = d_g_qt;
+                jm.value = -1.0;
+                add(kBrMass, 0, 0, jm);
+            } else {             // the opponent's sweep: the root's mass row, then the gadget's own node over the root row
+                jm.q = op.d_init_q;
+                jm.value = 1.0;
+                add(kBrMass, 0, 0, jm);
+                BrJob jo{};
+                jo.v = pl.root;
+                jo.sum_src[0] = d_g_row[p];
+                add(kBrGadgetOwn, 0, 0, jo);
+            }
+        }
         for (size_t id = 0; id < N; ++id) {   // parents before children: a node's q and v slot are known when it comes up
             const rs_tree_node &n = tree->nodes[id];
             if (n.kind == RS_NODE_TERMINAL) {
@@ -1795,6 +1924,12 @@ struct BrRun {
         pl.jobs.reserve(perm.size());
         for (uint32_t i : perm) {
             const BrPlan::Entry &e = entries[i];
+            if (e.kind == kBrGadgetReach || e.kind == kBrGadgetOwn || (e.kind == kBrMass && cfr)) {   // (a full-width solver's only mass job is the gadget's)
+                (e.kind == kBrGadgetReach ? pl.gadget_reach_at : (e.kind == kBrGadgetOwn ? pl.gadget_own_at : pl.gadget_mass_at)) = int(pl.jobs.size());
+                pl.entries.push_back(e);
+                pl.jobs.push_back(jobs[i]);
+                continue;
+            }
             std::vector<int> &at_of = e.kind == kBrSum ? pl.sum_at : (e.kind == kBrReachOwn ? pl.own_reach_at : (e.kind == kBrMass ? pl.mass_at : (e.kind == kBrReport ? pl.report_at : pl.job_at)));
             at_of[size_t(e.node)] = int(pl.jobs.size());
             pl.entries.push_back(e);
@@ -1962,6 +2097,12 @@ struct BrRun {
             else hipLaunchKernelGGL(k_br_report_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
             break;
         }
+        case kBrGadgetReach:   // one job, whichever tree order: the same launch
+            hipLaunchKernelGGL(k_br_gadget_reach, dim3(grid1(op.n)), block, 0, s, d_g_regret, d_g_alt, op.n_hands, op.n, j.q, j.q_out, j.v);
+            break;
+        case kBrGadgetOwn:
+            hipLaunchKernelGGL(k_br_gadget_own, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, d_g_regret, d_g_ssum, d_g_alt, j.sum_src[0], j.v, cfr_rmplus);
+            break;
         case kBrKinds:   // a count, no kind
             return;
         }
@@ -1993,8 +2134,15 @@ struct BrRun {
         if (int rc = build_plan(pl)) return rc;
         DevBuf<BrJob> d_jobs;
         n_launches = 0;
-        if (!ws_levels) walk(pl, 0);
-        else {   // reach downwards by depth, the leaves in slices of 16 384, values upwards by depth: the plan's order
+        auto one_gadget = [&](int at) {
+            if (at >= 0) launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, nullptr, 1, &pl.jobs[size_t(at)]);
+        };
+        if (!ws_levels) {
+            one_gadget(pl.gadget_reach_at);
+            walk(pl, 0);
+            one_gadget(pl.gadget_mass_at);
+            one_gadget(pl.gadget_own_at);
+        } else {   // reach downwards by depth, the leaves in slices of 16 384, values upwards by depth: the plan's order
             err = d_jobs.alloc(pl.jobs.size());
             if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, pl.jobs.data(), pl.jobs.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
             for (size_t lo = 0, hi; lo < pl.jobs.size() && err == hipSuccess; lo = hi) {
@@ -2004,10 +2152,15 @@ struct BrRun {
             }
         }
         if (err == hipSuccess) err = hipMemcpyAsync(root_host, pl.root, side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
+        if (cfr && gadget == p) {   // the resolver's sweep: the TERMINATE leaf's row comes back beside the root's
+            gadget_term.resize(side[p].n);
+            if (err == hipSuccess) err = hipMemcpyAsync(gadget_term.data(), d_g_row[p], side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
+        }
         const hipError_t done = hipStreamSynchronize(t->stream);   // the plan and d_jobs are freed on return: after an error too, nothing queued may still touch them
         if (err == hipSuccess) err = done;
         return err == hipSuccess ? RS_OK : hip_fail(err, ws_levels ? "rs_best_response (level plan)" : "rs_best_response");
     }
+    std::vector<double> gadget_term;   // the TERMINATE leaf's row of the last resolver's sweep
     int traverse(int traverser, std::vector<double> &root, double *total);
 };
 
@@ -2495,6 +2648,11 @@ int BrRun::traverse(int traverser, std::vector<double> &root, double *total) {
     last_launches += ws_levels ? n_launches : 0;
     double sum = 0.0;
     for (uint32_t l = 0; l < side[p].n; ++l) sum += root[l];
+    if (cfr && gadget == p) {   // plus the TERMINATE branch, summed like a root row
+        double term = 0.0;
+        for (uint32_t l = 0; l < side[p].n; ++l) term += gadget_term[l];
+        sum += term;
+    }
     *total = sum;
     return RS_OK;
 }
@@ -2640,6 +2798,57 @@ int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
     return RS_OK;
 }
 
+// ---- the re-solving gadget on a full-width solver's prepared game ---------------------------------------------------------------------------------------------------
+// Everything that can refuse has refused before anything is written: a refused call leaves the rows and the table alone.
+int br_cfr_set_gadget(BrRun *prepared, int resolver, const double *alt) {
+    if (!prepared || !prepared->cfr || !alt) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: NULL argument");
+    if (resolver != 0 && resolver != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: resolver is 0 or 1");
+    BrRun &run = *prepared;
+    const uint32_t n = run.side[1 - resolver].n_hands;
+    for (uint32_t h = 0; h < n; ++h)
+        if (!std::isfinite(alt[h])) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: alt[" + std::to_string(h) + "] is not finite");
+    rs_table *t = run.t;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    RS_HIP(hipStreamSynchronize(t->stream), "rs_range_cfr_set_gadget");
+    run.err = hipSuccess;
+    if (!run.d_g_alt) {   // first arming: the rows' buffers, kept with the object and sized for either player as the resolver
+        const size_t most = std::max(run.side[0].n_hands, run.side[1].n_hands);
+        double *a = run.dalloc<double>(most), *qf = run.dalloc<double>(run.n_pad_max), *qt = run.dalloc<double>(run.n_pad_max);
+        double *row0 = run.dalloc<double>(run.side[0].n_pad), *row1 = run.dalloc<double>(run.side[1].n_pad);
+        float *rg = run.dalloc<float>(2 * most), *ss = run.dalloc<float>(2 * most);
+        if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr_set_gadget: the gadget's rows");
+        run.d_g_alt = a, run.d_g_qf = qf, run.d_g_qt = qt, run.d_g_row[0] = row0, run.d_g_row[1] = row1, run.d_g_regret = rg, run.d_g_ssum = ss;
+    }
+    RS_HIP(hipMemcpy(run.d_g_alt, alt, size_t(n) * sizeof(double), hipMemcpyHostToDevice), "rs_range_cfr_set_gadget: alt");
+    RS_HIP(hipMemset(run.d_g_regret, 0, size_t(2) * n * sizeof(float)), "rs_range_cfr_set_gadget: the rows");
+    RS_HIP(hipMemset(run.d_g_ssum, 0, size_t(2) * n * sizeof(float)), "rs_range_cfr_set_gadget: the rows");
+    RS_HIP(hipDeviceSynchronize(), "rs_range_cfr_set_gadget");
+    run.gadget = resolver;
+    return RS_OK;
+}
+int br_cfr_gadget_rows(BrRun *prepared, float *regrets, float *strategy_sum, const float *set_regrets, const float *set_strategy_sum, const char *fn) {
+    if (!prepared || !prepared->cfr) return fail(RS_ERR_INVALID, std::string(fn) + ": NULL argument");
+    BrRun &run = *prepared;
+    if (run.gadget < 0) return fail(RS_ERR_INVALID, std::string(fn) + ": the object has no gadget (rs_range_cfr_set_gadget first)");
+    const size_t bytes = size_t(2) * run.side[1 - run.gadget].n_hands * sizeof(float);
+    RS_HIP(hipSetDevice(run.t->device), "hipSetDevice");
+    RS_HIP(hipStreamSynchronize(run.t->stream), fn);
+    if (regrets) RS_HIP(hipMemcpy(regrets, run.d_g_regret, bytes, hipMemcpyDeviceToHost), fn);
+    if (strategy_sum) RS_HIP(hipMemcpy(strategy_sum, run.d_g_ssum, bytes, hipMemcpyDeviceToHost), fn);
+    if (set_regrets) RS_HIP(hipMemcpy(run.d_g_regret, set_regrets, bytes, hipMemcpyHostToDevice), fn);
+    if (set_strategy_sum) RS_HIP(hipMemcpy(run.d_g_ssum, set_strategy_sum, bytes, hipMemcpyHostToDevice), fn);
+    if (set_regrets || set_strategy_sum) RS_HIP(hipDeviceSynchronize(), fn);
+    return RS_OK;
+}
+// a Discounted CFR tick on the gadget rows, on the table's stream behind rs_discount_dcfr's
+static int br_cfr_gadget_discount(BrRun &run, float d_pos, float d_neg, float d_sum) {
+    if (run.gadget < 0) return RS_OK;
+    const uint32_t cells = 2u * run.side[1 - run.gadget].n_hands;
+    hipLaunchKernelGGL(k_br_gadget_discount, dim3(grid1(cells)), dim3(kBrBlock), 0, run.t->stream, run.d_g_regret, run.d_g_ssum, cells, d_pos, d_neg, d_sum);
+    RS_HIP(hipGetLastError(), "rs_range_cfr_train: the gadget's tick");
+    return RS_OK;
+}
+
 }  // namespace rs
 
 struct rs_range_cfr {
@@ -2699,6 +2908,18 @@ int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_param
     if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_train: NULL argument");
     return rs::br_cfr_train(s->run, s->table, s->mode == RS_UPD_RMPLUS, iterations, dcfr, values);
 }
+int rs_range_cfr_set_gadget(rs_range_cfr *s, int resolver, const double *alt) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: NULL argument");
+    return rs::br_cfr_set_gadget(s->run, resolver, alt);
+}
+int rs_range_cfr_gadget_get(const rs_range_cfr *s, float *regrets, float *strategy_sum) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_get: NULL argument");
+    return rs::br_cfr_gadget_rows(s->run, regrets, strategy_sum, nullptr, nullptr, "rs_range_cfr_gadget_get");
+}
+int rs_range_cfr_gadget_set(rs_range_cfr *s, const float *regrets, const float *strategy_sum) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_set: NULL argument");
+    return rs::br_cfr_gadget_rows(s->run, nullptr, nullptr, regrets, strategy_sum, "rs_range_cfr_gadget_set");
+}
 size_t rs_range_cfr_bytes(const rs_range_cfr *s) { return s ? rs::br_held_bytes(s->run) : 0; }
 int rs_range_cfr_launches(const rs_range_cfr *s) { return s ? rs::br_last_launches(s->run) : -1; }
 
@@ -2722,6 +2943,7 @@ int br_cfr_train(BrRun *run, rs_table *t, int rmplus, uint64_t iterations, const
             float f[3];
             if (int rc = rs_dcfr_factors(dcfr->alpha, dcfr->beta, dcfr->gamma, it / dcfr->interval, f)) return rc;
             if (int rc = rs_discount_dcfr(t, f[0], f[1], f[2])) return rc;
+            if (int rc = br_cfr_gadget_discount(*run, f[0], f[1], f[2])) return rc;
         }
     }
     return RS_OK;

@@ -3,8 +3,10 @@
 // state machine of state.rs:86-212, so that table shapes and ActionNode.index numbering match the
 // Rust solver's; or adopts a tree the Rust side already built (rs_tree_from_nodes).
 // No GPU code here: the branchy tree work stays on the host by design.
+#include <algorithm>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "rs_internal.hpp"
 
@@ -286,6 +288,50 @@ int rs_tree_from_nodes(const rs_tree_node *nodes, int n_nodes, rs_tree **out) {
         }
     t->n_action_nodes = n_act;
     *out = t;
+    return RS_OK;
+}
+
+// the subtree below an action node: its nodes keep the trunk's relative order (parents before children), action indices are renumbered in ascending trunk index
+int rs_tree_subtree(const rs_tree *tree, int node, rs_tree **out, int32_t *node_map) {
+    if (!tree || !out) return rs::fail(RS_ERR_INVALID, "rs_tree_subtree: NULL argument");
+    const int N = static_cast<int>(tree->nodes.size());
+    if (node < 0 || node >= N) return rs::fail(RS_ERR_INVALID, "rs_tree_subtree: node id out of range");
+    if (tree->nodes[size_t(node)].kind != RS_NODE_ACTION) return rs::fail(RS_ERR_INVALID, "rs_tree_subtree: the root of a subtree is an action node");
+    std::vector<int> new_id(size_t(N), -1), kept, indices;
+    try {
+        new_id[size_t(node)] = 0;
+        kept.push_back(node);
+        for (int i = node + 1; i < N; ++i) {   // parents come before children
+            const int par = tree->nodes[size_t(i)].parent;
+            if (par < node || new_id[size_t(par)] < 0) continue;
+            new_id[size_t(i)] = static_cast<int>(kept.size());
+            kept.push_back(i);
+        }
+        for (int i : kept)
+            if (tree->nodes[size_t(i)].kind == RS_NODE_ACTION) indices.push_back(tree->nodes[size_t(i)].index);
+        std::sort(indices.begin(), indices.end());
+        std::vector<rs_tree_node> nodes;
+        nodes.reserve(kept.size());
+        const uint8_t round0 = tree->nodes[size_t(node)].round_idx;
+        for (int i : kept) {
+            rs_tree_node nd = tree->nodes[size_t(i)];
+            nd.parent = i == node ? -1 : new_id[size_t(nd.parent)];
+            for (int k = 0; k < nd.n_children; ++k) nd.children[k] = new_id[size_t(nd.children[k])];
+            if (nd.kind == RS_NODE_ACTION) {
+                nd.index = static_cast<int32_t>(std::lower_bound(indices.begin(), indices.end(), nd.index) - indices.begin());
+                nd.round_idx = static_cast<uint8_t>(nd.round_idx - round0);
+            }
+            nodes.push_back(nd);
+        }
+        rs_tree *sub = nullptr;
+        if (int rc = rs_tree_from_nodes(nodes.data(), static_cast<int>(nodes.size()), &sub)) return rc;
+        if (node_map) {
+            for (int i = 0; i < N; ++i) node_map[i] = i < static_cast<int>(kept.size()) ? kept[size_t(i)] : -1;
+        }
+        *out = sub;
+    } catch (const std::bad_alloc &) {
+        return rs::fail(RS_ERR_OOM, "rs_tree_subtree: out of memory");
+    }
     return RS_OK;
 }
 

@@ -93,6 +93,15 @@ class GameTree:
                 out[nd.index] = nd
         return out
 
+    def subtree(self, node):
+        """rs_tree_subtree: the subtree below action node `node` as a GameTree of its own (root 0, action indices renumbered in ascending trunk index, round_idx rebased)
+        and node_map = int32 [its nodes]: the trunk node id of each of them"""
+        h = C.c_void_p()
+        node_map = np.full(max(self.n_nodes, 1), -1, dtype=np.int32)
+        L.check(L.load().rs_tree_subtree(self._h, int(node), C.byref(h), node_map.ctypes.data_as(C.POINTER(C.c_int32))))
+        sub = GameTree(h)
+        return sub, node_map[: sub.n_nodes].copy()
+
     def __del__(self):
         try:
             L.load().rs_tree_destroy(self._h)
@@ -984,7 +993,7 @@ class RangeCFR:
     def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True, weights=None, deal="sequential"):
         self.table, self.tree = table, tree
         self._b = np.ascontiguousarray(board0, dtype=np.uint8)
-        (self._h0, self._h1), cl, self._w, _ = drop_zero_weights((hands0, hands1), clusters, weights)   # weights, deal: as InfosetTable.best_response_rounds
+        (self._h0, self._h1), cl, self._w, self._keep = drop_zero_weights((hands0, hands1), clusters, weights)   # weights, deal: as InfosetTable.best_response_rounds
         self._cl = [c for row in cl for c in row]
         self._deal = deal
         self._sorted, self._rmplus, self._hs = bool(sorted_showdowns), bool(rmplus), {}
@@ -999,6 +1008,8 @@ class RangeCFR:
                                                           arr, len(self._cl) // 2, _range_weights(self._w, self._deal),
                                                           C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
             self._hs[rmplus] = h
+            if getattr(self, "_gadget", None) is not None:      # a handle created after set_gadget starts armed, from zero rows
+                L.check(L.load().rs_range_cfr_set_gadget(h, self._gadget[0], _vp(self._gadget[1])))
         self._last = self._hs[rmplus]
         return self._last
 
@@ -1013,6 +1024,41 @@ class RangeCFR:
         out = np.zeros(2, dtype=np.float64)
         L.check(L.load().rs_range_cfr_train(self._handle(rmplus), int(iterations), _dcfr_arg(dcfr), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def set_gadget(self, resolver, alt):
+        """rs_range_cfr_set_gadget: arms the re-solving gadget above the root -- player 1 - resolver chooses per hand between alt[h] (TERMINATE) and the tree (FOLLOW);
+        alt = one float64 per hand of that player as handed to the constructor (hands of weight 0 dropped with the range).  Zeroes the gadget rows of every update rule."""
+        keep = self._keep[1 - int(resolver)] if int(resolver) in (0, 1) else None
+        alt = np.ascontiguousarray(alt, dtype=np.float64).reshape(-1)
+        if keep is not None and len(alt) == len(keep):
+            alt = np.ascontiguousarray(alt[keep])
+        n = len((self._h0, self._h1)[1 - int(resolver)]) if int(resolver) in (0, 1) else len(alt)
+        if len(alt) != n:
+            raise ValueError("one alt per hand of the opponent: %d for %d hands" % (len(alt), n))
+        for h in self._hs.values():
+            L.check(L.load().rs_range_cfr_set_gadget(h, int(resolver), _vp(alt)))
+        self._gadget = (int(resolver), alt)
+
+    def gadget(self, rmplus=None):
+        """rs_range_cfr_gadget_get -> (regrets, ssum), float32 [2][n]: row 0 TERMINATE, row 1 FOLLOW"""
+        h = self._handle(rmplus)
+        n = len((self._h0, self._h1)[1 - self._gadget[0]]) if getattr(self, "_gadget", None) is not None else 0
+        r, s = np.zeros((2, n), dtype=np.float32), np.zeros((2, n), dtype=np.float32)
+        L.check(L.load().rs_range_cfr_gadget_get(h, _vp(r), _vp(s)))
+        return r, s
+
+    def set_gadget_rows(self, regrets=None, ssum=None, rmplus=None):
+        """rs_range_cfr_gadget_set: float32 [2][n] each, None = leave that array"""
+        h = self._handle(rmplus)
+        n = len((self._h0, self._h1)[1 - self._gadget[0]]) if getattr(self, "_gadget", None) is not None else 0
+        rows = []
+        for x in (regrets, ssum):
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=np.float32)
+                if x.shape != (2, n):
+                    raise ValueError("gadget rows are float32 [2][%d]" % n)
+            rows.append(x)
+        L.check(L.load().rs_range_cfr_gadget_set(h, None if rows[0] is None else _vp(rows[0]), None if rows[1] is None else _vp(rows[1])))
 
     @property
     def nbytes(self):
