@@ -54,7 +54,9 @@ extern "C" {
                                  additions only: the calls without weights take the code path they took;
                                  still 6: safe subgame re-solving: rs_tree_subtree, the re-solving gadget of a full-width solver (rs_range_cfr_set_gadget,
                                  rs_range_cfr_gadget_get, rs_range_cfr_gadget_set) -- additions only: an object without a gadget builds the plan it built and returns the bits it
-                                 returned */
+                                 returned;
+                                 still 6: node locks (rs_node_locks, rs_node_lock_size, rs_best_response_locked, rs_node_report_locked, rs_range_cfr_create_locked) -- additions
+                                 only: a call without locks builds the plan it built and returns the bits it returned */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -406,6 +408,44 @@ int rs_range_cfr_gadget_get(const rs_range_cfr *s, float *regrets /* [2][n] */, 
 int rs_range_cfr_gadget_set(rs_range_cfr *s, const float *regrets, const float *strategy_sum);
 size_t rs_range_cfr_bytes(const rs_range_cfr *s);
 int rs_range_cfr_launches(const rs_range_cfr *s);
+
+/* ---- node locks: a player's per-hand strategy fixed at chosen action nodes (an extension) ---------------
+ * "At this node this player plays THIS", per hand; everything around it is solved, measured and inspected as before.  A lock of action node n (round r, A actions, acted
+ * by player P) is a HOST array sigma[(a * n_prefix + f) * n_hands + h], a < A, f over the prefixes of round r in the node report's order (rs_br_runouts: the first r new
+ * cards of a run-out, the first most significant), h over P's hands: the granularity of the re-solving gadget and the layout of a node report's rows, so that a lock
+ * can be built from a report.  In every walk -- rs_best_response_locked, rs_node_report_locked, the sweeps of an object of rs_range_cfr_create_locked -- whichever player
+ * traverses and whatever the mode, with lane = b * n_hands + h and f = b / (run-outs under a prefix of round r):
+ *   P is the opponent:   child a's reach is q[lane] * sigma[a][f][h], one f64 multiply; the node's value is the sum of its children's values in action order, as without
+ *                        a lock.
+ *   P is the traverser:  v[lane] = sum_a sigma[a][f][h] * vch[a][lane], f64, a ascending from 0.0; 0.0 on a lane that is no deal (the hand holds a card of the run-out),
+ *                        as every own node writes.  Under RS_BR_MAX (with or without RS_BR_REAL) nothing is maximised there: the result is the best response of
+ *                        everything that is not locked.  A full-width sweep reads and writes neither the regret row nor the strategy-sum row of the node; the children's
+ *                        own reach is pi[lane] * sigma[a][f][h].  A node report at a locked node reports cfv, mass and own as usual and v by the lock.
+ * RS_BR_CURRENT / RS_BR_AVERAGE choose the table array for the nodes that are NOT locked only.  Discounted CFR ticks (rs_discount_dcfr, rs_range_cfr_train) still multiply
+ * the whole table, a locked node's rows included: harmless, nothing reads them.  The rows are used as given, nothing is renormalised.  WHOLE nodes only: locking some hands
+ * of a node and leaving the others free is out of scope (the free hands' info sets would need their lanes' sums without the locked lanes).
+ * Checked before anything is allocated or the table is settled -- a refused call returns RS_ERR_INVALID and leaves outputs and table alone: a node id that is out of range
+ * or no action node; an id given twice; a NULL row; an entry that is not finite or is < 0; |sum_a sigma[a][f][h] - 1| > 1e-9 (a ascending from 0.0) for a (prefix, hand)
+ * pair that shares no card.  Pairs that do share a card are not sum-checked, and their entries are never used for a deal.
+ * locks == NULL or n == 0 is the _weighted call in every respect: the same bits, the same launches, the same rs_range_cfr_bytes.  The rows are copied to the device
+ * when the game is prepared (counted in rs_range_cfr_bytes) and need not outlive the call.  rs_range_cfr_set_gadget on an object created with locks returns
+ * RS_ERR_UNSUPPORTED: a gadget and locks on one object are out of scope.  The rs_deal_trainer_* forms and the sampled trainer stay unlocked.
+ * rs_node_lock_size: the doubles of node's lock, A * n_prefix * n_hands_actor; 0 with rs_last_error set on bad arguments; host only. */
+typedef struct rs_node_locks {
+    uint32_t n;                   /* locked action nodes; 0 = none */
+    const int32_t *nodes;         /* [n] tree node ids (rs_tree_get_node), distinct action nodes */
+    const double *const *sigma;   /* [n] HOST arrays, rs_node_lock_size doubles each */
+} rs_node_locks;
+size_t rs_node_lock_size(const rs_tree *tree, int n_board0, size_t n_hands_actor, int node);
+int rs_best_response_locked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                            const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
+                            const rs_node_locks *locks, int mode, double *out /*[2]*/);
+int rs_node_report_locked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                          size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, int mode,
+                          int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
+int rs_range_cfr_create_locked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                               const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
+                               const rs_node_locks *locks, const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
 
 /* ---- iterate: MCCFRTrainer (cfr.rs) ------------------------------------------------------------
  * Lane model: lane (board b, cluster c) is one scalar cfr() traversal (cfr.rs:481-627)

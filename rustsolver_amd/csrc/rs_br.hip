@@ -12,6 +12,8 @@
 //  * rs_range_cfr_*: full-width CFR over the hand ranges on the same walk (the opponent plays the current strategy, the traverser's own nodes keep their info sets' sums as
 //    regrets): three more job kinds of the best response's job table and launcher.  RS_BR_CURRENT hands the readers the regret array.
 //  * rs_range_cfr_set_gadget: the re-solving gadget above the root of a full-width solver's tree (safe subgame re-solving): two more job kinds.
+//  * rs_node_locks: a player's per-hand strategy fixed at chosen action nodes: the locks' rows live with the prepared game, a locked node takes two more
+//    job kinds in place of its reach and value jobs, in all three walks.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1611,14 +1613,83 @@ __global__ __launch_bounds__(kBrBlock) void k_br_gadget_discount(float *__restri
     ssum[i] = ssum[i] * d_sum;
 }
 
+// ---- node locks (rs_node_locks): an action node whose acting player plays a given per-hand strategy, lock[(a * n_prefix + f) * n_hands + h] -------------------------
+// Two element-wise kernels in plain lane order, a thread per lane = b * n_hands + h: the reach that comes in, the A lock values of the lane's (prefix, hand) pair
+// (f = b / pp, pp the run-outs under a prefix of the node's round) and the A rows of q_out / vch are unit-stride 8-byte accesses.  Nothing is gathered by cluster id, so
+// no XCD slicing.  An early-round node's lock (A * n_prefix * n_hands doubles) stays in cache; a last-round node's rows are as long as a lane row.  Everything indexed
+// by the action is unrolled to RS_MAX_ACTIONS under the action count as a predicate (current_sigma's reason: indexed by a run-time count it becomes scratch).
+// reach, either side: out[a][lane] = in[lane] * lock[a][f][h].  The opponent's q at its locked node and the traverser's own pi at its own (full-width sweep, node report).
+// A lane that is no deal takes whatever the lock holds there, as k_br_opp_reach takes cluster 0's strategy: its reach is never looked at.
+__device__ __forceinline__ void br_lock_reach_body(const double *__restrict__ lock, uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions,
+                                                   const double *__restrict__ in, double *__restrict__ out /*[A][n_pad]*/) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    const uint32_t b = lane / n_hands, h = lane - b * n_hands;
+    const size_t n_pairs = (size_t)(n / n_hands / pp) * n_hands, pair = (size_t)(b / pp) * n_hands + h;
+    const double x = in[lane];
+    double s[RS_MAX_ACTIONS];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++) s[a] = (uint32_t)a < n_actions ? lock[(size_t)a * n_pairs + pair] : 0.0;   // every lock value on its way before the first store
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < n_actions) out[(size_t)a * n_pad + lane] = x * s[a];
+}
+// the traverser's locked node on the way up: v[lane] = sum_a lock[a][f][h] * vch[a][lane], a ascending from 0.0; 0.0 where the lane is no deal (what k_br_own* and
+// k_br_cfr_own* leave there).  Nothing is maximised and no table row is touched.
+__device__ __forceinline__ void br_lock_value_body(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, const double *__restrict__ lock, uint32_t pp,
+                                                   uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch,
+                                                   double *__restrict__ v) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    const uint32_t b = lane / n_hands, h = lane - b * n_hands;
+    if (mask_p[h] & bmask[b]) {
+        v[lane] = 0.0;
+        return;
+    }
+    const size_t n_pairs = (size_t)(n / n_hands / pp) * n_hands, pair = (size_t)(b / pp) * n_hands + h;
+    double s[RS_MAX_ACTIONS], t[RS_MAX_ACTIONS];
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++) {   // every value on its way before the first addition
+        s[a] = (uint32_t)a < n_actions ? lock[(size_t)a * n_pairs + pair] : 0.0;
+        t[a] = (uint32_t)a < n_actions ? vch[(size_t)a * n_pad + lane] : 0.0;
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int a = 0; a < RS_MAX_ACTIONS; a++)
+        if ((uint32_t)a < n_actions) acc += s[a] * t[a];
+    v[lane] = acc;
+}
+// a lock job (kBrLockReach, kBrLockValue): sum_src[0] = the lock's rows on the device, n_clusters = pp, n_children = A; a reach job carries its side's shape with it (one
+// launch takes the opponent's q jobs and the traverser's pi jobs of a depth): n_sets = n_hands, kmax = the side's lanes, row.pitch = its n_pad
+__global__ __launch_bounds__(kBrBlock) void k_br_lock_reach(const double *__restrict__ lock, uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions,
+                                                            const double *__restrict__ in, double *__restrict__ out) {
+    br_lock_reach_body(lock, pp, n_hands, n, n_pad, n_actions, in, out);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_lock_reach_jobs(const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_lock_reach_body(jp->sum_src[0], jp->n_clusters, jp->n_sets, jp->kmax, jp->row.pitch, jp->n_children, jp->q, jp->q_out);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_lock_value(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, const double *__restrict__ lock,
+                                                            uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch,
+                                                            double *__restrict__ v) {
+    br_lock_value_body(mask_p, bmask, lock, pp, n_hands, n, n_pad, n_actions, vch, v);
+}
+__global__ __launch_bounds__(kBrBlock) void k_br_lock_value_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
+                                                                 uint32_t n_pad, const BrJob *__restrict__ jobs) {
+    const BrJob *__restrict__ jp = jobs + blockIdx.y;
+    br_lock_value_body(mask_p, bmask, jp->sum_src[0], jp->n_clusters, n_hands, n, n_pad, jp->n_children, jp->vch, jp->v);
+}
+
 // What a node asks of the device.  The kinds stand in the order of their launches within a tree depth -- reach on the way down, values on the way up -- which traces and
 // br_launches() show.  A new own-node form is a body, a kind here, a line in BrRun::own_kind and a case in BrRun::launch.
 // (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up; the node report: kBrReachOwn on the way down, and after the value
 // job of a requested node kBrMass -- the leaf kernels on the node's q -- and kBrReport)
 // (the re-solving gadget: kBrGadgetReach in front of the root's reach on the resolver's sweep, its TERMINATE leaf a kBrMass job on the root; kBrMass and kBrGadgetOwn behind
 // the root's value job on the opponent's sweep)
-enum BrKind { kBrGadgetReach, kBrReachGrouped, kBrReach, kBrReachOwn, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread, kBrOwnThread,
-              kBrSum, kBrMass, kBrReport, kBrGadgetOwn, kBrKinds };
+// (node locks: a locked node takes kBrLockReach where it would take a reach kind -- the opponent's q, and the traverser's pi where that goes down -- and kBrLockValue where it
+// would take an own-node kind; they sort with those: the last reach kind in front of kBrLeaf, the last own-node kind in front of kBrSum)
+enum BrKind { kBrGadgetReach, kBrReachGrouped, kBrReach, kBrReachOwn, kBrLockReach, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread,
+              kBrOwnThread, kBrLockValue, kBrSum, kBrMass, kBrReport, kBrGadgetOwn, kBrKinds };
 // launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
 static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal || k == kBrReport; }
 // P, Pc, O and Q of br_terminal_sorted_body
@@ -1675,6 +1746,10 @@ struct BrRun {
     int gadget = -1;
     double *d_g_alt = nullptr, *d_g_qf = nullptr, *d_g_qt = nullptr, *d_g_row[2] = {nullptr, nullptr};
     float *d_g_regret = nullptr, *d_g_ssum = nullptr;
+    // node locks (rs_node_locks): per tree node its lock's rows [A][prefixes of its round][hands of the acting player] on the device (dalloc: the game-only half), nullptr =
+    // not locked; empty when the game has no lock at all
+    std::vector<const double *> lock_of;
+    const double *lock_at(size_t id) const { return lock_of.empty() ? nullptr : lock_of[id]; }
     bool takes_pi() const { return cfr || report_slot; }   // the traverser's own reach goes down beside q
     uint32_t per_prefix[RS_MAX_ROUNDS] = {1, 1, 1};   // run-outs under a prefix of round r
     int p = 0;
@@ -1793,6 +1868,18 @@ struct BrRun {
             entries.push_back({(uint32_t(step) * kBrKinds + kind) * RS_MAX_ROUNDS + uint32_t(br_per_round(kind) ? r : 0), kind, r, int(id)});
             jobs.push_back(j);
         };
+        auto lock_reach = [&](const double *lock, int r, const BrSide &s, const double *in, double *out, uint32_t n_children) {   // a kBrLockReach job on side s's lanes
+            BrJob jl{};
+            jl.sum_src[0] = lock;
+            jl.n_clusters = per_prefix[r];
+            jl.n_sets = s.n_hands;
+            jl.kmax = s.n;
+            jl.row.pitch = s.n_pad;
+            jl.q = in;
+            jl.q_out = out;
+            jl.n_children = n_children;
+            return jl;
+        };
         if (cfr && gadget >= 0) {   // the gadget node above the root; its rows belong to the object, not to the workspace
             BrJob jm{};
             jm.v = d_g_row[p];
@@ -1844,7 +1931,19 @@ struct BrRun {
             j.vch = vch;
             j.v = v_out[id];
             j.n_children = uint32_t(n.n_children);
-            if (int(n.player) == p) {
+            const double *const lock = lock_at(id);
+            if (lock && int(n.player) == p) {   // a locked own node: its value by the lock, never a fold, nothing of the table read -- its opponent children get their kBrSum jobs
+                j.sum_src[0] = lock;
+                j.n_clusters = per_prefix[r];
+                if (takes_pi()) {
+                    double *pch = ws_levels ? slot(size_t(n.n_children) * me.n_pad) : pi_level[size_t(d)];
+                    add(kBrLockReach, r, id, lock_reach(lock, r, me, pi_in[id], pch, j.n_children));
+                    j.q = pi_in[id];
+                    for (int a = 0; a < n.n_children; ++a) pi_in[size_t(n.children[a])] = pch + size_t(a) * me.n_pad;
+                }
+                add(kBrLockValue, r, id, j);
+                for (int a = 0; a < n.n_children; ++a) q_in[size_t(n.children[a])] = q_in[id];
+            } else if (int(n.player) == p) {
                 const BrKind kind = own_kind(r);
                 j.start = me.d_start[r];
                 j.order = me.d_order[r];
@@ -1875,7 +1974,9 @@ struct BrRun {
                 j.cid = op.d_cid[r];
                 j.q = q_in[id];
                 j.q_out = qch;
-                add(reach_kind(r), r, id, j);
+                // a locked opponent node: its children's reach by the lock; its value stays the sum of theirs (kBrSum below, or the parent's fold)
+                if (lock) add(kBrLockReach, r, id, lock_reach(lock, r, op, q_in[id], qch, j.n_children));
+                else add(reach_kind(r), r, id, j);
                 // its value is the sum of its children's; where the parent folds, that kernel adds the rows up as it loads them
                 const int par = n.parent;
                 bool taken = false;
@@ -1930,7 +2031,8 @@ struct BrRun {
                 pl.jobs.push_back(jobs[i]);
                 continue;
             }
-            std::vector<int> &at_of = e.kind == kBrSum ? pl.sum_at : (e.kind == kBrReachOwn ? pl.own_reach_at : (e.kind == kBrMass ? pl.mass_at : (e.kind == kBrReport ? pl.report_at : pl.job_at)));
+            const bool own_reach = e.kind == kBrReachOwn || (e.kind == kBrLockReach && int(tree->nodes[size_t(e.node)].player) == p);   // (a locked opponent node's reach is its job)
+            std::vector<int> &at_of = e.kind == kBrSum ? pl.sum_at : (own_reach ? pl.own_reach_at : (e.kind == kBrMass ? pl.mass_at : (e.kind == kBrReport ? pl.report_at : pl.job_at)));
             at_of[size_t(e.node)] = int(pl.jobs.size());
             pl.entries.push_back(e);
             pl.jobs.push_back(jobs[i]);
@@ -2082,6 +2184,15 @@ struct BrRun {
             hipLaunchKernelGGL(k, dim3(grid1(most(n_clusters)), nj), block, 0, s, ssum, d_jobs, me.n_pad, mode);
             break;
         }
+        case kBrLockReach:   // the jobs carry their side's shape: the grid is sized by the longest lane row
+            if (!d_jobs) hipLaunchKernelGGL(k_br_lock_reach, dim3(grid1(j.kmax)), block, 0, s, j.sum_src[0], j.n_clusters, j.n_sets, j.kmax, j.row.pitch, j.n_children, j.q, j.q_out);
+            else hipLaunchKernelGGL(k_br_lock_reach_jobs, dim3(grid1(most([](const BrJob &j) { return j.kmax; })), nj), block, 0, s, d_jobs);
+            break;
+        case kBrLockValue:
+            if (!d_jobs)
+                hipLaunchKernelGGL(k_br_lock_value, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, j.sum_src[0], j.n_clusters, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v);
+            else hipLaunchKernelGGL(k_br_lock_value_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
+            break;
         case kBrSum:
             if (!d_jobs) hipLaunchKernelGGL(k_br_sum, dim3(grid1(me.n)), block, 0, s, j.vch, j.n_children, me.n, me.n_pad, j.v);
             else hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), block, 0, s, d_jobs, me.n, me.n_pad);
@@ -2417,8 +2528,73 @@ int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t 
     return RS_OK;
 }
 
+// ---- node locks: the shape of a lock and the refusals, host only -----------------------------------------------------------------------------------------------------
+// the doubles of `node`'s lock, A * (prefixes of its round) * n_hands of the acting player; 0 and rs_last_error on bad arguments.  *prefixes (may be NULL): the middle factor
+static size_t br_lock_layout(const rs_tree *tree, int n_board0, size_t n_hands, int node, size_t *prefixes) {
+    const auto bad = [](const std::string &why) {
+        (void)fail(RS_ERR_INVALID, "rs_node_locks: " + why);
+        return size_t(0);
+    };
+    if (!tree) return bad("NULL argument");
+    if (n_board0 < 3 || n_board0 > 5) return bad("the initial board has 3, 4 or 5 cards");
+    if (n_hands == 0 || n_hands > 1326) return bad("1..1326 hands in the acting player's range");
+    if (node < 0 || size_t(node) >= tree->nodes.size()) return bad("node id " + std::to_string(node) + " is out of range");
+    const rs_tree_node &n = tree->nodes[size_t(node)];
+    if (n.kind != RS_NODE_ACTION) return bad("node " + std::to_string(node) + " is not an action node");
+    const int K = 5 - n_board0, D = 52 - n_board0;
+    if (n.n_children < 1 || n.n_children > RS_MAX_ACTIONS || int(n.round_idx) > K || n.player > 1) return bad("node " + std::to_string(node) + " has no place in a game from this board");
+    size_t f = 1;
+    for (int i = 0; i < int(n.round_idx); ++i) f *= size_t(D - i);
+    if (prefixes) *prefixes = f;
+    return size_t(n.n_children) * f * n_hands;
+}
+
+int br_check_locks(const rs_node_locks *locks, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                   size_t n_hands_p1) {
+    if (!locks || locks->n == 0) return RS_OK;
+    if (!tree || !board0 || !hands_p0 || !hands_p1 || !locks->nodes || !locks->sigma) return fail(RS_ERR_INVALID, "rs_node_locks: NULL argument");
+    if (n_board0 < 3 || n_board0 > 5) return fail(RS_ERR_INVALID, "rs_node_locks: the initial board has 3, 4 or 5 cards");
+    const uint8_t *hands[2] = {hands_p0, hands_p1};
+    const size_t n_hands[2] = {n_hands_p0, n_hands_p1};
+    std::vector<uint8_t> cards;   // the run-outs: prefix f of round r is the first r new cards of run-out f * (run-outs under a prefix of round r)
+    const size_t NB = enumerate_runouts(board0, n_board0, &cards);
+    std::vector<char> seen(tree->nodes.size(), 0);
+    for (uint32_t k = 0; k < locks->n; ++k) {
+        const int32_t id = locks->nodes[k];
+        size_t F = 0;
+        const size_t actor_hands = id >= 0 && size_t(id) < tree->nodes.size() ? n_hands[tree->nodes[size_t(id)].player & 1] : 1;
+        const size_t total = br_lock_layout(tree, n_board0, actor_hands, id, &F);
+        if (!total) return RS_ERR_INVALID;
+        if (seen[size_t(id)]) return fail(RS_ERR_INVALID, "rs_node_locks: node " + std::to_string(id) + " is locked twice");
+        seen[size_t(id)] = 1;
+        const double *row = locks->sigma[k];
+        if (!row) return fail(RS_ERR_INVALID, "rs_node_locks: the row of node " + std::to_string(id) + " is NULL");
+        const rs_tree_node &n = tree->nodes[size_t(id)];
+        const size_t H = actor_hands, A = size_t(n.n_children), pp = NB / F;
+        for (size_t i = 0; i < total; ++i)
+            if (!std::isfinite(row[i]) || row[i] < 0.0)
+                return fail(RS_ERR_INVALID, "rs_node_locks: entry " + std::to_string(i) + " of node " + std::to_string(id) + " is not finite and >= 0");
+        for (size_t f = 0; f < F; ++f) {
+            uint64_t pm = 0;   // the prefix's new cards
+            for (int i = 0; i < int(n.round_idx); ++i) pm |= 1ull << cards[f * pp * 5 + size_t(n_board0 + i)];
+            for (size_t h = 0; h < H; ++h) {
+                const uint8_t c0 = hands[n.player][2 * h], c1 = hands[n.player][2 * h + 1];
+                if (c0 >= 52 || c1 >= 52) return fail(RS_ERR_INVALID, "rs_best_response: bad hole cards in a range");
+                if (pm & (1ull << c0 | 1ull << c1)) continue;   // the pair shares a card: no deal, not sum-checked, never used
+                double sum = 0.0;
+                for (size_t a = 0; a < A; ++a) sum += row[(a * F + f) * H + h];
+                if (!(std::fabs(sum - 1.0) <= 1e-9))
+                    return fail(RS_ERR_INVALID, "rs_node_locks: the strategy of node " + std::to_string(id) + " at prefix " + std::to_string(f) + ", hand " + std::to_string(h) +
+                                                    " sums to " + std::to_string(sum) + ", not to 1");
+            }
+        }
+    }
+    return RS_OK;
+}
+
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
-               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights, BrRun **prepared) {
+               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights, BrRun **prepared,
+               const rs_node_locks *locks /* checked by the caller: br_check_locks */) {
     if (!t || !tree || !board0 || !hands_p0 || !hands_p1 || !cluster || !prepared) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     *prepared = nullptr;
     if (int rc = br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc;
@@ -2575,6 +2751,14 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
         double *d_ones = run.upload(ones);
         run.side[0].d_init_q = run.side[0].d_pw = d_w0;
         run.side[1].d_init_q = run.side[1].d_pw = d_ones;
+    }
+    if (locks && locks->n) {   // the locks' rows: buffers of the prepared game (no slots of the walk's workspace), as given
+        run.lock_of.assign(tree->nodes.size(), nullptr);
+        for (uint32_t k = 0; k < locks->n; ++k) {
+            const int32_t id = locks->nodes[k];
+            const size_t total = br_lock_layout(tree, n_board0, n_hands[tree->nodes[size_t(id)].player], id, nullptr);
+            run.lock_of[size_t(id)] = run.upload(std::vector<double>(locks->sigma[k], locks->sigma[k] + total));
+        }
     }
     // the walk's buffers are allocated by every call (br_execute) and freed when it returns: a kept object holds what depends on the game only
     run.n_pad_max = std::max(run.side[0].n_pad, run.side[1].n_pad);
@@ -2804,6 +2988,7 @@ int br_cfr_set_gadget(BrRun *prepared, int resolver, const double *alt) {
     if (!prepared || !prepared->cfr || !alt) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: NULL argument");
     if (resolver != 0 && resolver != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: resolver is 0 or 1");
     BrRun &run = *prepared;
+    if (!run.lock_of.empty()) return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_set_gadget: the object was created with node locks (a gadget and locks on one object are out of scope)");
     const uint32_t n = run.side[1 - resolver].n_hands;
     for (uint32_t h = 0; h < n; ++h)
         if (!std::isfinite(alt[h])) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: alt[" + std::to_string(h) + "] is not finite");
@@ -2861,15 +3046,21 @@ extern "C" {
 
 int rs_range_cfr_create(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                         size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_cfr_params *params, rs_range_cfr **out) {
-    return rs_range_cfr_create_weighted(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, nullptr, params, out);
+    return rs_range_cfr_create_locked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, nullptr, nullptr, params, out);
 }
 int rs_range_cfr_create_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                                  size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_range_cfr_params *params,
                                  rs_range_cfr **out) {
+    return rs_range_cfr_create_locked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, nullptr, params, out);
+}
+int rs_range_cfr_create_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks,
+                               const rs_range_cfr_params *params, rs_range_cfr **out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
     *out = nullptr;
     if (!t) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
     if (int rc_ = rs::br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc_;   // before the table is settled: a refused call writes nothing
+    if (int rc_ = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc_;
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate): the index kernels go to the table's stream
     const int mode = params ? params->mode : 0;
     if (mode != 0 && mode != RS_UPD_RMPLUS) return fail(RS_ERR_INVALID, "rs_range_cfr_create: params->mode is 0 or RS_UPD_RMPLUS");
@@ -2878,7 +3069,7 @@ int rs_range_cfr_create_weighted(rs_table *t, const rs_tree *tree, const uint8_t
         return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_create: RS_F32 tables only (the sums are per-deal probabilities times pots: no integer scale, and binary16 cells are out of scope)");
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, !params || params->sorted != RS_FORM_OFF, weights,
-                                &run))
+                                &run, locks))
         return rc;
     if (int rc = rs::br_cfr_mark(run)) {
         rs::br_free(run);
@@ -2960,12 +3151,21 @@ int rs_best_response_rounds(rs_table *t, const rs_tree *tree, const uint8_t *boa
 
 int rs_best_response_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                               size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode, double *out) {
+    return rs_best_response_locked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, nullptr, mode, out);
+}
+
+size_t rs_node_lock_size(const rs_tree *tree, int n_board0, size_t n_hands_actor, int node) { return rs::br_lock_layout(tree, n_board0, n_hands_actor, node, nullptr); }
+
+int rs_best_response_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                            size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, int mode,
+                            double *out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
     if (int rc = rs::br_check_mode(mode & ~(RS_BR_REAL | RS_BR_CURRENT), (mode & RS_BR_REAL) != 0)) return rc;
+    if (int rc = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc;   // before anything is allocated
     rs::BrRun *run = nullptr;
-    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run)) return rc;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
     const int rc = rs::br_execute(run, mode, out);
     rs::br_free(run);
     return rc;
@@ -2985,15 +3185,23 @@ int rs_node_report(rs_table *t, const rs_tree *tree, const uint8_t *board0, int 
 int rs_node_report_weighted(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                             size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, int mode, int traverser, const int32_t *nodes,
                             size_t n_nodes, double *out, size_t out_doubles) {
+    return rs_node_report_locked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, nullptr, mode, traverser, nodes, n_nodes, out,
+                                 out_doubles);
+}
+
+int rs_node_report_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                          size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, int mode, int traverser,
+                          const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
     if (!out) return fail(RS_ERR_INVALID, "rs_node_report: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
     if (int rc = rs::br_report_check_mode(mode, traverser)) return rc;
+    if (int rc = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc;   // before anything is allocated
     const size_t total = rs::br_report_layout(tree, n_board0, traverser == 0 ? n_hands_p0 : n_hands_p1, nodes, n_nodes, nullptr);   // before the game is prepared: a bad request costs nothing
     if (!total) return RS_ERR_INVALID;
     if (out_doubles < total) return fail(RS_ERR_INVALID, "rs_node_report: the output buffer is too small (rs_node_report_size doubles)");
     rs::BrRun *run = nullptr;
-    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run)) return rc;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
     const int rc = rs::br_report(run, mode, traverser, nodes, n_nodes, out, out_doubles);
     rs::br_free(run);
     return rc;

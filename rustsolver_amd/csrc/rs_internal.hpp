@@ -131,8 +131,12 @@ struct CompactJob {
 // best response over run-outs (rs_br.hip): what depends on the game only is prepared once, the walk runs against the table as it stands
 struct BrRun;
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
-               const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights /* NULL = every hand counts the same */, BrRun **prepared);
+               const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights /* NULL = every hand counts the same */, BrRun **prepared,
+               const rs_node_locks *locks = nullptr /* NULL or n == 0 = no node is locked; the caller has put them through br_check_locks */);
 int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t n_hands_p1);   // RS_ERR_INVALID as the header lists; touches nothing
+// rs_node_locks as the header states them (NULL or n == 0: nothing to check, whatever the other arguments are); RS_ERR_INVALID; touches nothing
+int br_check_locks(const rs_node_locks *locks, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                   size_t n_hands_p1);
 int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVERAGE */, double *out /* [2] */);
 // one traverser's node report (rs_node_report) on the prepared game; mode without RS_BR_SORTED.  A workspace that lacks the report's rows is traded for a larger one
 int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
