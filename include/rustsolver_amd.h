@@ -56,7 +56,9 @@ extern "C" {
                                  rs_range_cfr_gadget_get, rs_range_cfr_gadget_set) -- additions only: an object without a gadget builds the plan it built and returns the bits it
                                  returned;
                                  still 6: node locks (rs_node_locks, rs_node_lock_size, rs_best_response_locked, rs_node_report_locked, rs_range_cfr_create_locked) -- additions
-                                 only: a call without locks builds the plan it built and returns the bits it returned */
+                                 only: a call without locks builds the plan it built and returns the bits it returned;
+                                 still 6: rake (rs_rake, rs_rake_payoffs, rs_best_response_raked, rs_node_report_raked, rs_range_cfr_create_raked) -- additions only: a call
+                                 without rake runs the code it ran and returns the bits it returned */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -226,7 +228,9 @@ int rs_calc_br(rs_table *table, const rs_tree *tree, float *out /*[2]*/);
  * utilities (cfr.rs:314-348), of player p against the opponent's AVERAGE strategy when p plays
  *   RS_BR_MAX      a best response inside the abstraction (one action per info set = cluster), or
  *   RS_BR_AVERAGE  its own average strategy (out[0] + out[1] = 0: the game is zero-sum),
- * so (out[0] + out[1]) / 2 under RS_BR_MAX is the exploitability of the average strategy profile.  Vector form over both ranges
+ * so (out[0] + out[1]) / 2 under RS_BR_MAX is the exploitability of the average strategy profile.
+ * (With rake -- rs_best_response_raked below -- the game is GENERAL-SUM: under RS_BR_AVERAGE -(out[0] + out[1]) is the expected rake per deal, and the exploitability of a
+ * profile takes two calls: ((max[0] - avg[0]) + (max[1] - avg[1])) / 2, max the RS_BR_MAX result, avg the RS_BR_AVERAGE one.)  Vector form over both ranges
  * of a single-round tree on a full board (the configuration main.rs runs): deals weigh as generate_hand draws them (cfr.rs:124-137),
  * hands[n][2] hole cards, cluster[n] = get_cluster(hole cards + board, player) of every hand, board[5].  f64 on the device, every sum
  * in a fixed order.  Host pointers; synchronises the table's stream.  RS_ERR_UNSUPPORTED for trees with public chance nodes. */
@@ -446,6 +450,37 @@ int rs_node_report_locked(rs_table *table, const rs_tree *tree, const uint8_t *b
 int rs_range_cfr_create_locked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
                                const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
                                const rs_node_locks *locks, const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
+
+/* ---- rake: raked pots in best response, node report and full-width CFR (an extension) -------------------
+ * A percentage of the pot with a cap, taken from the winner at the tree's TERMINAL nodes.  For a terminal n: pot = (double)(float)n.value, the number every leaf pays,
+ * and r = min(cap, rate * pot), one f64 multiply; cap = +inf means uncapped.  What traverser p is paid:
+ *   RS_TERM_UNCONTESTED   p is the folder (p == last_to_act): -pot;   p is the other player: pot - r
+ *   RS_TERM_SHOWDOWN, RS_TERM_ALLIN   win: vw = pot - r;   lose: vl = -pot;   tie: vt = -0.5 * r
+ * A leaf row stays v[b, hp] = pw[lane] * sum over the deals (b, hp, ho), ascending ho, of q[b, ho] * u, u one of the three numbers; by rank order (RS_BR_SORTED) win and
+ * lose are the sums they were, tie = (((LE - L) - (E0 - L0)) - (E1 - L1)) + q[the opponent's hand of the traverser's own two cards, if it holds it] (LE, L: the prefix sums
+ * up to the traverser's score inclusive / exclusive, E_t, L_t the same among the holders of its card t) and acc = ((vw * win) + (vt * tie)) + (vl * lose) -- the level
+ * plan and the depth-first walk give the same bits.  Only tree terminals are raked: the mass rows of a node report (an uncontested leaf of value 1.0) are not.
+ * UNITS: a leaf pays +-pot, the WHOLE number in n.value, not the opponent's half of it.  Where both players have put in equal amounts n.value is one player's stake and
+ * the chips on the table are 2 * n.value, so a room's "5 % of the pot, capped at C" is rate = 0.10, cap = 2 C here.  The library converts nothing.
+ * The game becomes GENERAL-SUM: under RS_BR_AVERAGE -(out[0] + out[1]) is the expected rake per deal; the exploitability of a profile is
+ * ((max[0] - avg[0]) + (max[1] - avg[1])) / 2 -- two calls.  RS_BR_REAL, RS_BR_CURRENT, weights and locks compose unchanged: a traverser's walk reads its own payoffs only.
+ * Checked before anything is allocated or the table is settled -- RS_ERR_INVALID, outputs and table left alone: rate not finite, < 0 or > 1; cap NaN or < 0; a non-zero
+ * reserved.  rake == NULL, rate == 0 and cap == 0 are the _locked call in every respect: the same bits, the same launches, the same rs_range_cfr_bytes.
+ * rs_range_cfr_set_gadget on an object created with rake returns RS_ERR_UNSUPPORTED (the TERMINATE branch pays the resolver minus the opponent's alternative: a zero-sum
+ * construction).  The rs_deal_trainer_* forms, the sampled trainer's leaves (rs_leaf_desc) and the single-round rs_best_response stay unraked.
+ * rs_rake_payoffs: host only; out = {win, tie, lose} of `player` at terminal `node` -- an uncontested terminal fills all three with the player's one payoff; rake == NULL
+ * gives {pot, 0, -pot} (uncontested: +-pot); a node that is no terminal, a bad player or a bad rake: RS_ERR_INVALID, out untouched. */
+typedef struct rs_rake { double rate; double cap; int32_t reserved[2]; } rs_rake;
+int rs_rake_payoffs(const rs_tree *tree, int node, const rs_rake *rake, int player, double out[3] /* win, tie, lose */);
+int rs_best_response_raked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                           const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
+                           const rs_node_locks *locks, const rs_rake *rake, int mode, double *out /*[2]*/);
+int rs_node_report_raked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                         size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, const rs_rake *rake,
+                         int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);
+int rs_range_cfr_create_raked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
+                              const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
+                              const rs_node_locks *locks, const rs_rake *rake, const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
 
 /* ---- iterate: MCCFRTrainer (cfr.rs) ------------------------------------------------------------
  * Lane model: lane (board b, cluster c) is one scalar cfr() traversal (cfr.rs:481-627)

@@ -26,6 +26,7 @@ from . import synth  # noqa: E402
 from . import abstraction  # noqa: E402
 from . import resolve  # noqa: E402
 from . import locks  # noqa: E402
+from . import rake  # noqa: E402
 
 __all__ = ["Options", "default_flop", "three_street_options", "build_game_tree", "tree_from_nodes", "create_infosets",
            "InfosetTable", "Infoset", "GameTree", "MCCFRTrainer", "DealTrainer", "RangeCFR", "DeviceBuffer", "device_count", "discount_factor",

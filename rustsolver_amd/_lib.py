@@ -100,6 +100,10 @@ class NodeLocks(C.Structure):   # rs_node_locks
     _fields_ = [("n", C.c_uint32), ("nodes", C.c_void_p), ("sigma", C.c_void_p)]
 
 
+class Rake(C.Structure):   # rs_rake
+    _fields_ = [("rate", C.c_double), ("cap", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint64 * K_COUNT), ("ms", C.c_double * K_COUNT), ("algo_bytes", C.c_double * K_COUNT)]
 
@@ -249,6 +253,8 @@ SYMBOLS = {
     "rs_range_cfr_create_weighted": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(RangeCfrParams), _PP]),
     "rs_range_cfr_create_locked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks),
                                              C.POINTER(RangeCfrParams), _PP]),
+    "rs_range_cfr_create_raked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.POINTER(Rake),
+                                            C.POINTER(RangeCfrParams), _PP]),
     "rs_range_cfr_destroy": (None, [_P]),
     "rs_range_cfr_iterate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "rs_range_cfr_train": (C.c_int, [_P, C.c_uint64, C.POINTER(DcfrParams), C.POINTER(C.c_double)]),
@@ -273,6 +279,9 @@ SYMBOLS = {
     "rs_best_response_locked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.c_int,
                                           C.POINTER(C.c_double)]),
     "rs_node_lock_size": (C.c_size_t, [_P, C.c_int, C.c_size_t, C.c_int]),
+    "rs_best_response_raked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.POINTER(Rake), C.c_int,
+                                         C.POINTER(C.c_double)]),
+    "rs_rake_payoffs": (C.c_int, [_P, C.c_int, C.POINTER(Rake), C.c_int, C.POINTER(C.c_double)]),
     "rs_br_runouts": (C.c_size_t, [_P, C.c_int, _P]),
     "rs_node_report_size": (C.c_size_t, [_P, C.c_int, C.c_size_t, _P, C.c_size_t, _P]),
     "rs_node_report": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
@@ -280,6 +289,8 @@ SYMBOLS = {
                                           C.c_size_t]),
     "rs_node_report_locked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.c_int, C.c_int, _P,
                                         C.c_size_t, _P, C.c_size_t]),
+    "rs_node_report_raked": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.POINTER(Rake), C.c_int,
+                                       C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
     "rs_deal_trainer_node_report": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t]),
     "rs_kmeans_init_s": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "rs_kmeans_pick_restart": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),

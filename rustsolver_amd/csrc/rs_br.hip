@@ -14,6 +14,8 @@
 //  * rs_range_cfr_set_gadget: the re-solving gadget above the root of a full-width solver's tree (safe subgame re-solving): two more job kinds.
 //  * rs_node_locks: a player's per-hand strategy fixed at chosen action nodes: the locks' rows live with the prepared game, a locked node takes two more
 //    job kinds in place of its reach and value jobs, in all three walks.
+//  * rs_rake: raked pots: the tree's terminals pay three numbers (win, tie, lose) instead of +-value and 0 -- no new job kind, the leaf kernels are
+//    templates on RAKED and a raked run's leaf jobs go to the raked instantiations, in all three walks.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -413,10 +415,13 @@ __global__ __launch_bounds__(kBrBlock) void k_br_tile_weights(const double *__re
 
 // terminal: v[b, hp] = pw[b, hp] * sum over the opponent's hands ho of the SAME run-out that share no card with hp or the run-out, ascending, of q[b, ho] * u;
 // u as the trainer's leaves (cfr.rs:314-348).  One workgroup = up to 256 hands of one run-out; the opponent's side of that run-out is staged in LDS.
+// RAKED (rs_rake): a showdown's u is one of three payoffs -- value when the traverser wins, vt on a tie, vl when it loses; uncontested leaves keep
+// their one scalar.  The unraked instantiations are the text they were.
+template <bool RAKED>
 __device__ __forceinline__ void br_terminal_boards_body(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
                                                                  uint32_t n_p, const uint64_t *__restrict__ mask_o, const uint32_t *__restrict__ score_o,
                                                                  const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, int uncontested,
-                                                                 double value, double *__restrict__ v) {
+                                                                 double value, double vt, double vl, double *__restrict__ v) {
     extern __shared__ unsigned char br_lds[];
     double *lq = (double *)br_lds;
     uint64_t *lm = (uint64_t *)(lq + n_o);
@@ -443,7 +448,7 @@ __device__ __forceinline__ void br_terminal_boards_body(const uint64_t *__restri
     for (uint32_t ho = 0; ho < n_o; ho++) {
         if (lm[ho] & avoid) continue;
         const uint32_t so = ls[ho];
-        const double u = uncontested ? value : (sp > so ? value : (sp < so ? -value : 0.0));
+        const double u = uncontested ? value : (sp > so ? value : (sp < so ? (RAKED ? vl : -value) : (RAKED ? vt : 0.0)));
         acc += lq[ho] * u;
     }
     v[lane] = pw[lane] * acc;
@@ -559,9 +564,12 @@ __global__ __launch_bounds__(kBrBlock) void k_br_index(const uint8_t *__restrict
     }
 }
 // one workgroup per run-out: wave 0 builds P (chunked, see above) and the per-card prefixes in LDS, then all threads evaluate the traverser's hands
+// RAKED: acc = ((value * win) + (vt * tie)) + (vl * lose), tie = (((LE - L) - (E0 - L0)) - (E1 - L1)) + q[same hand]: the opponent's hands of the traverser's score, less the
+// holders of either of its cards among them -- the hand of the same two cards stands in both card lists, is taken off twice and comes back once
+template <bool RAKED>
 __device__ __forceinline__ void br_terminal_sorted_body(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
                                                                  uint32_t n_p, const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
-                                                                 int uncontested, double value, double *__restrict__ v) {
+                                                                 int uncontested, double value, double vt, double vl, double *__restrict__ v) {
     extern __shared__ unsigned char br_lds[];
     double *P = (double *)br_lds;                                // [n_o]
     double *Pc = P + n_o;                                        // [52][51]
@@ -632,7 +640,11 @@ __device__ __forceinline__ void br_terminal_sorted_body(const uint8_t *__restric
             const double E0 = e0 ? Pc[c0 * kBrCardHolders + e0 - 1] : 0.0, E1 = e1 ? Pc[c1 * kBrCardHolders + e1 - 1] : 0.0;
             const double win = (L - L0) - L1;
             const double lose = ((T - LE) - (T0 - E0)) - (T1 - E1);
-            acc = value * (win - lose);
+            if (RAKED) {
+                const int sm = ix.same[h];
+                const double tie = (((LE - L) - (E0 - L0)) - (E1 - L1)) + (sm >= 0 ? qb[sm] : 0.0);
+                acc = ((value * win) + (vt * tie)) + (vl * lose);
+            } else acc = value * (win - lose);
         }
         v[lane] = pw[lane] * acc;
     }
@@ -654,6 +666,7 @@ struct BrJob {
     uint32_t sum_n[RS_MAX_ACTIONS];          // from sum_src[a]) -- added up while the rows are staged instead of written by k_br_sum_jobs and read again; 0: child a's row is vch + a * n_pad
     const uint32_t *tord, *perm;   // own node by columns (k_br_own_cols_jobs): [kmax][n_sets] the k-th lane of the i-th info set, and which cluster that info set is
     uint32_t n_sets, kmax;
+    double value_tie, value_lose;  // a showdown leaf of a raked run (rs_rake): what a tie and a loss pay the traverser; `value` is the win.  Read by the RAKED leaf kernels only
     // a report job (kBrReport) reads its node's vch and v, q = the traverser's own reach that came in, sum_src[0] = the node's mass row (written by the kBrMass job before it,
     // a leaf job: q = the opponent's reach at the node, uncontested, value 1.0), and writes q_out = the node's block of the call's output buffer
 };
@@ -666,7 +679,7 @@ constexpr int kBrChunkMax = 21;        // ... in 64 chunks of the rank order
 // (the kernel is compiled for four range sizes -- <HPT, CHUNK> = <1, 4> up to 256 combos, <2, 8> up to 512, <4, 16> up to 1 024, <6, 21> beyond: its scans are unrolled to those
 // bounds, and at <6, 21> a 200-combo range paid for 1 326 -- until then small ranges kept a workgroup per (run-out, leaf), 2.5 M workgroups per traverser)
 static_assert(kBrCardHolders == 3 * 17, "the card scans of k_br_terminal_sorted_loop run in three blocks of 17");
-template <int HPT, int CHUNK, bool REG_IDX>
+template <int HPT, int CHUNK, bool REG_IDX, bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted_loop(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
                                                                       uint32_t n_p, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
                                                                       const BrJob *__restrict__ jobs, uint32_t n_jobs) {
@@ -739,6 +752,7 @@ __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted_loop(const uint
         double *__restrict__ v = jobs[j].v;
         const int uncontested = jobs[j].uncontested;
         const double value = jobs[j].value;
+        const double vt = RAKED ? jobs[j].value_tie : 0.0, vl = RAKED ? jobs[j].value_lose : 0.0;
 #pragma unroll
         for (int k = 0; k < HPT; ++k) {
             const uint32_t i = threadIdx.x + (uint32_t)k * kBrBlock;
@@ -817,7 +831,10 @@ __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted_loop(const uint
                 const double E0 = e0 ? Pc[c0 * kBrCardHolders + e0 - 1] : 0.0, E1 = e1 ? Pc[c1 * kBrCardHolders + e1 - 1] : 0.0;
                 const double win = (L - L0) - L1;
                 const double lose = ((T - LE) - (T0 - E0)) - (T1 - E1);
-                acc = value * (win - lose);
+                if (RAKED) {
+                    const double tie = (((LE - L) - (E0 - L0)) - (E1 - L1)) + ((hc[k] >> 17) ? Q[(hc[k] >> 17) - 1u] : 0.0);
+                    acc = ((value * win) + (vt * tie)) + (vl * lose);
+                } else acc = value * (win - lose);
             }
             v[lane] = hp[k] * acc;
         }
@@ -1246,28 +1263,40 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_wave_jobs(const void *__res
     const BrJob j = jobs[blockIdx.y];
     br_own_wave_body<DT>(ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, mode, j.v);
 }
+// a one-node entry's payoffs as a kernel argument: one scalar without rake (the argument block the entry has always had), three with it
+template <bool RAKED> struct BrPay { double value; };
+template <> struct BrPay<true> { double value, vt, vl; };
+template <bool RAKED> __device__ __forceinline__ double br_pay_tie(const BrPay<RAKED> &) { return 0.0; }
+template <> __device__ __forceinline__ double br_pay_tie<true>(const BrPay<true> &p) { return p.vt; }
+template <bool RAKED> __device__ __forceinline__ double br_pay_lose(const BrPay<RAKED> &) { return 0.0; }
+template <> __device__ __forceinline__ double br_pay_lose<true>(const BrPay<true> &p) { return p.vl; }
+template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
                                                                  uint32_t n_p, const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
-                                                                 int uncontested, double value, double *__restrict__ v) {
-    br_terminal_sorted_body(hands_p, mask_p, pw, n_p, q, n_o, bmask, ix, uncontested, value, v);
+                                                                 int uncontested, BrPay<RAKED> pay, double *__restrict__ v) {
+    br_terminal_sorted_body<RAKED>(hands_p, mask_p, pw, n_p, q, n_o, bmask, ix, uncontested, pay.value, br_pay_tie(pay), br_pay_lose(pay), v);
 }
+template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted_jobs(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
                                                                       uint32_t n_p, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
                                                                       const BrJob *__restrict__ jobs) {
     const BrJob j = jobs[blockIdx.y];
-    br_terminal_sorted_body(hands_p, mask_p, pw, n_p, j.q, n_o, bmask, ix, j.uncontested, j.value, j.v);
+    br_terminal_sorted_body<RAKED>(hands_p, mask_p, pw, n_p, j.q, n_o, bmask, ix, j.uncontested, j.value, RAKED ? j.value_tie : 0.0, RAKED ? j.value_lose : 0.0, j.v);
 }
+template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
                                                                  uint32_t n_p, const uint64_t *__restrict__ mask_o, const uint32_t *__restrict__ score_o,
                                                                  const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, int uncontested,
-                                                                 double value, double *__restrict__ v) {
-    br_terminal_boards_body(mask_p, score_p, pw, n_p, mask_o, score_o, q, n_o, bmask, uncontested, value, v);
+                                                                 BrPay<RAKED> pay, double *__restrict__ v) {
+    br_terminal_boards_body<RAKED>(mask_p, score_p, pw, n_p, mask_o, score_o, q, n_o, bmask, uncontested, pay.value, br_pay_tie(pay), br_pay_lose(pay), v);
 }
+template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards_jobs(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
                                                                       uint32_t n_p, const uint64_t *__restrict__ mask_o, const uint32_t *__restrict__ score_o, uint32_t n_o,
                                                                       const uint64_t *__restrict__ bmask, const BrJob *__restrict__ jobs) {
     const BrJob j = jobs[blockIdx.z];
-    br_terminal_boards_body(mask_p, score_p, pw, n_p, mask_o, score_o, j.q, n_o, bmask, j.uncontested, j.value, j.v);
+    br_terminal_boards_body<RAKED>(mask_p, score_p, pw, n_p, mask_o, score_o, j.q, n_o, bmask, j.uncontested, j.value, RAKED ? j.value_tie : 0.0, RAKED ? j.value_lose : 0.0,
+                                   j.v);
 }
 
 // ---- the full-width sweep (rs_range_cfr_*): vector-form CFR over both ranges and every run-out on this walk, f32 tables ----------------------------------------------
@@ -1732,6 +1761,8 @@ struct BrRun {
     bool sorted = false;           // RS_BR_SORTED: showdowns by rank order
     bool real = false;             // RS_BR_REAL (this call): the traverser's info sets are (prefix, hand), its own nodes go to k_br_own_real_*
     bool current = false;          // RS_BR_CURRENT (this call): get_strategy of the regrets where the walk reads a strategy
+    bool raked = false;            // rs_rake with rate > 0 and cap > 0: the tree's terminals pay by rs_rake_payoffs and their leaf jobs go to the RAKED kernels
+    rs_rake rake{};                // ... the rake, as given
     bool cfr = false;              // the object is a full-width solver's (br_cfr_sweep): pi buffers in the workspace, own nodes go to k_br_cfr_own*
     int cfr_rmplus = 0;            // ... RS_UPD_RMPLUS of the sweep in flight
     double *d_pi0[2] = {nullptr, nullptr};    // ... the traverser's own reach at the root: 1.0 on every lane (the node report's as well)
@@ -1912,6 +1943,11 @@ struct BrRun {
                 j.v = v_out[id];
                 j.uncontested = n.ttype == RS_TERM_UNCONTESTED;
                 j.value = br_terminal_value(n, p);
+                if (raked) {   // the one place the formulas live: win, tie, lose (an uncontested leaf: its one payoff three times)
+                    double pay[3];
+                    if (int rc = rs_rake_payoffs(tree, int(id), &rake, p, pay)) return rc;
+                    j.value = pay[0], j.value_tie = pay[1], j.value_lose = pay[2];
+                }
                 add(kBrLeaf, 0, id, j);
                 continue;
             }
@@ -2089,6 +2125,8 @@ struct BrRun {
         case kBrLeaf: {
             // (small ranges keep a workgroup per (run-out, leaf): the loop's scans are unrolled for 1 326 hands whatever the range holds -- 200 combos: 0.047 against 0.059 s per call)
             const uint32_t most_hands = std::max(me.n_hands, op.n_hands);
+            const bool rk = raked && kind == kBrLeaf;   // a raked run's tree terminals go to the RAKED instantiations; mass rows are no terminals (uncontested, 1.0)
+            const BrPay<true> pay3{j.value, j.value_tie, j.value_lose};
             if (sorted && ws_levels && most_hands <= uint32_t(kBrHandsPerThread) * kBrBlock && op.n_hands <= uint32_t(kBrChunkMax) * 64u) {
                 // the level plan's leaf loop: a workgroup per run-out (and slice of the leaves, when run-outs alone do not fill the card)
                 const size_t lds = br_sorted_leaf_lds(op.n_hands) + (((size_t(op.n_hands) + 3) & ~size_t(3)) + 52 * kBrCardHolders) * sizeof(uint16_t) + 64;
@@ -2107,29 +2145,41 @@ struct BrRun {
                         if (eff >= 0.95) break;
                     }
                 }
-#define RS_LEAF_LOOP(HPT_, CHUNK_)                                                                                                                                     \
-    hipLaunchKernelGGL((k_br_terminal_sorted_loop<HPT_, CHUNK_, (HPT_ == kBrHandsPerThread)>), dim3(NB, slices), block, lds, s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, \
+#define RS_LEAF_LOOP_(HPT_, CHUNK_, RAKED_)                                                                                                                                    \
+    hipLaunchKernelGGL((k_br_terminal_sorted_loop<HPT_, CHUNK_, (HPT_ == kBrHandsPerThread), RAKED_>), dim3(NB, slices), block, lds, s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, \
                        op.n_hands, d_bmask, me.index, d_jobs, nj)
+#define RS_LEAF_LOOP(HPT_, CHUNK_)                                                                                                                                             \
+    do {                                                                                                                                                                       \
+        if (rk) RS_LEAF_LOOP_(HPT_, CHUNK_, true);                                                                                                                              \
+        else RS_LEAF_LOOP_(HPT_, CHUNK_, false);                                                                                                                                \
+    } while (0)
                 if (form == 0) RS_LEAF_LOOP(1, 4);
                 else if (form == 1) RS_LEAF_LOOP(2, 8);
                 else if (form == 2) RS_LEAF_LOOP(4, 16);
                 else RS_LEAF_LOOP(kBrHandsPerThread, kBrChunkMax);
 #undef RS_LEAF_LOOP
+#undef RS_LEAF_LOOP_
             } else if (sorted) {   // a workgroup per (run-out, leaf)
-                if (!d_jobs)
-                    hipLaunchKernelGGL(k_br_terminal_sorted, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands, d_bmask,
-                                       me.index, j.uncontested, j.value, j.v);
+                if (!d_jobs && rk)
+                    hipLaunchKernelGGL(k_br_terminal_sorted<true>, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands,
+                                       d_bmask, me.index, j.uncontested, pay3, j.v);
+                else if (!d_jobs)
+                    hipLaunchKernelGGL(k_br_terminal_sorted<false>, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands,
+                                       d_bmask, me.index, j.uncontested, BrPay<false>{j.value}, j.v);
                 else
-                    hipLaunchKernelGGL(k_br_terminal_sorted_jobs, dim3(NB, nj), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask,
-                                       me.index, d_jobs);
+                    hipLaunchKernelGGL(rk ? k_br_terminal_sorted_jobs<true> : k_br_terminal_sorted_jobs<false>, dim3(NB, nj), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands,
+                                       me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask, me.index, d_jobs);
             } else {
                 const size_t lds = size_t(op.n_hands) * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
-                if (!d_jobs)
-                    hipLaunchKernelGGL(k_br_terminal_boards, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
-                                       op.n_hands, d_bmask, j.uncontested, j.value, j.v);
+                if (!d_jobs && rk)
+                    hipLaunchKernelGGL(k_br_terminal_boards<true>, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
+                                       op.n_hands, d_bmask, j.uncontested, pay3, j.v);
+                else if (!d_jobs)
+                    hipLaunchKernelGGL(k_br_terminal_boards<false>, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
+                                       op.n_hands, d_bmask, j.uncontested, BrPay<false>{j.value}, j.v);
                 else
-                    hipLaunchKernelGGL(k_br_terminal_boards_jobs, dim3(grid1(me.n_hands), NB, nj), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score,
-                                       op.n_hands, d_bmask, d_jobs);
+                    hipLaunchKernelGGL(rk ? k_br_terminal_boards_jobs<true> : k_br_terminal_boards_jobs<false>, dim3(grid1(me.n_hands), NB, nj), block, lds, s, me.d_mask, me.d_score,
+                                       me.d_pw, me.n_hands, op.d_mask, op.d_score, op.n_hands, d_bmask, d_jobs);
             }
             break;
         }
@@ -2316,6 +2366,21 @@ size_t rs_br_runouts(const uint8_t *board0, int n_board0, uint8_t *out_cards) {
     const size_t nb = enumerate_runouts(board0, n_board0, out_cards ? &cards : nullptr);
     if (out_cards) std::memcpy(out_cards, cards.data(), cards.size());
     return nb;
+}
+
+// host only; the one place the raked payoffs are worked out (build_plan calls it for every terminal of a raked run)
+int rs_rake_payoffs(const rs_tree *tree, int node, const rs_rake *rake, int player, double out[3]) {
+    if (!tree || !out) return rs::fail(RS_ERR_INVALID, "rs_rake_payoffs: NULL argument");
+    if (player != 0 && player != 1) return rs::fail(RS_ERR_INVALID, "rs_rake_payoffs: player is 0 or 1");
+    if (node < 0 || size_t(node) >= tree->nodes.size()) return rs::fail(RS_ERR_INVALID, "rs_rake_payoffs: node id " + std::to_string(node) + " is out of range");
+    const rs_tree_node &n = tree->nodes[size_t(node)];
+    if (n.kind != RS_NODE_TERMINAL) return rs::fail(RS_ERR_INVALID, "rs_rake_payoffs: node " + std::to_string(node) + " is not a terminal");
+    if (int rc = rs::br_check_rake(rake)) return rc;
+    const double pot = double(float(n.value));
+    const double r = rake ? std::min(rake->cap, rake->rate * pot) : 0.0;
+    if (n.ttype == RS_TERM_UNCONTESTED) out[0] = out[1] = out[2] = player == int(n.last_to_act) ? -pot : pot - r;
+    else out[0] = pot - r, out[1] = r > 0.0 ? -0.5 * r : 0.0, out[2] = -pot;
+    return RS_OK;
 }
 
 }  // extern "C"
@@ -2592,6 +2657,15 @@ int br_check_locks(const rs_node_locks *locks, const rs_tree *tree, const uint8_
     return RS_OK;
 }
 
+// rs_rake as the header states it; NULL = no rake.  Touches nothing: the raked entry points call it before anything is allocated or the table is settled
+int br_check_rake(const rs_rake *rake) {
+    if (!rake) return RS_OK;
+    if (!std::isfinite(rake->rate) || rake->rate < 0.0 || rake->rate > 1.0) return fail(RS_ERR_INVALID, "rs_rake: rate is finite and in [0, 1]");
+    if (std::isnan(rake->cap) || rake->cap < 0.0) return fail(RS_ERR_INVALID, "rs_rake: cap is >= 0 (+inf = uncapped)");
+    if (rake->reserved[0] != 0 || rake->reserved[1] != 0) return fail(RS_ERR_INVALID, "rs_rake: reserved must be 0");
+    return RS_OK;
+}
+
 int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights, BrRun **prepared,
                const rs_node_locks *locks /* checked by the caller: br_check_locks */) {
@@ -2841,6 +2915,11 @@ int BrRun::traverse(int traverser, std::vector<double> &root, double *total) {
     return RS_OK;
 }
 
+void br_set_rake(BrRun *prepared, const rs_rake *rake) {
+    prepared->raked = rake && rake->rate > 0.0 && rake->cap > 0.0;
+    if (prepared->raked) prepared->rake = *rake;
+}
+
 // the walk: both traversers against the table as it stands
 int br_execute(BrRun *prepared, int mode, double *out) {
     if (!prepared || !out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
@@ -2989,6 +3068,7 @@ int br_cfr_set_gadget(BrRun *prepared, int resolver, const double *alt) {
     if (resolver != 0 && resolver != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: resolver is 0 or 1");
     BrRun &run = *prepared;
     if (!run.lock_of.empty()) return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_set_gadget: the object was created with node locks (a gadget and locks on one object are out of scope)");
+    if (run.raked) return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_set_gadget: the object was created with rake (the gadget's TERMINATE branch is a zero-sum construction)");
     const uint32_t n = run.side[1 - resolver].n_hands;
     for (uint32_t h = 0; h < n; ++h)
         if (!std::isfinite(alt[h])) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: alt[" + std::to_string(h) + "] is not finite");
@@ -3056,10 +3136,16 @@ int rs_range_cfr_create_weighted(rs_table *t, const rs_tree *tree, const uint8_t
 int rs_range_cfr_create_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                                size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks,
                                const rs_range_cfr_params *params, rs_range_cfr **out) {
+    return rs_range_cfr_create_raked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, locks, nullptr, params, out);
+}
+int rs_range_cfr_create_raked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                              size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks,
+                              const rs_rake *rake, const rs_range_cfr_params *params, rs_range_cfr **out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
     *out = nullptr;
     if (!t) return fail(RS_ERR_INVALID, "rs_range_cfr_create: NULL argument");
-    if (int rc_ = rs::br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc_;   // before the table is settled: a refused call writes nothing
+    if (int rc_ = rs::br_check_rake(rake)) return rc_;   // before the table is settled: a refused call writes nothing
+    if (int rc_ = rs::br_check_weights(weights, n_hands_p0, n_hands_p1)) return rc_;
     if (int rc_ = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc_;
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate): the index kernels go to the table's stream
     const int mode = params ? params->mode : 0;
@@ -3075,6 +3161,7 @@ int rs_range_cfr_create_locked(rs_table *t, const rs_tree *tree, const uint8_t *
         rs::br_free(run);
         return rc;
     }
+    rs::br_set_rake(run, rake);
     rs_range_cfr *s = new (std::nothrow) rs_range_cfr;
     if (!s) {
         rs::br_free(run);
@@ -3159,13 +3246,21 @@ size_t rs_node_lock_size(const rs_tree *tree, int n_board0, size_t n_hands_actor
 int rs_best_response_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                             size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, int mode,
                             double *out) {
+    return rs_best_response_raked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, locks, nullptr, mode, out);
+}
+
+int rs_best_response_raked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                           size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, const rs_rake *rake,
+                           int mode, double *out) {
     if (!out) return fail(RS_ERR_INVALID, "rs_best_response: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
     if (int rc = rs::br_check_mode(mode & ~(RS_BR_REAL | RS_BR_CURRENT), (mode & RS_BR_REAL) != 0)) return rc;
+    if (int rc = rs::br_check_rake(rake)) return rc;
     if (int rc = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc;   // before anything is allocated
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
+    rs::br_set_rake(run, rake);
     const int rc = rs::br_execute(run, mode, out);
     rs::br_free(run);
     return rc;
@@ -3192,16 +3287,25 @@ int rs_node_report_weighted(rs_table *t, const rs_tree *tree, const uint8_t *boa
 int rs_node_report_locked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                           size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, int mode, int traverser,
                           const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
+    return rs_node_report_raked(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, weights, locks, nullptr, mode, traverser, nodes, n_nodes,
+                                out, out_doubles);
+}
+
+int rs_node_report_raked(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                         size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, const rs_rake *rake,
+                         int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
     if (!out) return fail(RS_ERR_INVALID, "rs_node_report: NULL argument");
     const bool sorted = (mode & RS_BR_SORTED) != 0;
     mode &= ~RS_BR_SORTED;
     if (int rc = rs::br_report_check_mode(mode, traverser)) return rc;
+    if (int rc = rs::br_check_rake(rake)) return rc;
     if (int rc = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc;   // before anything is allocated
     const size_t total = rs::br_report_layout(tree, n_board0, traverser == 0 ? n_hands_p0 : n_hands_p1, nodes, n_nodes, nullptr);   // before the game is prepared: a bad request costs nothing
     if (!total) return RS_ERR_INVALID;
     if (out_doubles < total) return fail(RS_ERR_INVALID, "rs_node_report: the output buffer is too small (rs_node_report_size doubles)");
     rs::BrRun *run = nullptr;
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
+    rs::br_set_rake(run, rake);
     const int rc = rs::br_report(run, mode, traverser, nodes, n_nodes, out, out_doubles);
     rs::br_free(run);
     return rc;

@@ -137,6 +137,10 @@ int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t 
 // rs_node_locks as the header states them (NULL or n == 0: nothing to check, whatever the other arguments are); RS_ERR_INVALID; touches nothing
 int br_check_locks(const rs_node_locks *locks, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
                    size_t n_hands_p1);
+// rs_rake as the header states it (NULL: nothing to check); RS_ERR_INVALID; touches nothing
+int br_check_rake(const rs_rake *rake);
+// the rake of a prepared game that has not walked yet (checked by the caller: br_check_rake); NULL, rate == 0 or cap == 0 = none
+void br_set_rake(BrRun *prepared, const rs_rake *rake);
 int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVERAGE */, double *out /* [2] */);
 // one traverser's node report (rs_node_report) on the prepared game; mode without RS_BR_SORTED.  A workspace that lacks the report's rows is traded for a larger one
 int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);

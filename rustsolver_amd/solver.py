@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _lib as L
 from . import locks as node_locks
+from . import rake as raked
 
 
 def _vp(a):
@@ -474,12 +475,15 @@ class InfosetTable:
         L.check(L.load().rs_best_response(self._h, tree._h, _vp(b), _vp(h0), len(h0), _vp(c0), _vp(h1), len(h1), _vp(c1), mode, _vp(out)))
         return out
 
-    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX, current=False, weights=None, deal="sequential", locks=None):
+    def best_response_rounds(self, tree, board0, hands0, hands1, clusters, mode=L.BR_MAX, current=False, weights=None, deal="sequential", locks=None,
+                             rake=None):
         """multi-round best response (rs_best_response_rounds): clusters[r][p] = uint32 [prefixes of round r][n_hands_p] dense ids; current: BR_CURRENT.
         weights = (w0, w1), either None: per-hand range weights (rs_best_response_weighted), a weight of 0.0 takes the hand out of the range; deal: "sequential"
         (generate_hand with weighted draws) or "joint" (the product of the two ranges with card removal).
         locks = {tree node id: float64 [A][prefixes of the node's round][hands of the acting player]}: node locks (rs_best_response_locked, rustsolver_amd.locks); the
-        columns of hands of weight 0.0 are dropped with the hands"""
+        columns of hands of weight 0.0 are dropped with the hands.
+        rake = (rate, cap): raked pots (rs_best_response_raked, rustsolver_amd.rake, which states the units); the game is then general-sum -- under BR_AVERAGE
+        -(out[0] + out[1]) is the rake paid per deal, and a profile's exploitability is rake.exploitability(max_values, avg_values)"""
         mode |= L.BR_CURRENT if current else 0
         b = np.ascontiguousarray(board0, dtype=np.uint8)
         (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
@@ -487,16 +491,19 @@ class InfosetTable:
         arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
         out = np.zeros(2, dtype=np.float64)
         lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
-        L.check(L.load().rs_best_response_locked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, mode,
-                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        rk, rk_alive = raked.arg(rake)
+        L.check(L.load().rs_best_response_raked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk, mode,
+                                                out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None):
+    def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None,
+                    rake=None):
         """per-hand values, reach and mass at the action nodes `nodes` (tree node ids) for one traverser, both players playing the average strategy (current: the current
         one) in the game best_response_rounds measures (rs_node_report).  -> {node: dict(cfv=[A][F][H], value=[F][H], mass=[F][H], own=[F][H])}, float64, F the prefixes of
         the node's round, H the traverser's hands: cfv[a] the action's counterfactual value, value the node's, mass the opponent range the hand faces (cfv / mass = chips
         given that the hand is there), own the traverser's own probability of getting there.  weights, deal: as best_response_rounds (rs_node_report_weighted); a hand of
-        weight 0.0 has 0.0 in every row.  locks: as best_response_rounds (rs_node_report_locked); a locked node reports its value by the lock"""
+        weight 0.0 has 0.0 in every row.  locks: as best_response_rounds (rs_node_report_locked); a locked node reports its value by the lock.
+        rake: as best_response_rounds (rs_node_report_raked); the tree's terminals are raked, the mass rows are not"""
         b = np.ascontiguousarray(board0, dtype=np.uint8)
         (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
         keep = [c for row in cl for c in row]
@@ -506,8 +513,9 @@ class InfosetTable:
         n_hands = len(h1) if traverser else len(h0)
         ids, offsets, out = _report_request(tree, len(b), n_hands, nodes)
         lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
-        L.check(L.load().rs_node_report_locked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk,
-                                               _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
+        rk, rk_alive = raked.arg(rake)
+        L.check(L.load().rs_node_report_raked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk,
+                                              _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
         return _restore_columns(_report_blocks(tree, n_hands, ids, offsets, out), kept[traverser])
 
     def update_node(self, node, action_utils, reach=None, scale=100.0, mode=L.UPD_CLAMP_I64):
@@ -995,10 +1003,12 @@ class RangeCFR:
     arguments: board0 (3, 4 or 5 cards), the two ranges, clusters[r][p] = uint32 [prefixes of round r][n_hands_p].  The table and the tree must outlive the object.
     The update rule (plain or regret matching+) is a property of the C object: one is created at construction (`rmplus`), the other on the first call that asks for it.
     locks = {tree node id: float64 [A][prefixes of the node's round][hands of the acting player]}: node locks (rs_range_cfr_create_locked, rustsolver_amd.locks) -- the
-    sweeps solve everything around them and leave the locked nodes' table rows alone; set_gadget is refused on such an object."""
+    sweeps solve everything around them and leave the locked nodes' table rows alone; set_gadget is refused on such an object.
+    rake = (rate, cap): raked pots (rs_range_cfr_create_raked, rustsolver_amd.rake): the sweeps solve the raked, general-sum game; set_gadget is refused on such an object."""
 
-    def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None):
+    def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None, rake=None):
         self.table, self.tree = table, tree
+        self._rake = rake
         self._b = np.ascontiguousarray(board0, dtype=np.uint8)
         (self._h0, self._h1), cl, self._w, self._keep = drop_zero_weights((hands0, hands1), clusters, weights)   # weights, deal: as InfosetTable.best_response_rounds
         self._locks = node_locks.drop_columns(tree, locks, self._keep)
@@ -1013,9 +1023,10 @@ class RangeCFR:
             arr = (C.c_void_p * len(self._cl))(*[k.ctypes.data for k in self._cl])
             h = C.c_void_p()
             lk, lk_alive = node_locks.arg(self.tree, len(self._b), (len(self._h0), len(self._h1)), self._locks)   # (the library copies the rows)
-            L.check(L.load().rs_range_cfr_create_locked(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1),
-                                                        arr, len(self._cl) // 2, _range_weights(self._w, self._deal), lk,
-                                                        C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
+            rk, rk_alive = raked.arg(self._rake)
+            L.check(L.load().rs_range_cfr_create_raked(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1),
+                                                       arr, len(self._cl) // 2, _range_weights(self._w, self._deal), lk, rk,
+                                                       C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
             self._hs[rmplus] = h
             if getattr(self, "_gadget", None) is not None:      # a handle created after set_gadget starts armed, from zero rows
                 L.check(L.load().rs_range_cfr_set_gadget(h, self._gadget[0], _vp(self._gadget[1])))
