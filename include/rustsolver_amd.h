@@ -845,6 +845,38 @@ int rs_kmeans_fit_regular(rs_table *table, int dist, const float *d_dataset, siz
 int rs_kmeans_fit_growbatch(rs_table *table, int dist, const float *d_dataset, size_t n, const uint32_t *d_order, size_t batch, float *centers, int n_centers,
                             int n_bins, uint32_t *d_clusters, float *d_bounds, float *stats);
 
+/* ---- exact expected hand strength and the EHS histograms the k-means above clusters (gen_abstraction/ehs.rs, bin/gen_ehs.rs, main.rs generate_histograms) -------------
+ * The reference samples (`calc_equity`, an unseeded SmallRng); here every run-out and every opponent hand is enumerated, so a result depends on the cards alone.
+ * Cards are 4 * rank + suit.  A hand is two hole cards followed by 3, 4 or 5 board cards.  An opponent hand is any two of the remaining cards, each counted once.  A
+ * completion is any SET of further board cards, drawn from what is left, that brings the board to 5 (unordered sets give the distribution of the reference's ordered draws).
+ *   river, 7 cards   over the N = 990 opponent hands, W have a lower `evaluate` score and T an equal one: ehs = (float)((double)(2 W + T) / (double)(2 N)).
+ *   flop / turn      the same formula with W, T and N summed over the completions: 1081 of a flop hand (N = 1081 * 990), 46 of a turn hand (N = 46 * 990) -- what
+ *                    calc_equity(hand vs random, board) estimates.
+ *   bin              rs_ehs_bin(value, n_bins) is get_bin (main.rs:58-70) literally: f32 interval = 1 / bins, threshold = 1 - interval, `threshold -= interval` in f32 going
+ *                    down, a strict `>`.  The accumulated thresholds are NOT j / bins (at 20 bins the tenth is 0.49999988, so an exact 0.5 lands in bin 10; 0.95f in bin
+ *                    18).  The thresholds are computed once on the host by that loop; the kernels take the same array.
+ *   histogram        of a flop or turn hand: for each completion the river ehs of the 7 cards, count[rs_ehs_bin(ehs, n_bins)] += 1; out[k] = (float)count[k] /
+ *                    (float)n_completions.
+ * Everything before the last division is an integer: the results do not depend on the order of summation, the kernel form or the grouping. */
+#define RS_EHS_MAX_BINS 64   /* the k-means' limit; the reference uses 20, 30 and 35 */
+/* host only; RS_ERR_INVALID (negative) unless 1 <= n_bins <= RS_EHS_MAX_BINS */
+int rs_ehs_bin(float value, int n_bins);
+/* EHS::get_ehs for a list of hands, by enumeration: d_cards[n_cards][pitch] (u8, row i = card i of the hand, pitch = round_up(n, 64): the layout of
+ * rs_hand_index_device), n_cards = 5, 6 or 7, d_out[n].  A plain per-hand kernel (a wave per 7-card hand, a workgroup per 5- or 6-card hand); it is the device-side
+ * definition the sweep below is tested against.  RS_ERR_INVALID before anything is launched or allocated: n_cards not 5, 6 or 7, NULL d_cards or d_out with n > 0.
+ * A hand with a repeated card or a byte >= 52 raises an error word that THIS call reads back: it synchronises and returns RS_ERR_INVALID; the outputs of such hands
+ * are left as they were, every other hand's is written. */
+int rs_ehs(rs_table *table, const uint8_t *d_cards, int n_cards, uint32_t n, float *d_out);
+/* The histograms of a whole round.  `indexer` = hand_indexer_s::init(2, [2, 3]) (flop) or (2, [2, 4]) (turn); d_out[rs_hand_indexer_size(indexer, 1)][n_bins].
+ * d_boards[3 or 4][pitch] (pitch = round_up(n_boards, 64)) lists boards; NULL = every board of the round (22 100 flops / 270 725 turn boards, enumerated on the device;
+ * n_boards is ignored).  For each board the histogram of every hole pair that fits it (1176 on a flop, 1128 on a turn board) is written to the row of the hand's canonical
+ * index; rows whose hands lie on no listed board are left as they were.  Suit-isomorphic copies of a hand (on one board or on several) write IDENTICAL BITS to the same
+ * row -- the integer counts are equal and the one division is the same -- and this is relied on: the writes are plain stores, unordered.
+ * RS_ERR_INVALID before anything is launched or allocated: an indexer of another shape, n_bins outside 1..RS_EHS_MAX_BINS, NULL d_out with boards to do.  A listed board
+ * with a repeated card or a byte >= 52 is skipped and reported as for rs_ehs (error word read back by this call, RS_ERR_INVALID; the other boards' rows are written).
+ * Synchronises. */
+int rs_ehs_round_histograms(rs_table *table, rs_hand_indexer *indexer, int n_bins, const uint8_t *d_boards, uint32_t n_boards, float *d_out);
+
 /* ---- showdown evaluation on the device ---------------------------------------------------------------
  * d_cards[9][pitch] (u8, pitch = round_up(n_deals, 64)): rows 0-4 the board, 5-6 player 0's hole cards, 7-8 player 1's;
  * card = 4*rank + suit, rank 0..12 = 2..A (cfr.rs:592).  d_sign[lane] = sign(evaluate(hand0) - evaluate(hand1)) exactly as

@@ -26,6 +26,7 @@ BR_REAL = 0x200             # | into BR_MAX: the best response in the real game 
 BR_CURRENT = 0x400          # | into any mode: the strategies read are the CURRENT ones (get_strategy of the regrets) instead of the average ones
 DEAL_SEQUENTIAL, DEAL_JOINT = 0, 1   # rs_range_weights.deal (RS_DEAL_*)
 DIST_EMD, DIST_L2 = 0, 1
+EHS_MAX_BINS = 64           # RS_EHS_MAX_BINS
 K_UPDATE, K_NODE_UTIL, K_REACH, K_CHANCE, K_DISCOUNT, K_STRATEGY, K_TREE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -297,6 +298,9 @@ SYMBOLS = {
     "rs_kmeans_reassign": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rs_kmeans_fit_regular": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_float)]),
     "rs_kmeans_fit_growbatch": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rs_ehs_bin": (C.c_int, [C.c_float, C.c_int]),
+    "rs_ehs": (C.c_int, [_P, _P, C.c_int, C.c_uint32, _P]),
+    "rs_ehs_round_histograms": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint32, _P]),
     "rs_table_save": (C.c_int, [_P, C.c_char_p]),
     "rs_table_load": (C.c_int, [C.c_char_p, C.c_int, _PP]),
     "rs_profile_enable": (C.c_int, [_P, C.c_int]),
@@ -339,5 +343,12 @@ def load():
 
 def check(rc):
     if rc != OK:
+        raise RsError(rc, load().rs_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+def check_nonneg(rc):
+    """for calls that return a count or an index, or a negative error code"""
+    if rc < 0:
         raise RsError(rc, load().rs_last_error().decode("utf-8", "replace"))
     return rc

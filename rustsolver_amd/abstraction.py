@@ -278,6 +278,90 @@ def histogram_distance(p, q, dist=DIST_EMD):
     return np.float32(out.value)
 
 
+# ---- exact EHS and the round histograms the k-means clusters (rs_ehs.hip; semantics in include/rustsolver_amd.h) -----------------------------------
+EHS_MAX_BINS = L.EHS_MAX_BINS
+
+
+def ehs_bin(value, n_bins):
+    """get_bin (gen_abstraction/main.rs:58-70) literally, on the host"""
+    return L.check_nonneg(L.load().rs_ehs_bin(float(np.float32(value)), n_bins))
+
+
+def _card_rows(table, cards, n_cards):
+    """uint8 [n][n_cards] -> the SoA rows [n_cards][pitch] on the device"""
+    from .solver import DeviceBuffer, deal_pitch
+    c = np.ascontiguousarray(cards, dtype=np.uint8).reshape(-1, n_cards)
+    pitch = deal_pitch(len(c))
+    host = np.zeros((n_cards, max(pitch, 1)), dtype=np.uint8)
+    host[:, :len(c)] = c.T
+    return DeviceBuffer.from_numpy(table, host), len(c)
+
+
+def ehs(table, cards):
+    """Exact expected hand strength against a random hand (EHS::get_ehs by enumeration): cards uint8 [n][5, 6 or 7] = two hole cards then the
+    board (or one hand) -> float32 [n].  A hand with a repeated card or a byte that is no card raises RsError (ERR_INVALID)."""
+    from .solver import DeviceBuffer
+    c = np.ascontiguousarray(cards, dtype=np.uint8)
+    one = c.ndim == 1
+    c = c.reshape(-1, c.shape[-1])
+    dc, n = _card_rows(table, c, c.shape[1])
+    do = DeviceBuffer(table, max(n, 1) * 4)
+    L.check(L.load().rs_ehs(table._h, dc.ptr, c.shape[1], n, do.ptr))
+    out = do.download(np.float32, n)
+    return out[0] if one else out
+
+
+class RoundHistograms:
+    """The device buffer `round_histograms` fills: float32 [rows][n_bins], one row per canonical hand index of the round"""
+
+    def __init__(self, table, rows, n_bins, buffer):
+        self.table, self.rows, self.n_bins, self.buffer = table, rows, n_bins, buffer
+
+    @property
+    def ptr(self):
+        return self.buffer.ptr
+
+    @property
+    def nbytes(self):
+        return self.buffer.nbytes
+
+    def download(self, first=0, count=None):
+        """rows first .. first + count (default: all) as float32 [count][n_bins] on the host -- small cases, or in slices: the turn round at 30 bins is 1.7 GB"""
+        count = self.rows - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.rows:
+            raise IndexError("rows %d .. %d of %d" % (first, first + count, self.rows))
+        out = np.empty((count, self.n_bins), dtype=np.float32)
+        if out.size:
+            L.check(L.load().rs_d2h(self.table._h, out.ctypes.data, self.ptr + first * self.n_bins * 4, out.nbytes))
+        return out
+
+    def gather(self, indices):
+        """the rows `indices` (a few: candidate centers), one copy each"""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        return np.concatenate([self.download(int(i), 1) for i in idx]) if len(idx) else np.zeros((0, self.n_bins), dtype=np.float32)
+
+
+def round_histograms(table, indexer, n_bins, boards=None, out=None):
+    """The EHS histograms of a flop (indexer [2, 3]) or turn (indexer [2, 4]) round on the device.  boards: uint8 [n][3 or 4], or None = every board of the
+    round.  Rows whose hands lie on no listed board are left as they were (a buffer made here starts at zero).  -> RoundHistograms"""
+    from .solver import DeviceBuffer
+    if out is None:
+        rows = indexer.size(indexer.rounds - 1)
+        out = RoundHistograms(table, rows, n_bins, DeviceBuffer(table, max(rows * max(n_bins, 0), 1) * 4))
+        out.buffer.zero()
+    db, n = None, 0
+    if boards is not None:
+        b = np.ascontiguousarray(boards, dtype=np.uint8)
+        if b.size == 0:
+            return out
+        b = b.reshape(-1, b.shape[-1])
+        if b.shape[1] != indexer.n_cards(indexer.rounds - 1) - 2:
+            raise ValueError("a board of this round has %d cards" % (indexer.n_cards(indexer.rounds - 1) - 2))
+        db, n = _card_rows(table, b, b.shape[1])
+    L.check(L.load().rs_ehs_round_histograms(table._h, indexer._h, n_bins, db.ptr if db else None, n, out.ptr))
+    return out
+
+
 class Kmeans:
     """The distance sweeps of gen_abstraction/kmeans.rs on the GPU: `predict` (kmeans.rs:173-211) and the kmeans++ `update_min_dists`
     (kmeans.rs:603-619).  The dataset stays resident on the device between calls."""
@@ -290,6 +374,18 @@ class Kmeans:
         self.table, self.n, self.n_bins = table, d.shape[0], d.shape[1]
         self._data = DeviceBuffer.from_numpy(table, d) if d.size else None
         self._DeviceBuffer = DeviceBuffer
+
+    @classmethod
+    def from_device(cls, table, buffer, n, n_bins):
+        """the same over a dataset that is on the device already: `buffer` (a DeviceBuffer or RoundHistograms, kept alive by this object) holds float32 [n][n_bins]"""
+        from .solver import DeviceBuffer
+        if n < 0 or n_bins < 1 or n * n_bins * 4 > buffer.nbytes:
+            raise ValueError("the buffer holds fewer than n x n_bins floats")
+        self = cls.__new__(cls)
+        self.table, self.n, self.n_bins = table, n, n_bins
+        self._data = buffer if n else None
+        self._DeviceBuffer = DeviceBuffer
+        return self
 
     def predict(self, centers, dist=DIST_EMD):
         """-> (clusters uint32 [n], distance to the chosen center float32 [n])"""

@@ -498,6 +498,7 @@ struct rs_card_abs {
 
 namespace rs {
 hipError_t build_xlut(rs_card_abs *a, rs_table *t, rs_card_abs::Mirror *m);   // below the kernels
+int hand_indexer_view_on(rs_hand_indexer *indexer, int device, hipStream_t stream, HandIndexView *out) { return device_view(indexer, device, stream, out); }
 }
 namespace {
 int abs_device(rs_card_abs *a, rs_table *t, rs_card_abs::Dev *out) {

@@ -1,0 +1,415 @@
+// rs_ehs.hip -- exact expected hand strength against a random hand, and the EHS histograms of a whole flop or turn round: the front end of the abstraction
+// generator (gen_abstraction/ehs.rs EHS::get_ehs, main.rs:58-70 get_bin, main.rs generate_histograms), with enumeration in place of the reference's Monte-Carlo
+// calc_equity.  Semantics: include/rustsolver_amd.h.  Everything before the last division is an integer, so results depend on the cards alone.
+//   * k_ehs: the lookup form, one hand per wave (7 cards) or per workgroup (5 / 6 cards), every opponent hand of every completion evaluated;
+//   * k_ehs_round_hist: the sweep, one workgroup per board of the round.  Per run-out (the cards that bring the board to 5) the 1081 hole pairs are evaluated once,
+//     ordered by score in LDS, and each pair's counts come from the rank order with card removal, the way the best-response leaves count (rs_br.hip);
+//     the (hole pair, bin) counters of the board are a uint16 histogram in LDS (profiles/ehs.md).
+// Cards and suits only ever select under predicates (no array indexed by a card): the kernels carry no scratch.  A byte that is no card never indexes LDS: lists are
+// validated before use, and every card the kernels enumerate themselves comes out of a bit mask.
+#include <cstring>
+#include <string>
+
+#include "rs_hand_index.hpp"
+#include "rs_internal.hpp"
+#include "rs_eval.hpp"
+
+using namespace rs;
+
+#define RS_HIP(call, what)                                   \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return rs::hip_fail(e_, what); \
+    } while (0)
+
+namespace rs {
+
+constexpr int kEhsThreads = 256;         // the lookup form
+constexpr int kEhsWaves = kEhsThreads / 64;
+constexpr int kEhsSweepThreads = 1024;   // the sweep: LDS allows two workgroups per CU at 20-30 bins, so a workgroup brings 16 waves and is held to 8 per SIMD (profiles/ehs.md)
+constexpr uint32_t kEhsOpp = 990;      // C(45, 2) opponent hands of a 7-card hand
+constexpr uint32_t kEhsPairs = 1081;   // C(47, 2) hole pairs of a 5-card board
+constexpr uint32_t kEhsSortN = 2048;   // the bitonic network's width
+constexpr uint64_t kDeck = (1ull << 52) - 1;
+
+// thr[b], b = 1 .. n_bins - 1: get_bin's thresholds as its loop accumulates them (thr[0] is never read).  Non-decreasing in b.
+struct EhsBins {
+    float thr[RS_EHS_MAX_BINS];
+    int32_t n_bins;
+};
+
+// position of the n-th (from 0) set bit of m; n < popcount(m)
+__device__ __forceinline__ uint32_t nth_bit(uint64_t m, uint32_t n) {
+    uint32_t w = (uint32_t)m, pos = 0, c = (uint32_t)__popc(w);
+    if (n >= c) {
+        n -= c;
+        w = (uint32_t)(m >> 32);
+        pos = 32;
+    }
+#pragma unroll
+    for (int sh = 16; sh >= 1; sh >>= 1) {
+        const uint32_t lo = w & ((1u << sh) - 1u);
+        c = (uint32_t)__popc(lo);
+        if (n >= c) {
+            n -= c;
+            w >>= sh;
+            pos += (uint32_t)sh;
+        } else w = lo;
+    }
+    return pos;
+}
+
+// Unordered pairs of M elements, M odd, numbered 0 .. M (M - 1) / 2 - 1: pair p = (a, (a + d) mod M) with a = p / H, d = p % H + 1, H = (M - 1) / 2 -- every
+// pair has exactly one circular distance in 1 .. H.  The pairs that hold element i are i * H + d - 1 and ((i - d) mod M) * H + d - 1, d = 1 .. H.
+template <uint32_t M>
+__device__ __forceinline__ void pair_of(uint32_t p, uint32_t &i, uint32_t &j) {
+    constexpr uint32_t H = (M - 1) / 2;
+    i = p / H;
+    j = (i + p % H + 1) % M;
+}
+
+// get_bin over the staged thresholds: the largest b with v > thr[b], else 0 (thr is non-decreasing, so the predicate is monotone in b)
+__device__ __forceinline__ uint32_t ehs_bin_of(const float *thr, int n_bins, float v) {
+    int b = 0;
+#pragma unroll
+    for (int step = RS_EHS_MAX_BINS / 2; step; step >>= 1) {
+        const int c = b + step;
+        if (c < n_bins && v > thr[c]) b = c;
+    }
+    return (uint32_t)b;
+}
+
+// ---- the lookup form ------------------------------------------------------------------------------------------------------------------------------------
+// NC = 7: a wave per hand, the lanes share its 990 opponents.  NC = 5 / 6: a workgroup per hand, its waves share the 1081 / 46 completions.
+template <int NC>
+__global__ __launch_bounds__(kEhsThreads) void k_ehs(const uint8_t *__restrict__ cards, uint32_t n, uint32_t pitch, float *__restrict__ out, uint32_t *__restrict__ err) {
+    constexpr uint32_t kPer = NC == 7 ? kEhsWaves : 1;                      // hands per workgroup and trip
+    constexpr uint32_t kCompl = NC == 7 ? 1u : (NC == 6 ? 46u : kEhsPairs);  // completions of a hand
+    __shared__ uint32_t acc[kEhsWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t base = blockIdx.x * kPer; base < n; base += gridDim.x * kPer) {
+        if (threadIdx.x < kEhsWaves) acc[threadIdx.x] = 0;
+        __syncthreads();
+        const uint32_t h = NC == 7 ? base + wave : base;
+        const uint32_t slot = NC == 7 ? wave : 0;
+        bool ok = h < n;
+        uint64_t held = 0;
+        uint32_t own[4] = {0, 0, 0, 0}, brd[4] = {0, 0, 0, 0};
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const uint32_t c = cards[(size_t)i * pitch + h];
+                ok = ok && c < 52u;
+                held |= 1ull << (c & 63u);
+                if (i >= 2) add_card(brd, c);
+                else add_card(own, c);
+            }
+            ok = ok && __popcll(held) == NC;
+            if (!ok && (NC == 7 ? lane == 0 : threadIdx.x == 0)) atomicOr(err, 1u);
+        }
+        if (ok) {
+            const uint64_t free0 = kDeck & ~held;   // 45 / 46 / 47 cards
+            uint32_t sum = 0;                        // of 2 [opp < own] + [opp == own]
+            for (uint32_t co = NC == 7 ? 0 : wave; co < kCompl; co += NC == 7 ? 1 : kEhsWaves) {
+                uint32_t b[4] = {brd[0], brd[1], brd[2], brd[3]};
+                uint64_t free7 = free0;
+                if (NC == 6) {
+                    const uint32_t c = nth_bit(free0, co);
+                    add_card(b, c);
+                    free7 &= ~(1ull << c);
+                }
+                if (NC == 5) {
+                    uint32_t i, j;
+                    pair_of<47>(co, i, j);
+                    const uint32_t ci = nth_bit(free0, i), cj = nth_bit(free0, j);
+                    add_card(b, ci);
+                    add_card(b, cj);
+                    free7 &= ~(1ull << ci | 1ull << cj);
+                }
+                const uint32_t mine[4] = {b[0] | own[0], b[1] | own[1], b[2] | own[2], b[3] | own[3]};
+                const uint32_t s = evaluate_suits(mine);
+                for (uint32_t o = lane; o < kEhsOpp; o += 64) {
+                    uint32_t i, j;
+                    pair_of<45>(o, i, j);
+                    uint32_t m[4] = {b[0], b[1], b[2], b[3]};
+                    add_card(m, nth_bit(free7, i));
+                    add_card(m, nth_bit(free7, j));
+                    const uint32_t so = evaluate_suits(m);
+                    sum += so < s ? 2u : (so == s ? 1u : 0u);
+                }
+            }
+            atomicAdd(&acc[slot], sum);
+        }
+        __syncthreads();
+        if (ok && (NC == 7 ? lane == 0 : threadIdx.x == 0)) out[h] = (float)((double)acc[slot] / (double)(2u * kEhsOpp * kCompl));
+        __syncthreads();
+    }
+}
+
+// ---- the sweep ------------------------------------------------------------------------------------------------------------------------------------------
+struct EhsSweep {
+    HandIndexView view;
+    EhsBins bins;
+    const uint8_t *boards;   // [nb][pitch], or nullptr: board number blockIdx.x of all C(52, nb)
+    uint32_t pitch;
+    int32_t nb;              // 3 or 4
+    float *out;              // [size(1)][n_bins]
+    uint32_t *err;
+};
+
+// LDS words of one workgroup: the sort buffer, the scores by pair number, the thresholds, the histogram (two uint16 counters per word)
+__host__ __device__ inline uint32_t ehs_sweep_lds_words(int nb, int n_bins) {
+    const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
+    return kEhsSortN + 1088u + (uint32_t)RS_EHS_MAX_BINS + (n_hp * (uint32_t)n_bins + 1u) / 2u;
+}
+
+// the board with colexicographic number idx among the C(52, nb) boards: idx = C(c0, 1) + C(c1, 2) + C(c2, 3) (+ C(c3, 4)), c0 < c1 < c2 (< c3)
+__device__ __forceinline__ uint32_t colex_digit(uint32_t &idx, int k) {
+    uint32_t x = 51;
+    while (hi_choose(x, k) > idx) --x;
+    idx -= (uint32_t)hi_choose(x, k);
+    return x;
+}
+
+__global__ __launch_bounds__(kEhsSweepThreads, 8) void k_ehs_round_hist(const EhsSweep a) {
+    extern __shared__ uint32_t ehs_lds[];
+    uint32_t *sorted = ehs_lds;                                   // [kEhsSortN]
+    uint32_t *sc = sorted + kEhsSortN;                             // [1088] score of pair p
+    float *thr = reinterpret_cast<float *>(sc + 1088);             // [RS_EHS_MAX_BINS]
+    uint32_t *hist = reinterpret_cast<uint32_t *>(thr + RS_EHS_MAX_BINS);
+    const int nb = a.nb, n_bins = a.bins.n_bins;
+    const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
+    const uint32_t n_ro = nb == 3 ? 1176u : 48u;          // run-outs of the board
+    const uint32_t n_compl = nb == 3 ? kEhsPairs : 46u;   // ... that take no card of a given hole pair: the completions of the hand
+    const uint32_t tid = threadIdx.x;
+
+    // the board (uniform over the workgroup)
+    uint32_t bc[4] = {0, 0, 0, 0};
+    if (a.boards) {
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < nb) {
+                bc[i] = a.boards[(size_t)i * a.pitch + blockIdx.x];
+                ok = ok && bc[i] < 52u;
+            }
+        uint64_t m = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < nb) m |= 1ull << (bc[i] & 63u);
+        if (!ok || __popcll(m) != nb) {   // reported, nothing written
+            if (tid == 0) atomicOr(a.err, 1u);
+            return;
+        }
+    } else {
+        uint32_t idx = blockIdx.x;
+        if (nb == 4) bc[3] = colex_digit(idx, 4);
+        bc[2] = colex_digit(idx, 3);
+        bc[1] = colex_digit(idx, 2);
+        bc[0] = idx;
+    }
+    uint64_t board = 0;
+    uint32_t bm[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i < nb) {
+            board |= 1ull << bc[i];
+            add_card(bm, bc[i]);
+        }
+    const uint64_t free0 = kDeck & ~board;   // nf cards
+
+    for (uint32_t i = tid; i < (uint32_t)RS_EHS_MAX_BINS; i += kEhsSweepThreads) thr[i] = a.bins.thr[i];
+    for (uint32_t i = tid; i < (n_hp * (uint32_t)n_bins + 1u) / 2u; i += kEhsSweepThreads) hist[i] = 0;
+    __syncthreads();
+
+    for (uint32_t ro = 0; ro < n_ro; ++ro) {
+        // the run-out's cards and the 5-card board's suit masks
+        uint32_t b5[4] = {bm[0], bm[1], bm[2], bm[3]};
+        uint64_t free5 = free0;   // 47 cards
+        if (nb == 4) {
+            const uint32_t c = nth_bit(free0, ro);
+            add_card(b5, c);
+            free5 &= ~(1ull << c);
+        } else {
+            uint32_t i, j;
+            pair_of<49>(ro, i, j);
+            const uint32_t ci = nth_bit(free0, i), cj = nth_bit(free0, j);
+            add_card(b5, ci);
+            add_card(b5, cj);
+            free5 &= ~(1ull << ci | 1ull << cj);
+        }
+        for (uint32_t p = tid; p < kEhsSortN; p += kEhsSweepThreads) {
+            uint32_t s = 0xffffffffu;   // padding sorts behind every score
+            if (p < kEhsPairs) {
+                uint32_t i, j;
+                pair_of<47>(p, i, j);
+                uint32_t m[4] = {b5[0], b5[1], b5[2], b5[3]};
+                add_card(m, nth_bit(free5, i));
+                add_card(m, nth_bit(free5, j));
+                s = evaluate_suits(m);
+                sc[p] = s;
+            }
+            sorted[p] = s;
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= kEhsSortN; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < kEhsSortN / 2; t += kEhsSweepThreads) {
+                    const uint32_t lo = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), hi = lo | j;
+                    const uint32_t x = sorted[lo], y = sorted[hi];
+                    if ((x > y) == ((lo & k) == 0)) {
+                        sorted[lo] = y;
+                        sorted[hi] = x;
+                    }
+                }
+                __syncthreads();
+            }
+        for (uint32_t p = tid; p < kEhsPairs; p += kEhsSweepThreads) {
+            uint32_t i, j;
+            pair_of<47>(p, i, j);
+            const uint32_t s = sc[p];
+            // scores below and equal among all 1081 pairs (the pair itself is one of the equal ones)
+            uint32_t lb = 0, ub = 0;
+#pragma unroll
+            for (uint32_t step = kEhsSortN / 2; step; step >>= 1) {
+                if (sorted[lb + step - 1] < s) lb += step;
+                if (sorted[ub + step - 1] <= s) ub += step;
+            }
+            // ... and among the 46 pairs that hold its first card and the 46 that hold its second (it stands in both lists)
+            uint32_t below = 0, equal = 0;
+            for (uint32_t d = 1; d <= 23; ++d) {
+                const uint32_t q0 = sc[i * 23 + d - 1], q1 = sc[((i + 47 - d) % 47) * 23 + d - 1];
+                const uint32_t q2 = sc[j * 23 + d - 1], q3 = sc[((j + 47 - d) % 47) * 23 + d - 1];
+                below += (q0 < s) + (q1 < s) + (q2 < s) + (q3 < s);
+                equal += (q0 == s) + (q1 == s) + (q2 == s) + (q3 == s);
+            }
+            const uint32_t w = lb - below, t = (ub - lb) - equal + 1u;   // over the 990 hands that share no card with it
+            const float v = (float)((double)(2u * w + t) / (double)(2u * kEhsOpp));
+            const uint32_t bin = ehs_bin_of(thr, n_bins, v);
+            // the hole pair's number among the pairs of the board's free cards
+            const uint32_t ci = nth_bit(free5, i), cj = nth_bit(free5, j);
+            const uint32_t pi = (uint32_t)__popcll(free0 & ((1ull << ci) - 1)), pj = (uint32_t)__popcll(free0 & ((1ull << cj) - 1));
+            const uint32_t hi = pi > pj ? pi : pj, lo = pi > pj ? pj : pi;
+            const uint32_t cell = (hi * (hi - 1) / 2 + lo) * (uint32_t)n_bins + bin;
+            atomicAdd(&hist[cell >> 1], 1u << (16u * (cell & 1u)));   // a counter never passes n_ro <= 1176: no carry into its neighbour
+        }
+        __syncthreads();
+    }
+
+    // normalise and scatter through the indexer; the card bytes of a hand stand in LDS (the sort buffer is free now) so that hand_index reads no private array
+    uint8_t *hand = reinterpret_cast<uint8_t *>(sorted) + tid * 8u;
+    for (uint32_t hp = tid; hp < n_hp; hp += kEhsSweepThreads) {
+        uint32_t hi = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)hp)) * 0.5f);
+        while (hi * (hi - 1) / 2 > hp) --hi;
+        while ((hi + 1) * hi / 2 <= hp) ++hi;
+        const uint32_t lo = hp - hi * (hi - 1) / 2;
+        hand[0] = (uint8_t)nth_bit(free0, lo);
+        hand[1] = (uint8_t)nth_bit(free0, hi);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < nb) hand[2 + i] = (uint8_t)bc[i];
+        const uint64_t row = hand_index(a.view, 1, hand);
+        float *dst = a.out + row * (uint64_t)n_bins;
+        for (int k = 0; k < n_bins; ++k) {
+            const uint32_t cell = hp * (uint32_t)n_bins + (uint32_t)k;
+            dst[k] = (float)((hist[cell >> 1] >> (16u * (cell & 1u))) & 0xffffu) / (float)n_compl;
+        }
+    }
+}
+
+}  // namespace rs
+
+namespace {
+
+// get_bin's thresholds (gen_abstraction/main.rs:58-70), accumulated in f32 exactly as its loop does
+void ehs_thresholds(int n_bins, float *thr) {
+    const float interval = 1.0f / (float)n_bins;
+    float threshold = 1.0f - interval;
+    thr[0] = 0.0f;
+    for (int bin = n_bins - 1; bin > 0; --bin) {
+        thr[bin] = threshold;
+        threshold -= interval;
+    }
+}
+
+// the kernels' error word, read back by the call
+int read_err(rs_table *t, const uint32_t *d_err, const char *who, const char *what) {
+    uint32_t err = 0;
+    RS_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, t->stream), who);
+    RS_HIP(hipStreamSynchronize(t->stream), who);
+    if (err) return fail(RS_ERR_INVALID, std::string(who) + ": " + what + " repeats a card or holds a byte that is not a card (0..51); nothing was written for it");
+    return RS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rs_ehs_bin(float value, int n_bins) {
+    if (n_bins < 1 || n_bins > RS_EHS_MAX_BINS) return fail(RS_ERR_INVALID, "rs_ehs_bin: n_bins must be 1..RS_EHS_MAX_BINS");
+    float thr[RS_EHS_MAX_BINS];
+    ehs_thresholds(n_bins, thr);
+    for (int bin = n_bins - 1; bin > 0; --bin)
+        if (value > thr[bin]) return bin;
+    return 0;
+}
+
+int rs_ehs(rs_table *t, const uint8_t *d_cards, int n_cards, uint32_t n, float *d_out) {
+    if (!t) return fail(RS_ERR_INVALID, "rs_ehs: NULL table");
+    if (n_cards != 5 && n_cards != 6 && n_cards != 7) return fail(RS_ERR_INVALID, "rs_ehs: n_cards must be 5, 6 or 7 (two hole cards and a flop, turn or river board)");
+    if (n && (!d_out || !d_cards)) return fail(RS_ERR_INVALID, "rs_ehs: NULL cards or output with n > 0");
+    if (n == 0) return RS_OK;
+    if (int rc_ = rs::table_settle(t, false)) return rc_;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    DevBuf<uint32_t> d_err;
+    RS_HIP(d_err.alloc(1), "rs_ehs: error word");
+    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ehs");
+    const uint32_t pitch = uint32_t(round_up(n, kLanePad));
+    const uint32_t per = n_cards == 7 ? uint32_t(kEhsWaves) : 1u;
+    const dim3 grid(std::min((n + per - 1) / per, 65536u)), block(kEhsThreads);
+    if (n_cards == 7) hipLaunchKernelGGL(k_ehs<7>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
+    else if (n_cards == 6) hipLaunchKernelGGL(k_ehs<6>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
+    else hipLaunchKernelGGL(k_ehs<5>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
+    RS_HIP(hipGetLastError(), "k_ehs");
+    return read_err(t, d_err, "rs_ehs", "a hand");
+}
+
+int rs_ehs_round_histograms(rs_table *t, rs_hand_indexer *ix, int n_bins, const uint8_t *d_boards, uint32_t n_boards, float *d_out) {
+    if (!t || !ix) return fail(RS_ERR_INVALID, "rs_ehs_round_histograms: NULL argument");
+    const int nc = rs_hand_indexer_n_cards(ix, 1);
+    if (rs_hand_indexer_rounds(ix) != 2 || rs_hand_indexer_n_cards(ix, 0) != 2 || (nc != 5 && nc != 6))
+        return fail(RS_ERR_INVALID, "rs_ehs_round_histograms: the indexer must be hand_indexer_s::init(2, [2, 3]) (flop) or (2, [2, 4]) (turn)");
+    if (n_bins < 1 || n_bins > RS_EHS_MAX_BINS) return fail(RS_ERR_INVALID, "rs_ehs_round_histograms: n_bins must be 1..RS_EHS_MAX_BINS");
+    const int nb = nc - 2;
+    if (!d_boards) n_boards = nb == 3 ? 22100u : 270725u;
+    if (n_boards && !d_out) return fail(RS_ERR_INVALID, "rs_ehs_round_histograms: NULL output");
+    if (n_boards == 0) return RS_OK;
+    if (int rc_ = rs::table_settle(t, false)) return rc_;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    EhsSweep a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = hand_indexer_view_on(ix, t->device, t->stream, &a.view)) return rc;
+    ehs_thresholds(n_bins, a.bins.thr);
+    a.bins.n_bins = n_bins;
+    a.boards = d_boards;
+    a.pitch = uint32_t(round_up(n_boards, kLanePad));
+    a.nb = nb;
+    a.out = d_out;
+    const size_t lds = size_t(ehs_sweep_lds_words(nb, n_bins)) * sizeof(uint32_t);
+    if (lds > 64 * 1024) {   // beyond what a launch gets unasked
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_ehs_round_hist), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RS_ERR_UNSUPPORTED, "rs_ehs_round_histograms: the device grants no workgroup " + std::to_string(lds) + " bytes of LDS (" + hipGetErrorString(e) + ")");
+        }
+    }
+    DevBuf<uint32_t> d_err;
+    RS_HIP(d_err.alloc(1), "rs_ehs_round_histograms: error word");
+    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ehs_round_histograms");
+    a.err = d_err;
+    hipLaunchKernelGGL(k_ehs_round_hist, dim3(n_boards), dim3(kEhsSweepThreads), lds, t->stream, a);
+    RS_HIP(hipGetLastError(), "k_ehs_round_hist");
+    return read_err(t, d_err, "rs_ehs_round_histograms", "a board");
+}
+
+}  // extern "C"

@@ -507,7 +507,11 @@ struct rs_table {
 };
 
 struct rs_card_abs;
+struct rs_hand_indexer;
 namespace rs {
+struct HandIndexView;
+// the indexer's tables on `device` (rs_cards.hip; the mirror is created on first use and lives as long as the indexer) for kernels outside rs_cards.hip (rs_ehs.hip)
+int hand_indexer_view_on(rs_hand_indexer *indexer, int device, hipStream_t stream, HandIndexView *out);
 // card kernels on a stream of the caller's choice (rs_cards.hip); the C ABI forms use the table's stream
 int card_abs_clusters_on(rs_card_abs *abs, rs_table *t, hipStream_t stream, const uint8_t *d_cards, uint32_t n_deals, uint32_t *d_cluster_p0,
                          uint32_t *d_cluster_p1);
