@@ -11,6 +11,7 @@ Scores come from oracle.np_br.scores7 (an evaluator written independently of the
 shares-a-card mask (the definition), and the rank-order form with card removal (fast; what whole boards are computed with)."""
 import functools
 import itertools
+import math
 
 import numpy as np
 
@@ -144,9 +145,9 @@ def histogram(cards, n_bins):
     return count.astype(F32) / F32(len(comps))
 
 
-def board_counts(board):
-    """every hole pair of a flop or turn board, through the rank-order form: -> (pairs [n][2], 2 W + T per run-out [n][n_runouts], -1 where the run-out takes a card of the pair)"""
-    board = [int(c) for c in board]
+@functools.lru_cache(maxsize=64)
+def _board_counts(board):
+    board = list(board)
     pairs = hole_pairs(board)
     runouts = list(itertools.combinations(free_cards(board), 5 - len(board)))
     out = np.full((len(pairs), len(runouts)), -1, dtype=np.int64)
@@ -154,7 +155,15 @@ def board_counts(board):
         k2, pid = _river_k2(tuple(sorted(board + list(extra))))
         p = pid[pairs[:, 0], pairs[:, 1]]
         out[p >= 0, r] = k2[p[p >= 0]]
+    pairs.setflags(write=False)
+    out.setflags(write=False)
     return pairs, out
+
+
+def board_counts(board):
+    """every hole pair of a flop or turn board, through the rank-order form: -> (pairs [n][2], 2 W + T per run-out [n][n_runouts], -1 where the run-out takes a card of the pair).
+    Kept per board (in the order its cards are given) and handed out read-only: a board shared between tests is paid for once"""
+    return _board_counts(tuple(int(c) for c in board))
 
 
 def board_histograms(board, n_bins):
@@ -168,3 +177,83 @@ def board_histograms(board, n_bins):
         live = k2[:, r] >= 0
         np.add.at(count, (np.nonzero(live)[0], lut[k2[live, r]]), 1)
     return pairs, count.astype(F32) / F32(n_compl)
+
+
+# ---- whole rounds: the boards by number, and the words a histogram row can hold ------------------------------------------------------------------------------------
+def board_by_number(nb, idx):
+    """the board with colexicographic number idx among the C(52, nb) sets of nb cards, ascending: idx = C(c0, 1) + C(c1, 2) + ... + C(c[nb-1], nb), c0 < c1 < ...
+    (the combinatorial number system: the highest card is the largest c with C(c, nb) <= idx, and so on down)"""
+    idx = int(idx)
+    assert 0 <= idx < math.comb(52, nb)
+    cards = []
+    for k in range(nb, 0, -1):
+        c = k - 1
+        while math.comb(c + 1, k) <= idx:
+            c += 1
+        idx -= math.comb(c, k)
+        cards.append(c)
+    return cards[::-1]
+
+
+def board_number(board):
+    """the inverse: the cards in any order"""
+    return sum(math.comb(int(c), k + 1) for k, c in enumerate(sorted(int(c) for c in board)))
+
+
+@functools.lru_cache(maxsize=None)
+def round_boards(nb):
+    """every board of nb cards in colexicographic order (row idx is board_by_number(nb, idx)): uint8 [C(52, nb)][nb], read-only.  By the order's definition -- compare
+    the highest cards first -- not by the digits"""
+    b = np.array(list(itertools.combinations(range(52), nb)), dtype=np.uint8)
+    b = b[np.lexsort(tuple(b[:, i] for i in range(nb)))]      # lexsort's LAST key is the primary one: the highest card
+    b.setflags(write=False)
+    return b
+
+
+def thresholds(n_bins):
+    """get_bin's thresholds as its loop accumulates them: f32 [n_bins], thr[b] for b = 1 .. n_bins - 1 is what a value must exceed to land in bin b or above; thr[0] is
+    unused (bin 0 takes the rest) and set to -inf"""
+    thr = np.full(n_bins, -np.inf, dtype=F32)
+    interval = F32(1) / F32(n_bins)
+    threshold = F32(1) - interval
+    for b in range(n_bins - 1, 0, -1):
+        thr[b] = threshold
+        threshold = F32(threshold - interval)
+    return thr
+
+
+def on_threshold(n_bins):
+    """the k in 0..1980 whose value f32(k / 1980) is bit-equal to one of get_bin's thresholds: [(k, b)], thr[b] the threshold hit"""
+    thr = thresholds(n_bins)
+    values = np.array([ehs_value(k, 2 * N_OPP) for k in range(2 * N_OPP + 1)], dtype=F32)
+    return [(int(k), int(b)) for b in range(1, n_bins) for k in np.nonzero(values == thr[b])[0]]
+
+
+@functools.lru_cache(maxsize=None)
+def count_words(n_compl):
+    """the n_compl + 1 words a histogram cell can hold, f32(k) / f32(n_compl) for k = 0 .. n_compl, as uint32: positive floats, so ascending in k as integers too"""
+    w = (np.arange(n_compl + 1, dtype=F32) / F32(n_compl)).view(np.uint32)
+    assert (np.diff(w.astype(np.int64)) > 0).all()
+    w.setflags(write=False)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def _count_lut(n_compl):
+    """count_words told apart by their high bits alone: (shift, int16 table over word >> shift; -1: no cell word starts so; the last entry takes every larger word)"""
+    words = count_words(n_compl)
+    shift = 31
+    while len(np.unique(words >> np.uint32(shift))) < len(words):
+        shift -= 1
+    lut = np.full((int(words[-1]) >> shift) + 2, -1, dtype=np.int16)
+    lut[words >> np.uint32(shift)] = np.arange(len(words), dtype=np.int16)
+    return shift, lut
+
+
+def counts_of_words(words, n_compl):
+    """uint32 words of histogram rows -> the count k each holds exactly (int16, same shape); -1 where a word is none of count_words(n_compl).  A table lookup on the
+    high bits finds the only candidate, the comparison of all 32 bits decides (np.searchsorted over the sorted words says the same, at ten times the cost)"""
+    shift, lut = _count_lut(n_compl)
+    k = lut[np.minimum(words >> np.uint32(shift), np.uint32(len(lut) - 1))]
+    k[count_words(n_compl)[k] != words] = -1            # k = -1 reads the last word, 1.0, whose own high bits give n_compl: never equal here
+    return k
