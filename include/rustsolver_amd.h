@@ -877,6 +877,36 @@ int rs_ehs(rs_table *table, const uint8_t *d_cards, int n_cards, uint32_t n, flo
  * Synchronises. */
 int rs_ehs_round_histograms(rs_table *table, rs_hand_indexer *indexer, int n_bins, const uint8_t *d_boards, uint32_t n_boards, float *d_out);
 
+/* ---- exact OCHS features: a hand's equity against each of a few opponent ranges (gen_abstraction/main.rs:161-330 gen_ochs) ---------------------------------------------
+ * The river's bucket file comes from an L2 k-means over these vectors (a river hand has one EHS value, not a distribution).  The reference samples them
+ * (`calc_equity(..., 1000)`, thread_rng) and ships the generator commented out; here, as above, everything is enumerated.
+ *   opponent partition   pair_cluster[1326] (host): one entry per hole pair c0 < c1 at index c1 (c1 - 1) / 2 + c0, a cluster id 0 .. n_clusters - 1 or
+ *                        RS_OCHS_NO_CLUSTER for a hand that is in no range; 1 <= n_clusters <= RS_OCHS_MAX_CLUSTERS (the reference's n_opp_clusters is 8).  Any
+ *                        partition is taken: nothing here knows of preflop classes.
+ *   feature of a hand    hole pair h and a board b of 3, 4 or 5 cards.  For cluster k, over every completion r of the board to 5 cards from the cards not in h or b
+ *                        (the river has the single empty one) and every opponent pair o with pair_cluster[o] == k that shares no card with h, b or r: W_k score lower
+ *                        than h, T_k equal, N_k is their count.  e_k = (float)((double)(2 W_k + T_k) / (double)(2 N_k)), and +0.0 where N_k == 0.
+ *   normalize != 0       the reference's hist[i] /= norm_sum (main.rs:281-297): s = e_0 + e_1 + ... in f32 in index order, out_k = e_k / s in f32.  A row whose s is 0
+ *                        stays all +0.0 (the reference would write NaN there).
+ *   preflop counts       for hole pair p and a flop f that shares no card with it, count_f[p][bin] = the number of the 1081 completions whose river EHS (rs_ehs's
+ *                        value) falls in rs_ehs_bin(., n_bins): the un-normalised row of rs_ehs_round_histograms.  counts[p][bin] sums them over the swept flops.  Over
+ *                        all 22 100 flops each of the pair's C(50, 5) boards is met C(5, 3) = 10 times: every row sums to 21 187 600, every cell is a multiple of 10.
+ * Everything before the last division is an integer (2 W + T <= 2 * 1176 * 990): nothing depends on summation order or kernel form. */
+#define RS_OCHS_MAX_CLUSTERS 8
+#define RS_OCHS_NO_CLUSTER   255
+/* indexer = hand_indexer_s::init(2, [2, 3] | [2, 4] | [2, 5]); d_out[rs_hand_indexer_size(indexer, 1)][n_clusters].
+ * d_boards[3|4|5][pitch] (pitch = round_up(n_boards, 64)) lists boards (any order of cards within a board): the rows of the 1176 / 1128 / 1081 hole pairs of each are
+ * written, the others left as they were.  NULL = the whole round: every row of d_out is written, with the bits that listing all C(52, nb) boards would give (the call
+ * sweeps one board per suit-isomorphism class -- 1 755 / 16 432 / 134 459 -- from a list it builds, uploads and frees).  Suit-isomorphic copies write identical bits:
+ * plain stores.  RS_ERR_INVALID before anything is launched or allocated: an indexer of another shape, n_clusters out of range, a pair_cluster entry that is neither
+ * an id below n_clusters nor RS_OCHS_NO_CLUSTER, NULL d_out with work to do.  A listed board with a repeated card or a byte >= 52 is skipped and reported as for
+ * rs_ehs_round_histograms (RS_ERR_INVALID, the other boards done).  Synchronises. */
+int rs_ochs_round_features(rs_table *table, rs_hand_indexer *indexer, const uint8_t *pair_cluster, int n_clusters, int normalize,
+                           const uint8_t *d_boards, uint32_t n_boards, float *d_out);
+/* d_counts[1326][n_bins] uint32 (row = c1 (c1 - 1) / 2 + c0), zeroed by the call; d_boards[3][pitch] or NULL = all 22 100 flops.  RS_ERR_INVALID before anything is
+ * launched or allocated: n_bins outside 1..RS_EHS_MAX_BINS, NULL d_counts.  A bad listed board: as above.  Synchronises. */
+int rs_ehs_preflop_counts(rs_table *table, int n_bins, const uint8_t *d_boards, uint32_t n_boards, uint32_t *d_counts);
+
 /* ---- showdown evaluation on the device ---------------------------------------------------------------
  * d_cards[9][pitch] (u8, pitch = round_up(n_deals, 64)): rows 0-4 the board, 5-6 player 0's hole cards, 7-8 player 1's;
  * card = 4*rank + suit, rank 0..12 = 2..A (cfr.rs:592).  d_sign[lane] = sign(evaluate(hand0) - evaluate(hand1)) exactly as

@@ -27,6 +27,7 @@ BR_CURRENT = 0x400          # | into any mode: the strategies read are the CURRE
 DEAL_SEQUENTIAL, DEAL_JOINT = 0, 1   # rs_range_weights.deal (RS_DEAL_*)
 DIST_EMD, DIST_L2 = 0, 1
 EHS_MAX_BINS = 64           # RS_EHS_MAX_BINS
+OCHS_MAX_CLUSTERS, OCHS_NO_CLUSTER = 8, 255   # RS_OCHS_*
 K_UPDATE, K_NODE_UTIL, K_REACH, K_CHANCE, K_DISCOUNT, K_STRATEGY, K_TREE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -301,6 +302,8 @@ SYMBOLS = {
     "rs_ehs_bin": (C.c_int, [C.c_float, C.c_int]),
     "rs_ehs": (C.c_int, [_P, _P, C.c_int, C.c_uint32, _P]),
     "rs_ehs_round_histograms": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint32, _P]),
+    "rs_ochs_round_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_uint32, _P]),
+    "rs_ehs_preflop_counts": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P]),
     "rs_table_save": (C.c_int, [_P, C.c_char_p]),
     "rs_table_load": (C.c_int, [C.c_char_p, C.c_int, _PP]),
     "rs_profile_enable": (C.c_int, [_P, C.c_int]),

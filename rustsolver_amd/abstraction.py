@@ -362,6 +362,121 @@ def round_histograms(table, indexer, n_bins, boards=None, out=None):
     return out
 
 
+# ---- exact OCHS features and the opponent ranges they are measured against (rs_ochs.hip; semantics in include/rustsolver_amd.h) -----------------------------
+OCHS_MAX_CLUSTERS, OCHS_NO_CLUSTER = L.OCHS_MAX_CLUSTERS, L.OCHS_NO_CLUSTER
+PREFLOP_ROW_SUM = 21187600   # C(50, 5) boards of a hole pair, each met on C(5, 3) flops
+
+
+def hole_pair_index(c0, c1):
+    """the row of a hole pair in pair_cluster and in the preflop counts: c1 (c1 - 1) / 2 + c0 for c0 < c1 (either order given)"""
+    lo, hi = np.minimum(c0, c1), np.maximum(c0, c1)
+    return hi * (hi - 1) // 2 + lo
+
+
+def _hole_pairs():
+    """uint8 [1326][2]: the cards of every hole pair in hole_pair_index order"""
+    return np.array([(c0, c1) for c1 in range(52) for c0 in range(c1)], dtype=np.uint8)
+
+
+def _board_rows(table, boards, n_cards):
+    b = np.ascontiguousarray(boards, dtype=np.uint8)
+    b = b.reshape(-1, b.shape[-1])
+    if b.shape[1] != n_cards:
+        raise ValueError("a board of this round has %d cards" % n_cards)
+    return _card_rows(table, b, n_cards)
+
+
+def ochs_features(table, indexer, pair_cluster, n_clusters, normalize=True, boards=None, out=None):
+    """The OCHS feature vectors of a flop ([2, 3]), turn ([2, 4]) or river ([2, 5]) round on the device: one row of n_clusters equities per canonical hand index.
+    pair_cluster: uint8 [1326] by hole_pair_index, a cluster id or OCHS_NO_CLUSTER.  boards: uint8 [n][3, 4 or 5], or None = the whole round (every row is
+    written).  Rows whose hands lie on no listed board are left as they were (a buffer made here starts at zero).  -> RoundHistograms (rows x n_clusters), which
+    Kmeans.from_device takes as it is"""
+    from .solver import DeviceBuffer
+    pc = np.ascontiguousarray(pair_cluster, dtype=np.uint8).reshape(-1)
+    if len(pc) != 1326:
+        raise ValueError("pair_cluster has one entry per hole pair: 1326")
+    if out is None:
+        rows = indexer.size(indexer.rounds - 1)
+        out = RoundHistograms(table, rows, n_clusters, DeviceBuffer(table, max(rows * max(n_clusters, 0), 1) * 4))
+        out.buffer.zero()
+    db, n = None, 0
+    if boards is not None:
+        if np.asarray(boards).size == 0:
+            return out
+        db, n = _board_rows(table, boards, indexer.n_cards(indexer.rounds - 1) - 2)
+    L.check(L.load().rs_ochs_round_features(table._h, indexer._h, pc.ctypes.data, n_clusters, int(bool(normalize)), db.ptr if db else None, n, out.ptr))
+    return out
+
+
+def preflop_counts(table, n_bins, boards=None):
+    """For every hole pair (hole_pair_index order) the river-EHS bin counts of its completions, summed over the listed flops (uint8 [n][3]) or over all 22 100:
+    -> uint32 [1326][n_bins].  Over all flops every row sums to PREFLOP_ROW_SUM"""
+    from .solver import DeviceBuffer
+    do = DeviceBuffer(table, 1326 * max(n_bins, 1) * 4)
+    db, n = None, 0
+    if boards is not None:
+        if np.asarray(boards).size == 0:
+            return np.zeros((1326, n_bins), dtype=np.uint32)
+        db, n = _board_rows(table, boards, 3)
+    L.check(L.load().rs_ehs_preflop_counts(table._h, n_bins, db.ptr if db else None, n, do.ptr))
+    return do.download(np.uint32, 1326 * n_bins).reshape(1326, n_bins)
+
+
+def _preflop_classes():
+    """-> (HandIndexer([2]) row of every hole pair [1326], pairs per row [169])"""
+    rows = HandIndexer([2]).get_index(_hole_pairs()).astype(np.int64)
+    return rows, np.bincount(rows, minlength=169)
+
+
+def _class_histograms(counts):
+    rows, n_pairs = _preflop_classes()
+    sums = np.zeros((169, counts.shape[1]), dtype=np.int64)
+    np.add.at(sums, rows, counts.astype(np.int64))
+    return (sums.astype(np.float64) / (n_pairs * PREFLOP_ROW_SUM).astype(np.float64)[:, None]).astype(np.float32)
+
+
+def preflop_histograms(table, n_bins):
+    """The EHS histograms of the 169 preflop classes (generate_histograms(.., 0, n_bins) by enumeration): float32 [169][n_bins]; row r of HandIndexer([2]) is
+    f32(f64(sum of its pairs' counts) / f64(n_pairs x PREFLOP_ROW_SUM))"""
+    return _class_histograms(preflop_counts(table, n_bins))
+
+
+def opponent_clusters(table, n_clusters, n_bins=35, seed=1):
+    """generate_opponent_clusters (gen_abstraction/main.rs:161-236): the 169 preflop classes clustered into n_clusters opponent ranges by their EHS histograms --
+    kmeans++ (init_pp: a uniform first center, then draws weighted by update_min_dists) with EMD, fit_regular, predict -- and expanded to pair_cluster uint8 [1326].
+    The draws come from numpy's Generator(PCG64(seed)) where the reference uses thread_rng.
+    A deviation: the reference orders the ranges by an all-in equity it samples (calc_equity(range vs random, 10000)); here range 0 .. n_clusters - 1 ascend by the
+    combo-weighted mean bin of their members' summed counts (f64 from integers), ties to the range with the lowest member row; a range without members sorts last."""
+    if not 1 <= n_clusters <= OCHS_MAX_CLUSTERS:
+        raise ValueError("n_clusters must be 1..OCHS_MAX_CLUSTERS")
+    counts = preflop_counts(table, n_bins).astype(np.int64)
+    hist = _class_histograms(counts)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    km = Kmeans(table, hist)
+    centers = [hist[int(rng.integers(0, len(hist)))]]
+    min_dists = np.full(len(hist), np.finfo(np.float32).max, dtype=np.float32)
+    for _ in range(1, n_clusters):
+        min_dists = km.update_min_dists(min_dists, centers[-1])
+        w = min_dists.astype(np.float64)
+        if not w.sum() > 0:
+            raise ValueError("fewer distinct preflop histograms than opponent clusters")
+        centers.append(hist[int(rng.choice(len(hist), p=w / w.sum()))])
+    _, centers, _, _ = km.fit_regular(np.stack(centers))
+    clusters, _ = km.predict(centers)
+    rows, _ = _preflop_classes()
+    of_pair = clusters.astype(np.int64)[rows]
+    keys = []
+    for c in range(n_clusters):
+        total = counts[of_pair == c].sum(axis=0)
+        members = np.nonzero(clusters == c)[0]
+        mean = float(np.dot(np.arange(n_bins, dtype=np.float64), total.astype(np.float64)) / np.float64(total.sum())) if len(members) else np.inf
+        keys.append((mean, int(members[0]) if len(members) else 169 + c, c))
+    rank = np.empty(n_clusters, dtype=np.uint8)
+    for new, (_, _, c) in enumerate(sorted(keys)):
+        rank[c] = new
+    return rank[of_pair]
+
+
 class Kmeans:
     """The distance sweeps of gen_abstraction/kmeans.rs on the GPU: `predict` (kmeans.rs:173-211) and the kmeans++ `update_min_dists`
     (kmeans.rs:603-619).  The dataset stays resident on the device between calls."""

@@ -10,9 +10,7 @@
 #include <cstring>
 #include <string>
 
-#include "rs_hand_index.hpp"
-#include "rs_internal.hpp"
-#include "rs_eval.hpp"
+#include "rs_ehs_dev.hpp"
 
 using namespace rs;
 
@@ -27,57 +25,6 @@ namespace rs {
 constexpr int kEhsThreads = 256;         // the lookup form
 constexpr int kEhsWaves = kEhsThreads / 64;
 constexpr int kEhsSweepThreads = 1024;   // the sweep: LDS allows two workgroups per CU at 20-30 bins, so a workgroup brings 16 waves and is held to 8 per SIMD (profiles/ehs.md)
-constexpr uint32_t kEhsOpp = 990;      // C(45, 2) opponent hands of a 7-card hand
-constexpr uint32_t kEhsPairs = 1081;   // C(47, 2) hole pairs of a 5-card board
-constexpr uint32_t kEhsSortN = 2048;   // the bitonic network's width
-constexpr uint64_t kDeck = (1ull << 52) - 1;
-
-// thr[b], b = 1 .. n_bins - 1: get_bin's thresholds as its loop accumulates them (thr[0] is never read).  Non-decreasing in b.
-struct EhsBins {
-    float thr[RS_EHS_MAX_BINS];
-    int32_t n_bins;
-};
-
-// position of the n-th (from 0) set bit of m; n < popcount(m)
-__device__ __forceinline__ uint32_t nth_bit(uint64_t m, uint32_t n) {
-    uint32_t w = (uint32_t)m, pos = 0, c = (uint32_t)__popc(w);
-    if (n >= c) {
-        n -= c;
-        w = (uint32_t)(m >> 32);
-        pos = 32;
-    }
-#pragma unroll
-    for (int sh = 16; sh >= 1; sh >>= 1) {
-        const uint32_t lo = w & ((1u << sh) - 1u);
-        c = (uint32_t)__popc(lo);
-        if (n >= c) {
-            n -= c;
-            w >>= sh;
-            pos += (uint32_t)sh;
-        } else w = lo;
-    }
-    return pos;
-}
-
-// Unordered pairs of M elements, M odd, numbered 0 .. M (M - 1) / 2 - 1: pair p = (a, (a + d) mod M) with a = p / H, d = p % H + 1, H = (M - 1) / 2 -- every
-// pair has exactly one circular distance in 1 .. H.  The pairs that hold element i are i * H + d - 1 and ((i - d) mod M) * H + d - 1, d = 1 .. H.
-template <uint32_t M>
-__device__ __forceinline__ void pair_of(uint32_t p, uint32_t &i, uint32_t &j) {
-    constexpr uint32_t H = (M - 1) / 2;
-    i = p / H;
-    j = (i + p % H + 1) % M;
-}
-
-// get_bin over the staged thresholds: the largest b with v > thr[b], else 0 (thr is non-decreasing, so the predicate is monotone in b)
-__device__ __forceinline__ uint32_t ehs_bin_of(const float *thr, int n_bins, float v) {
-    int b = 0;
-#pragma unroll
-    for (int step = RS_EHS_MAX_BINS / 2; step; step >>= 1) {
-        const int c = b + step;
-        if (c < n_bins && v > thr[c]) b = c;
-    }
-    return (uint32_t)b;
-}
 
 // ---- the lookup form ------------------------------------------------------------------------------------------------------------------------------------
 // NC = 7: a wave per hand, the lanes share its 990 opponents.  NC = 5 / 6: a workgroup per hand, its waves share the 1081 / 46 completions.
@@ -161,14 +108,6 @@ struct EhsSweep {
 __host__ __device__ inline uint32_t ehs_sweep_lds_words(int nb, int n_bins) {
     const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
     return kEhsSortN + 1088u + (uint32_t)RS_EHS_MAX_BINS + (n_hp * (uint32_t)n_bins + 1u) / 2u;
-}
-
-// the board with colexicographic number idx among the C(52, nb) boards: idx = C(c0, 1) + C(c1, 2) + C(c2, 3) (+ C(c3, 4)), c0 < c1 < c2 (< c3)
-__device__ __forceinline__ uint32_t colex_digit(uint32_t &idx, int k) {
-    uint32_t x = 51;
-    while (hi_choose(x, k) > idx) --x;
-    idx -= (uint32_t)hi_choose(x, k);
-    return x;
 }
 
 __global__ __launch_bounds__(kEhsSweepThreads, 8) void k_ehs_round_hist(const EhsSweep a) {
@@ -319,30 +258,6 @@ __global__ __launch_bounds__(kEhsSweepThreads, 8) void k_ehs_round_hist(const Eh
 
 }  // namespace rs
 
-namespace {
-
-// get_bin's thresholds (gen_abstraction/main.rs:58-70), accumulated in f32 exactly as its loop does
-void ehs_thresholds(int n_bins, float *thr) {
-    const float interval = 1.0f / (float)n_bins;
-    float threshold = 1.0f - interval;
-    thr[0] = 0.0f;
-    for (int bin = n_bins - 1; bin > 0; --bin) {
-        thr[bin] = threshold;
-        threshold -= interval;
-    }
-}
-
-// the kernels' error word, read back by the call
-int read_err(rs_table *t, const uint32_t *d_err, const char *who, const char *what) {
-    uint32_t err = 0;
-    RS_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, t->stream), who);
-    RS_HIP(hipStreamSynchronize(t->stream), who);
-    if (err) return fail(RS_ERR_INVALID, std::string(who) + ": " + what + " repeats a card or holds a byte that is not a card (0..51); nothing was written for it");
-    return RS_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rs_ehs_bin(float value, int n_bins) {
@@ -371,7 +286,7 @@ int rs_ehs(rs_table *t, const uint8_t *d_cards, int n_cards, uint32_t n, float *
     else if (n_cards == 6) hipLaunchKernelGGL(k_ehs<6>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
     else hipLaunchKernelGGL(k_ehs<5>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
     RS_HIP(hipGetLastError(), "k_ehs");
-    return read_err(t, d_err, "rs_ehs", "a hand");
+    return ehs_read_err(t, d_err, "rs_ehs", "a hand");
 }
 
 int rs_ehs_round_histograms(rs_table *t, rs_hand_indexer *ix, int n_bins, const uint8_t *d_boards, uint32_t n_boards, float *d_out) {
@@ -409,7 +324,7 @@ int rs_ehs_round_histograms(rs_table *t, rs_hand_indexer *ix, int n_bins, const 
     a.err = d_err;
     hipLaunchKernelGGL(k_ehs_round_hist, dim3(n_boards), dim3(kEhsSweepThreads), lds, t->stream, a);
     RS_HIP(hipGetLastError(), "k_ehs_round_hist");
-    return read_err(t, d_err, "rs_ehs_round_histograms", "a board");
+    return ehs_read_err(t, d_err, "rs_ehs_round_histograms", "a board");
 }
 
 }  // extern "C"
