@@ -2,9 +2,9 @@
 // generator (gen_abstraction/ehs.rs EHS::get_ehs, main.rs:58-70 get_bin, main.rs generate_histograms), with enumeration in place of the reference's Monte-Carlo
 // calc_equity.  Semantics: include/rustsolver_amd.h.  Everything before the last division is an integer, so results depend on the cards alone.
 //   * k_ehs: the lookup form, one hand per wave (7 cards) or per workgroup (5 / 6 cards), every opponent hand of every completion evaluated;
-//   * k_ehs_round_hist: the sweep, one workgroup per board of the round.  Per run-out (the cards that bring the board to 5) the 1081 hole pairs are evaluated once,
-//     ordered by score in LDS, and each pair's counts come from the rank order with card removal, the way the best-response leaves count (rs_br.hip);
-//     the (hole pair, bin) counters of the board are a uint16 histogram in LDS (profiles/ehs.md).
+//   * k_ehs_round_hist: the sweep, one workgroup per board of the round.  The board's decode and its (hole pair, bin) counters over all run-outs, a uint16 histogram
+//     in LDS (profiles/ehs.md), are sweep_board and board_histogram of rs_ehs_dev.hpp, shared with k_preflop_counts (rs_ochs.hip); what is the kernel's own is the
+//     last step: normalise, hand_index, store.
 // Cards and suits only ever select under predicates (no array indexed by a card): the kernels carry no scratch.  A byte that is no card never indexes LDS: lists are
 // validated before use, and every card the kernels enumerate themselves comes out of a bit mask.
 #include <cstring>
@@ -24,7 +24,6 @@ namespace rs {
 
 constexpr int kEhsThreads = 256;         // the lookup form
 constexpr int kEhsWaves = kEhsThreads / 64;
-constexpr int kEhsSweepThreads = 1024;   // the sweep: LDS allows two workgroups per CU at 20-30 bins, so a workgroup brings 16 waves and is held to 8 per SIMD (profiles/ehs.md)
 
 // ---- the lookup form ------------------------------------------------------------------------------------------------------------------------------------
 // NC = 7: a wave per hand, the lanes share its 990 opponents.  NC = 5 / 6: a workgroup per hand, its waves share the 1081 / 46 completions.
@@ -104,144 +103,28 @@ struct EhsSweep {
     uint32_t *err;
 };
 
-// LDS words of one workgroup: the sort buffer, the scores by pair number, the thresholds, the histogram (two uint16 counters per word)
-__host__ __device__ inline uint32_t ehs_sweep_lds_words(int nb, int n_bins) {
-    const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
-    return kEhsSortN + 1088u + (uint32_t)RS_EHS_MAX_BINS + (n_hp * (uint32_t)n_bins + 1u) / 2u;
-}
-
-__global__ __launch_bounds__(kEhsSweepThreads, 8) void k_ehs_round_hist(const EhsSweep a) {
+__global__ __launch_bounds__(kSweepThreads, 8) void k_ehs_round_hist(const EhsSweep a) {
     extern __shared__ uint32_t ehs_lds[];
-    uint32_t *sorted = ehs_lds;                                   // [kEhsSortN]
-    uint32_t *sc = sorted + kEhsSortN;                             // [1088] score of pair p
-    float *thr = reinterpret_cast<float *>(sc + 1088);             // [RS_EHS_MAX_BINS]
-    uint32_t *hist = reinterpret_cast<uint32_t *>(thr + RS_EHS_MAX_BINS);
+    const HistLds l = carve_hist_lds(ehs_lds);
     const int nb = a.nb, n_bins = a.bins.n_bins;
     const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
-    const uint32_t n_ro = nb == 3 ? 1176u : 48u;          // run-outs of the board
-    const uint32_t n_compl = nb == 3 ? kEhsPairs : 46u;   // ... that take no card of a given hole pair: the completions of the hand
+    const uint32_t n_compl = nb == 3 ? kEhsPairs : 46u;   // run-outs of the board that take no card of a given hole pair: the completions of the hand
     const uint32_t tid = threadIdx.x;
 
-    // the board (uniform over the workgroup)
-    uint32_t bc[4] = {0, 0, 0, 0};
-    if (a.boards) {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < nb) {
-                bc[i] = a.boards[(size_t)i * a.pitch + blockIdx.x];
-                ok = ok && bc[i] < 52u;
-            }
-        uint64_t m = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < nb) m |= 1ull << (bc[i] & 63u);
-        if (!ok || __popcll(m) != nb) {   // reported, nothing written
-            if (tid == 0) atomicOr(a.err, 1u);
-            return;
-        }
-    } else {
-        uint32_t idx = blockIdx.x;
-        if (nb == 4) bc[3] = colex_digit(idx, 4);
-        bc[2] = colex_digit(idx, 3);
-        bc[1] = colex_digit(idx, 2);
-        bc[0] = idx;
+    uint32_t bc[5], bm[4] = {0, 0, 0, 0};
+    uint64_t board;
+    if (!sweep_board(a.boards, a.pitch, nb, bc, board, bm)) {   // uniform over the workgroup: reported, nothing written
+        if (tid == 0) atomicOr(a.err, 1u);
+        return;
     }
-    uint64_t board = 0;
-    uint32_t bm[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (i < nb) {
-            board |= 1ull << bc[i];
-            add_card(bm, bc[i]);
-        }
     const uint64_t free0 = kDeck & ~board;   // nf cards
-
-    for (uint32_t i = tid; i < (uint32_t)RS_EHS_MAX_BINS; i += kEhsSweepThreads) thr[i] = a.bins.thr[i];
-    for (uint32_t i = tid; i < (n_hp * (uint32_t)n_bins + 1u) / 2u; i += kEhsSweepThreads) hist[i] = 0;
-    __syncthreads();
-
-    for (uint32_t ro = 0; ro < n_ro; ++ro) {
-        // the run-out's cards and the 5-card board's suit masks
-        uint32_t b5[4] = {bm[0], bm[1], bm[2], bm[3]};
-        uint64_t free5 = free0;   // 47 cards
-        if (nb == 4) {
-            const uint32_t c = nth_bit(free0, ro);
-            add_card(b5, c);
-            free5 &= ~(1ull << c);
-        } else {
-            uint32_t i, j;
-            pair_of<49>(ro, i, j);
-            const uint32_t ci = nth_bit(free0, i), cj = nth_bit(free0, j);
-            add_card(b5, ci);
-            add_card(b5, cj);
-            free5 &= ~(1ull << ci | 1ull << cj);
-        }
-        for (uint32_t p = tid; p < kEhsSortN; p += kEhsSweepThreads) {
-            uint32_t s = 0xffffffffu;   // padding sorts behind every score
-            if (p < kEhsPairs) {
-                uint32_t i, j;
-                pair_of<47>(p, i, j);
-                uint32_t m[4] = {b5[0], b5[1], b5[2], b5[3]};
-                add_card(m, nth_bit(free5, i));
-                add_card(m, nth_bit(free5, j));
-                s = evaluate_suits(m);
-                sc[p] = s;
-            }
-            sorted[p] = s;
-        }
-        __syncthreads();
-        for (uint32_t k = 2; k <= kEhsSortN; k <<= 1)
-            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-                for (uint32_t t = tid; t < kEhsSortN / 2; t += kEhsSweepThreads) {
-                    const uint32_t lo = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), hi = lo | j;
-                    const uint32_t x = sorted[lo], y = sorted[hi];
-                    if ((x > y) == ((lo & k) == 0)) {
-                        sorted[lo] = y;
-                        sorted[hi] = x;
-                    }
-                }
-                __syncthreads();
-            }
-        for (uint32_t p = tid; p < kEhsPairs; p += kEhsSweepThreads) {
-            uint32_t i, j;
-            pair_of<47>(p, i, j);
-            const uint32_t s = sc[p];
-            // scores below and equal among all 1081 pairs (the pair itself is one of the equal ones)
-            uint32_t lb = 0, ub = 0;
-#pragma unroll
-            for (uint32_t step = kEhsSortN / 2; step; step >>= 1) {
-                if (sorted[lb + step - 1] < s) lb += step;
-                if (sorted[ub + step - 1] <= s) ub += step;
-            }
-            // ... and among the 46 pairs that hold its first card and the 46 that hold its second (it stands in both lists)
-            uint32_t below = 0, equal = 0;
-            for (uint32_t d = 1; d <= 23; ++d) {
-                const uint32_t q0 = sc[i * 23 + d - 1], q1 = sc[((i + 47 - d) % 47) * 23 + d - 1];
-                const uint32_t q2 = sc[j * 23 + d - 1], q3 = sc[((j + 47 - d) % 47) * 23 + d - 1];
-                below += (q0 < s) + (q1 < s) + (q2 < s) + (q3 < s);
-                equal += (q0 == s) + (q1 == s) + (q2 == s) + (q3 == s);
-            }
-            const uint32_t w = lb - below, t = (ub - lb) - equal + 1u;   // over the 990 hands that share no card with it
-            const float v = (float)((double)(2u * w + t) / (double)(2u * kEhsOpp));
-            const uint32_t bin = ehs_bin_of(thr, n_bins, v);
-            // the hole pair's number among the pairs of the board's free cards
-            const uint32_t ci = nth_bit(free5, i), cj = nth_bit(free5, j);
-            const uint32_t pi = (uint32_t)__popcll(free0 & ((1ull << ci) - 1)), pj = (uint32_t)__popcll(free0 & ((1ull << cj) - 1));
-            const uint32_t hi = pi > pj ? pi : pj, lo = pi > pj ? pj : pi;
-            const uint32_t cell = (hi * (hi - 1) / 2 + lo) * (uint32_t)n_bins + bin;
-            atomicAdd(&hist[cell >> 1], 1u << (16u * (cell & 1u)));   // a counter never passes n_ro <= 1176: no carry into its neighbour
-        }
-        __syncthreads();
-    }
+    board_histogram(nb, a.bins, free0, bm, l, tid);
 
     // normalise and scatter through the indexer; the card bytes of a hand stand in LDS (the sort buffer is free now) so that hand_index reads no private array
-    uint8_t *hand = reinterpret_cast<uint8_t *>(sorted) + tid * 8u;
-    for (uint32_t hp = tid; hp < n_hp; hp += kEhsSweepThreads) {
-        uint32_t hi = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)hp)) * 0.5f);
-        while (hi * (hi - 1) / 2 > hp) --hi;
-        while ((hi + 1) * hi / 2 <= hp) ++hi;
-        const uint32_t lo = hp - hi * (hi - 1) / 2;
+    uint8_t *hand = reinterpret_cast<uint8_t *>(l.sorted) + tid * 8u;
+    for (uint32_t hp = tid; hp < n_hp; hp += kSweepThreads) {
+        uint32_t lo, hi;
+        pair_positions(hp, lo, hi);
         hand[0] = (uint8_t)nth_bit(free0, lo);
         hand[1] = (uint8_t)nth_bit(free0, hi);
 #pragma unroll
@@ -249,10 +132,7 @@ __global__ __launch_bounds__(kEhsSweepThreads, 8) void k_ehs_round_hist(const Eh
             if (i < nb) hand[2 + i] = (uint8_t)bc[i];
         const uint64_t row = hand_index(a.view, 1, hand);
         float *dst = a.out + row * (uint64_t)n_bins;
-        for (int k = 0; k < n_bins; ++k) {
-            const uint32_t cell = hp * (uint32_t)n_bins + (uint32_t)k;
-            dst[k] = (float)((hist[cell >> 1] >> (16u * (cell & 1u))) & 0xffffu) / (float)n_compl;
-        }
+        for (int k = 0; k < n_bins; ++k) dst[k] = (float)hist_count(l.hist, hp * (uint32_t)n_bins + (uint32_t)k) / (float)n_compl;
     }
 }
 
@@ -276,17 +156,14 @@ int rs_ehs(rs_table *t, const uint8_t *d_cards, int n_cards, uint32_t n, float *
     if (n == 0) return RS_OK;
     if (int rc_ = rs::table_settle(t, false)) return rc_;
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
-    DevBuf<uint32_t> d_err;
-    RS_HIP(d_err.alloc(1), "rs_ehs: error word");
-    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ehs");
     const uint32_t pitch = uint32_t(round_up(n, kLanePad));
     const uint32_t per = n_cards == 7 ? uint32_t(kEhsWaves) : 1u;
     const dim3 grid(std::min((n + per - 1) / per, 65536u)), block(kEhsThreads);
-    if (n_cards == 7) hipLaunchKernelGGL(k_ehs<7>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
-    else if (n_cards == 6) hipLaunchKernelGGL(k_ehs<6>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
-    else hipLaunchKernelGGL(k_ehs<5>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err.get());
-    RS_HIP(hipGetLastError(), "k_ehs");
-    return ehs_read_err(t, d_err, "rs_ehs", "a hand");
+    return launch_checked(t, "rs_ehs", "k_ehs", "a hand", [&](uint32_t *d_err) {
+        if (n_cards == 7) hipLaunchKernelGGL(k_ehs<7>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err);
+        else if (n_cards == 6) hipLaunchKernelGGL(k_ehs<6>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err);
+        else hipLaunchKernelGGL(k_ehs<5>, grid, block, 0, t->stream, d_cards, n, pitch, d_out, d_err);
+    });
 }
 
 int rs_ehs_round_histograms(rs_table *t, rs_hand_indexer *ix, int n_bins, const uint8_t *d_boards, uint32_t n_boards, float *d_out) {
@@ -311,20 +188,11 @@ int rs_ehs_round_histograms(rs_table *t, rs_hand_indexer *ix, int n_bins, const 
     a.nb = nb;
     a.out = d_out;
     const size_t lds = size_t(ehs_sweep_lds_words(nb, n_bins)) * sizeof(uint32_t);
-    if (lds > 64 * 1024) {   // beyond what a launch gets unasked
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_ehs_round_hist), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RS_ERR_UNSUPPORTED, "rs_ehs_round_histograms: the device grants no workgroup " + std::to_string(lds) + " bytes of LDS (" + hipGetErrorString(e) + ")");
-        }
-    }
-    DevBuf<uint32_t> d_err;
-    RS_HIP(d_err.alloc(1), "rs_ehs_round_histograms: error word");
-    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ehs_round_histograms");
-    a.err = d_err;
-    hipLaunchKernelGGL(k_ehs_round_hist, dim3(n_boards), dim3(kEhsSweepThreads), lds, t->stream, a);
-    RS_HIP(hipGetLastError(), "k_ehs_round_hist");
-    return ehs_read_err(t, d_err, "rs_ehs_round_histograms", "a board");
+    if (int rc = grant_lds(reinterpret_cast<const void *>(k_ehs_round_hist), lds, "rs_ehs_round_histograms")) return rc;
+    return launch_checked(t, "rs_ehs_round_histograms", "k_ehs_round_hist", "a board", [&](uint32_t *d_err) {
+        a.err = d_err;
+        hipLaunchKernelGGL(k_ehs_round_hist, dim3(n_boards), dim3(kSweepThreads), lds, t->stream, a);
+    });
 }
 
 }  // extern "C"

@@ -6,7 +6,10 @@
 //     count per cluster over that order (eight uint16 counters = two 64-bit words per position) gives, at the lower and upper bound of a pair's score, the hands of
 //     every cluster that score lower or equal; the 46 + 46 pairs that hold one of its cards are taken off, cluster by cluster, in the same packed words.  Flop and turn
 //     add (2 W + T, N) per (hole pair, cluster) into LDS; the last step divides, normalises and scatters the rows through hand_index.
-//   * k_preflop_counts: the flop sweep of k_ehs_round_hist (rs_ehs.hip) up to its LDS histogram, then one atomicAdd per non-zero cell into the 1326 x n_bins table.
+//   * k_preflop_counts: a flop's LDS histogram as k_ehs_round_hist (rs_ehs.hip) builds it, then one atomicAdd per non-zero cell into the 1326 x n_bins table.
+// The stages the sweeps share are one copy each in rs_ehs_dev.hpp: the board's decode, the run-out, the 1081 keys (k_ochs_round supplies `score << 8 | cluster`), the
+// sort, the hole pair's number, and for k_preflop_counts the whole histogram of a board.  k_ochs_round's own: Packed8, the prefix scan, the packed card removal, the
+// accumulators and the last step.
 // Cards, suits and clusters only ever select under predicates (no private array indexed by one): the kernels carry no scratch (profiles/ochs.md).
 #include <cstring>
 #include <string>
@@ -24,9 +27,7 @@ using namespace rs;
 
 namespace rs {
 
-constexpr int kOchsThreads = 1024;    // half the sort width: a thread owns two positions of the order when the prefix counts are built
 constexpr uint32_t kHolePairs = 1326;  // C(52, 2)
-constexpr uint32_t kNoKey = 0xffffffffu;   // padding of the sort: behind every score, in no cluster
 
 // eight uint16 counters, clusters 0-3 in lo and 4-7 in hi.  No counter passes 1081, so sums and differences of such words never carry between counters.
 struct Packed8 {
@@ -37,47 +38,6 @@ __device__ __forceinline__ Packed8 one_of(uint32_t cluster) {   // one hand of `
     return {cluster < 4u ? bit : 0ull, cluster >= 4u && cluster < (uint32_t)RS_OCHS_MAX_CLUSTERS ? bit : 0ull};
 }
 __device__ __forceinline__ uint32_t counter(const Packed8 &v, int k) { return (uint32_t)((k < 4 ? v.lo : v.hi) >> (16 * (k & 3))) & 0xffffu; }
-
-// the 5-card board and its free cards after run-out `ro` of a board of nb cards (nb = 5: the board itself)
-__device__ __forceinline__ void run_out(int nb, uint64_t free0, uint32_t ro, uint32_t (&b5)[4], uint64_t &free5) {
-    free5 = free0;
-    if (nb == 4) {
-        const uint32_t c = nth_bit(free0, ro);
-        add_card(b5, c);
-        free5 &= ~(1ull << c);
-    } else if (nb == 3) {
-        uint32_t i, j;
-        pair_of<49>(ro, i, j);
-        const uint32_t ci = nth_bit(free0, i), cj = nth_bit(free0, j);
-        add_card(b5, ci);
-        add_card(b5, cj);
-        free5 &= ~(1ull << ci | 1ull << cj);
-    }
-}
-
-// ascending bitonic sort of sorted[kEhsSortN] by the whole workgroup; ends on a barrier
-__device__ __forceinline__ void sort_keys(uint32_t *sorted, uint32_t tid) {
-    for (uint32_t k = 2; k <= kEhsSortN; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = tid; t < kEhsSortN / 2; t += kOchsThreads) {
-                const uint32_t lo = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), hi = lo | j;
-                const uint32_t x = sorted[lo], y = sorted[hi];
-                if ((x > y) == ((lo & k) == 0)) {
-                    sorted[lo] = y;
-                    sorted[hi] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// hole pair number hp = hi (hi - 1) / 2 + lo over positions lo < hi
-__device__ __forceinline__ void pair_positions(uint32_t hp, uint32_t &lo, uint32_t &hi) {
-    hi = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)hp)) * 0.5f);
-    while (hi * (hi - 1) / 2 > hp) --hi;
-    while ((hi + 1) * hi / 2 <= hp) ++hi;
-    lo = hp - hi * (hi - 1) / 2;
-}
 
 // ---- the features ---------------------------------------------------------------------------------------------------------------------------------------
 struct OchsSweep {
@@ -92,20 +52,20 @@ struct OchsSweep {
     uint8_t pair_cluster[1328];   // [1326] by c1 (c1 - 1) / 2 + c0
 };
 
-constexpr uint32_t kOchsFixedWords = kEhsSortN + 1088u + 4u * kEhsSortN + 4u * (kOchsThreads / 64) + 1328u / 4u;
+constexpr uint32_t kOchsFixedWords = kEhsSortN + 1088u + 4u * kEhsSortN + 4u * (kSweepThreads / 64) + 1328u / 4u;
 // LDS words of one workgroup: the sort buffer, the keys by pair number, the prefix counts, the waves' totals, the partition, the (2 W + T, N) accumulators
 __host__ __device__ inline uint32_t ochs_lds_words(int nb, int n_clusters) {
     const uint32_t nf = 52u - (uint32_t)nb;
     return kOchsFixedWords + 2u * (uint32_t)n_clusters * (nf * (nf - 1) / 2);
 }
 
-__global__ __launch_bounds__(kOchsThreads, 4) void k_ochs_round(const OchsSweep a) {
+__global__ __launch_bounds__(kSweepThreads, 4) void k_ochs_round(const OchsSweep a) {
     extern __shared__ uint32_t ochs_lds[];
     uint32_t *sorted = ochs_lds;                                                 // [kEhsSortN] score << 8 | cluster, ascending
     uint32_t *sc = sorted + kEhsSortN;                                            // [1088] the key of pair p
     Packed8 *prefix = reinterpret_cast<Packed8 *>(sc + 1088);                     // [kEhsSortN] hands of each cluster in front of a position of the order
     Packed8 *wave_total = prefix + kEhsSortN;                                     // [16]
-    uint8_t *pc = reinterpret_cast<uint8_t *>(wave_total + kOchsThreads / 64);    // [1328]
+    uint8_t *pc = reinterpret_cast<uint8_t *>(wave_total + kSweepThreads / 64);    // [1328]
     uint32_t *acc = reinterpret_cast<uint32_t *>(pc + 1328);                      // [n_clusters][2][n_hp]: 2 W + T, N
     const int nb = a.nb, ncl = a.n_clusters;
     const uint32_t nf = 52u - (uint32_t)nb, n_hp = nf * (nf - 1) / 2;
@@ -114,36 +74,25 @@ __global__ __launch_bounds__(kOchsThreads, 4) void k_ochs_round(const OchsSweep 
 
     uint32_t bc[5], bm[4] = {0, 0, 0, 0};
     uint64_t board;
-    if (!listed_board(a.boards, a.pitch, nb, blockIdx.x, bc, board, bm)) {   // uniform over the workgroup: reported, nothing written
+    __builtin_assume(a.boards != nullptr);   // the host always lists the boards (class_boards): the numbered decode drops out of this kernel
+    if (!sweep_board(a.boards, a.pitch, nb, bc, board, bm)) {   // uniform over the workgroup: reported, nothing written
         if (tid == 0) atomicOr(a.err, 1u);
         return;
     }
     const uint64_t free0 = kDeck & ~board;   // nf cards
 
-    for (uint32_t i = tid; i < 1328u; i += kOchsThreads) pc[i] = a.pair_cluster[i];
-    for (uint32_t i = tid; i < 2u * (uint32_t)ncl * n_hp; i += kOchsThreads) acc[i] = 0;
+    for (uint32_t i = tid; i < 1328u; i += kSweepThreads) pc[i] = a.pair_cluster[i];
+    for (uint32_t i = tid; i < 2u * (uint32_t)ncl * n_hp; i += kSweepThreads) acc[i] = 0;
     __syncthreads();
 
     for (uint32_t ro = 0; ro < n_ro; ++ro) {
         uint32_t b5[4] = {bm[0], bm[1], bm[2], bm[3]};
         uint64_t free5;   // 47 cards
         run_out(nb, free0, ro, b5, free5);
-        for (uint32_t p = tid; p < kEhsSortN; p += kOchsThreads) {
-            uint32_t key = kNoKey;
-            if (p < kEhsPairs) {
-                uint32_t i, j;
-                pair_of<47>(p, i, j);
-                const uint32_t ci = nth_bit(free5, i), cj = nth_bit(free5, j);
-                uint32_t m[4] = {b5[0], b5[1], b5[2], b5[3]};
-                add_card(m, ci);
-                add_card(m, cj);
-                const uint32_t hi = ci > cj ? ci : cj, lo = ci > cj ? cj : ci;
-                key = evaluate_suits(m) << 8 | pc[hi * (hi - 1) / 2 + lo];   // a score has 24 bits
-                sc[p] = key;
-            }
-            sorted[p] = key;
-        }
-        __syncthreads();
+        fill_keys(b5, free5, sc, sorted, tid, [pc](uint32_t score, uint32_t ci, uint32_t cj) {
+            const uint32_t hi = ci > cj ? ci : cj, lo = ci > cj ? cj : ci;
+            return score << 8 | pc[hi * (hi - 1) / 2 + lo];   // a score has 24 bits
+        });
         sort_keys(sorted, tid);
 
         // exclusive prefix counts: a thread sums its two positions, the wave scans, the waves' totals carry over
@@ -171,7 +120,7 @@ __global__ __launch_bounds__(kOchsThreads, 4) void k_ochs_round(const OchsSweep 
         }
         __syncthreads();
 
-        for (uint32_t p = tid; p < kEhsPairs; p += kOchsThreads) {
+        for (uint32_t p = tid; p < kEhsPairs; p += kSweepThreads) {
             uint32_t i, j;
             pair_of<47>(p, i, j);
             const uint32_t key = sc[p], s = key >> 8;
@@ -205,11 +154,7 @@ __global__ __launch_bounds__(kOchsThreads, 4) void k_ochs_round(const OchsSweep 
             const Packed8 t = {at_ub.lo - at_lb.lo + self.lo - equal.lo, at_ub.hi - at_lb.hi + self.hi - equal.hi};
             const Packed8 n = {total.lo + self.lo - held.lo, total.hi + self.hi - held.hi};
             const Packed8 k2 = {2ull * w.lo + t.lo, 2ull * w.hi + t.hi};   // at most 2 * 990 per counter
-            // the hole pair's number among the pairs of the board's free cards; one thread per hole pair and run-out, so plain adds
-            const uint32_t ci = nth_bit(free5, i), cj = nth_bit(free5, j);
-            const uint32_t pi = (uint32_t)__popcll(free0 & ((1ull << ci) - 1)), pj = (uint32_t)__popcll(free0 & ((1ull << cj) - 1));
-            const uint32_t hi = pi > pj ? pi : pj, lo = pi > pj ? pj : pi;
-            uint32_t *cell = acc + hi * (hi - 1) / 2 + lo;
+            uint32_t *cell = acc + hole_pair_number(free0, free5, i, j);   // one thread per hole pair and run-out, so plain adds
 #pragma unroll
             for (int k = 0; k < RS_OCHS_MAX_CLUSTERS; ++k)
                 if (k < ncl) {
@@ -222,7 +167,7 @@ __global__ __launch_bounds__(kOchsThreads, 4) void k_ochs_round(const OchsSweep 
 
     // divide, normalise and scatter through the indexer; the card bytes of a hand stand in LDS (the sort buffer is free now) so that hand_index reads no private array
     uint8_t *hand = reinterpret_cast<uint8_t *>(sorted) + tid * 8u;
-    for (uint32_t hp = tid; hp < n_hp; hp += kOchsThreads) {
+    for (uint32_t hp = tid; hp < n_hp; hp += kSweepThreads) {
         uint32_t lo, hi;
         pair_positions(hp, lo, hi);
         hand[0] = (uint8_t)nth_bit(free0, lo);
@@ -257,108 +202,33 @@ struct PreflopSweep {
     uint32_t *err;
 };
 
-// as ehs_sweep_lds_words(3, n_bins) of rs_ehs.hip
-__host__ __device__ inline uint32_t preflop_lds_words(int n_bins) { return kEhsSortN + 1088u + (uint32_t)RS_EHS_MAX_BINS + (1176u * (uint32_t)n_bins + 1u) / 2u; }
-
-__global__ __launch_bounds__(kOchsThreads, 8) void k_preflop_counts(const PreflopSweep a) {
+__global__ __launch_bounds__(kSweepThreads, 8) void k_preflop_counts(const PreflopSweep a) {
     extern __shared__ uint32_t ochs_lds[];
-    uint32_t *sorted = ochs_lds;                                   // [kEhsSortN]
-    uint32_t *sc = sorted + kEhsSortN;                             // [1088] score of pair p
-    float *thr = reinterpret_cast<float *>(sc + 1088);             // [RS_EHS_MAX_BINS]
-    uint32_t *hist = reinterpret_cast<uint32_t *>(thr + RS_EHS_MAX_BINS);   // [1176][n_bins] uint16, two to a word
+    const HistLds l = carve_hist_lds(ochs_lds);
     const int n_bins = a.bins.n_bins;
-    constexpr uint32_t n_hp = 1176u, n_ro = 1176u;
     const uint32_t tid = threadIdx.x;
 
-    uint32_t bc[5] = {0, 0, 0, 0, 0}, bm[4] = {0, 0, 0, 0};
-    uint64_t board = 0;
-    if (a.boards) {
-        if (!listed_board(a.boards, a.pitch, 3, blockIdx.x, bc, board, bm)) {
-            if (tid == 0) atomicOr(a.err, 1u);
-            return;
-        }
-    } else {
-        uint32_t idx = blockIdx.x;
-        bc[2] = colex_digit(idx, 3);
-        bc[1] = colex_digit(idx, 2);
-        bc[0] = idx;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            board |= 1ull << bc[i];
-            add_card(bm, bc[i]);
-        }
+    uint32_t bc[5], bm[4] = {0, 0, 0, 0};
+    uint64_t board;
+    if (!sweep_board(a.boards, a.pitch, 3, bc, board, bm)) {
+        if (tid == 0) atomicOr(a.err, 1u);
+        return;
     }
     const uint64_t free0 = kDeck & ~board;   // 49 cards
-
-    for (uint32_t i = tid; i < (uint32_t)RS_EHS_MAX_BINS; i += kOchsThreads) thr[i] = a.bins.thr[i];
-    for (uint32_t i = tid; i < (n_hp * (uint32_t)n_bins + 1u) / 2u; i += kOchsThreads) hist[i] = 0;
-    __syncthreads();
-
-    for (uint32_t ro = 0; ro < n_ro; ++ro) {
-        uint32_t b5[4] = {bm[0], bm[1], bm[2], bm[3]};
-        uint64_t free5;
-        run_out(3, free0, ro, b5, free5);
-        for (uint32_t p = tid; p < kEhsSortN; p += kOchsThreads) {
-            uint32_t s = kNoKey;
-            if (p < kEhsPairs) {
-                uint32_t i, j;
-                pair_of<47>(p, i, j);
-                uint32_t m[4] = {b5[0], b5[1], b5[2], b5[3]};
-                add_card(m, nth_bit(free5, i));
-                add_card(m, nth_bit(free5, j));
-                s = evaluate_suits(m);
-                sc[p] = s;
-            }
-            sorted[p] = s;
-        }
-        __syncthreads();
-        sort_keys(sorted, tid);
-        for (uint32_t p = tid; p < kEhsPairs; p += kOchsThreads) {
-            uint32_t i, j;
-            pair_of<47>(p, i, j);
-            const uint32_t s = sc[p];
-            uint32_t lb = 0, ub = 0;
-#pragma unroll
-            for (uint32_t step = kEhsSortN / 2; step; step >>= 1) {
-                if (sorted[lb + step - 1] < s) lb += step;
-                if (sorted[ub + step - 1] <= s) ub += step;
-            }
-            uint32_t below = 0, equal = 0;
-            for (uint32_t d = 1; d <= 23; ++d) {
-                const uint32_t q0 = sc[i * 23 + d - 1], q1 = sc[((i + 47 - d) % 47) * 23 + d - 1];
-                const uint32_t q2 = sc[j * 23 + d - 1], q3 = sc[((j + 47 - d) % 47) * 23 + d - 1];
-                below += (q0 < s) + (q1 < s) + (q2 < s) + (q3 < s);
-                equal += (q0 == s) + (q1 == s) + (q2 == s) + (q3 == s);
-            }
-            const uint32_t w = lb - below, t = (ub - lb) - equal + 1u;   // over the 990 hands that share no card with it
-            const float v = (float)((double)(2u * w + t) / (double)(2u * kEhsOpp));
-            const uint32_t bin = ehs_bin_of(thr, n_bins, v);
-            const uint32_t ci = nth_bit(free5, i), cj = nth_bit(free5, j);
-            const uint32_t pi = (uint32_t)__popcll(free0 & ((1ull << ci) - 1)), pj = (uint32_t)__popcll(free0 & ((1ull << cj) - 1));
-            const uint32_t hi = pi > pj ? pi : pj, lo = pi > pj ? pj : pi;
-            const uint32_t cell = (hi * (hi - 1) / 2 + lo) * (uint32_t)n_bins + bin;
-            atomicAdd(&hist[cell >> 1], 1u << (16u * (cell & 1u)));   // a counter never passes 1081: no carry into its neighbour
-        }
-        __syncthreads();
-    }
+    board_histogram(3, a.bins, free0, bm, l, tid);
 
     // the board's non-zero cells into the table, by the pair's card numbers; integer adds, so their order is free
-    for (uint32_t hp = tid; hp < n_hp; hp += kOchsThreads) {
+    for (uint32_t hp = tid; hp < 1176u; hp += kSweepThreads) {
         uint32_t lo, hi;
         pair_positions(hp, lo, hi);
         const uint32_t c0 = nth_bit(free0, lo), c1 = nth_bit(free0, hi);   // c0 < c1
         uint32_t *dst = a.counts + (size_t)(c1 * (c1 - 1) / 2 + c0) * (uint32_t)n_bins;
         for (int k = 0; k < n_bins; ++k) {
-            const uint32_t cell = hp * (uint32_t)n_bins + (uint32_t)k;
-            const uint32_t count = (hist[cell >> 1] >> (16u * (cell & 1u))) & 0xffffu;
+            const uint32_t count = hist_count(l.hist, hp * (uint32_t)n_bins + (uint32_t)k);
             if (count) atomicAdd(&dst[k], count);
         }
     }
 }
-
-}  // namespace rs
-
-namespace {
 
 // dynamic LDS beyond what a launch gets unasked
 int grant_lds(const void *kernel, size_t lds, const char *who) {
@@ -368,6 +238,10 @@ int grant_lds(const void *kernel, size_t lds, const char *who) {
     (void)hipGetLastError();
     return fail(RS_ERR_UNSUPPORTED, std::string(who) + ": the device grants no workgroup " + std::to_string(lds) + " bytes of LDS (" + hipGetErrorString(e) + ")");
 }
+
+}  // namespace rs
+
+namespace {
 
 // one representative board per suit-isomorphism class of the nb-card boards, as SoA rows [nb][pitch]
 int class_boards(int nb, std::vector<uint8_t> *rows, uint32_t *n, uint32_t *pitch) {
@@ -434,13 +308,10 @@ int rs_ochs_round_features(rs_table *t, rs_hand_indexer *ix, const uint8_t *pair
     a.n_clusters = n_clusters;
     a.normalize = normalize;
     a.out = d_out;
-    DevBuf<uint32_t> d_err;
-    RS_HIP(d_err.alloc(1), "rs_ochs_round_features: error word");
-    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ochs_round_features");
-    a.err = d_err;
-    hipLaunchKernelGGL(k_ochs_round, dim3(n_boards), dim3(kOchsThreads), lds, t->stream, a);
-    RS_HIP(hipGetLastError(), "k_ochs_round");
-    return ehs_read_err(t, d_err, "rs_ochs_round_features", "a board");
+    return launch_checked(t, "rs_ochs_round_features", "k_ochs_round", "a board", [&](uint32_t *d_err) {
+        a.err = d_err;
+        hipLaunchKernelGGL(k_ochs_round, dim3(n_boards), dim3(kSweepThreads), lds, t->stream, a);
+    });
 }
 
 int rs_ehs_preflop_counts(rs_table *t, int n_bins, const uint8_t *d_boards, uint32_t n_boards, uint32_t *d_counts) {
@@ -462,15 +333,12 @@ int rs_ehs_preflop_counts(rs_table *t, int n_bins, const uint8_t *d_boards, uint
     a.boards = d_boards;
     a.pitch = uint32_t(round_up(n_boards, kLanePad));
     a.counts = d_counts;
-    const size_t lds = size_t(preflop_lds_words(n_bins)) * sizeof(uint32_t);
+    const size_t lds = size_t(ehs_sweep_lds_words(3, n_bins)) * sizeof(uint32_t);
     if (int rc = grant_lds(reinterpret_cast<const void *>(k_preflop_counts), lds, "rs_ehs_preflop_counts")) return rc;
-    DevBuf<uint32_t> d_err;
-    RS_HIP(d_err.alloc(1), "rs_ehs_preflop_counts: error word");
-    RS_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t), t->stream), "rs_ehs_preflop_counts");
-    a.err = d_err;
-    hipLaunchKernelGGL(k_preflop_counts, dim3(n_boards), dim3(kOchsThreads), lds, t->stream, a);
-    RS_HIP(hipGetLastError(), "k_preflop_counts");
-    return ehs_read_err(t, d_err, "rs_ehs_preflop_counts", "a board");
+    return launch_checked(t, "rs_ehs_preflop_counts", "k_preflop_counts", "a board", [&](uint32_t *d_err) {
+        a.err = d_err;
+        hipLaunchKernelGGL(k_preflop_counts, dim3(n_boards), dim3(kSweepThreads), lds, t->stream, a);
+    });
 }
 
 }  // extern "C"

@@ -287,6 +287,28 @@ def test_preflop_counts_of_listed_flops_equal_the_restatement(table):
     assert differ == 0
 
 
+@pytest.mark.parametrize("n_bins", [1, 64])
+def test_preflop_counts_of_listed_flops_equal_the_device_histograms_of_those_flops(table, indexers, n_bins):
+    """test_the_preflop_counts_of_two_listed_flops (test_ochs_cpu.py) on the device: the two kernels that share one histogram body, each through its own last step.
+    The rows of rs_ehs_round_histograms for the two flops (pinned at these bin counts by test_gpu_ehs_rounds.py), as counts, placed by each hand's hole cards and
+    summed over the flops, are the preflop counts cell for cell.  64 bins is the 163 328-byte launch; 1 bin leaves the last uint16 cell of the histogram unpaired"""
+    t0 = time.perf_counter()
+    flops = [FLOP_PAIRED, FLOP_LAST]
+    got = ab.preflop_counts(table, n_bins, boards=flops)
+    hist = ab.round_histograms(table, indexers[3], n_bins, boards=flops)
+    want = np.zeros((1326, n_bins), dtype=np.int64)
+    for flop in flops:
+        hands = hands_of(flop).astype(np.int64)
+        k = ne.counts_of_words(rows_of(hist, indexers[3].get_index(hands.astype(np.uint8)).astype(np.int64)), 1081).astype(np.int64)
+        assert k.shape == (1176, n_bins) and k.min() >= 0 and (k.sum(axis=1) == 1081).all()
+        want[no.pair_index(hands[:, 0], hands[:, 1])] += k      # the 1176 hole pairs of a flop are 1176 different rows
+    hist.buffer.free()
+    assert got.dtype == np.uint32 and got.shape == want.shape and int(want.sum()) == 2 * 1176 * 1081
+    differ = int((got.astype(np.int64) != want).sum())
+    report("preflop against the device's flop histograms, %d bins" % n_bins, flops=2, cells=want.size, differ=differ, wall_s=time.perf_counter() - t0)
+    assert differ == 0
+
+
 @pytest.fixture(scope="module")
 def all_flops_35(table):
     t0 = time.perf_counter()
