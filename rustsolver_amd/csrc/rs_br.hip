@@ -650,7 +650,7 @@ __device__ __forceinline__ void br_terminal_sorted_body(const uint8_t *__restric
     }
 }
 
-// one JOB per node of the level plan (all nodes of one tree depth and kind in one launch)
+// one JOB per node and launch it takes part in: a grid row of the kind's kernel (the level plan: all nodes of one tree depth and kind in one launch; depth first: one row)
 struct BrJob {
     BrNodeRow row;                 // action nodes: the node's strategy_sum block
     const uint32_t *cid;           // opponent node: the opponent's lane -> cluster of the node's round
@@ -1080,7 +1080,7 @@ struct BrRealChild {
     uint32_t ns;
 };
 __device__ __forceinline__ BrRealChild br_real_child(const double *__restrict__ vch, const BrJob *__restrict__ jp, uint32_t a, uint32_t n_pad) {
-    if (jp && jp->sum_n[a]) return {jp->sum_src[a], jp->sum_n[a]};   // (read where they lie: indexed by the action)
+    if (jp->sum_n[a]) return {jp->sum_src[a], jp->sum_n[a]};   // (read where they lie: indexed by the action)
     return {vch + (size_t)a * n_pad, 0u};
 }
 template <int N>
@@ -1178,18 +1178,10 @@ __device__ __forceinline__ void br_own_real_cols_body(const uint64_t *__restrict
             if (k + q < pp) v[lane[q]] = deal[q] ? t[q] : 0.0;
     }
 }
-__global__ __launch_bounds__(kBrBlock) void k_br_own_real_last(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
-                                                               uint32_t n_actions, const double *__restrict__ vch, double *__restrict__ v) {
-    br_own_real_last_body(mask_p, bmask, n_hands, n, n_pad, n_actions, vch, nullptr, v);
-}
 __global__ __launch_bounds__(kBrBlock) void k_br_own_real_last_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
                                                                     uint32_t n_pad, const BrJob *__restrict__ jobs) {
     const BrJob *__restrict__ jp = jobs + blockIdx.y;
     br_own_real_last_body(mask_p, bmask, n_hands, n, n_pad, jp->n_children, jp->vch, jp, jp->v);
-}
-__global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
-                                                               uint32_t pp, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, double *__restrict__ v) {
-    br_own_real_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, n_actions, vch, nullptr, v);
 }
 __global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
                                                                     uint32_t pp, uint32_t n_pad, const BrJob *__restrict__ jobs) {
@@ -1197,25 +1189,10 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_real_cols_jobs(const uint64
     br_own_real_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, jp->n_children, jp->vch, jp, jp->v);
 }
 
-// ---- the kernels: one node per launch, its pointers as kernel arguments (the depth-first walk), or one JOB per node and grid row (the level plan: all nodes of one tree
-// depth and kind in one launch).  Both forward to the same bodies; BrRun::launch picks. -----------------------------------------------------------------------------------
+// ---- the kernels: one JOB per node and grid row, a wrapper that hands the job's fields to the kind's body.  The level plan launches all nodes of one tree depth and kind
+// at once, the depth-first walk one row of the same table (k_br_own_wave apart): BrRun::launch is the one launch path. -----------------------------------------------------
 // opponent node: q_a[h] = q[h] * sigma_bar(cluster(h), a) for every action (cfr.rs:585's reach product, over the whole range at once)
-template <int DT>
-__device__ __forceinline__ void br_opp_reach_body(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n,
-                                                           uint32_t n_pad, const double *__restrict__ q, double *__restrict__ q_out /*[A][n_pad]*/) {
-    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
-    if (h >= n) return;
-    float sig[RS_MAX_ACTIONS];
-    final_sigma<DT>(ssum, row.cell_off, row.pitch, row.n_actions, cid[h], sig);
-    const double qh = q[h];
-    for (uint32_t a = 0; a < row.n_actions; a++) q_out[(size_t)a * n_pad + h] = qh * (double)sig[a];
-}
-template <int DT>
-__global__ __launch_bounds__(kBrBlock) void k_br_opp_reach(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
-                                                           const double *__restrict__ q, double *__restrict__ q_out) {
-    br_opp_reach_body<DT>(ssum, row, cid, n, n_pad, q, q_out);
-}
-// (level plan) The strategy-sum rows are gathered by cluster id, and a lossless abstraction numbers its clusters hand by hand: workgroups go round the eight XCDs in turn, so
+// The strategy-sum rows are gathered by cluster id, and a lossless abstraction numbers its clusters hand by hand: workgroups go round the eight XCDs in turn, so
 // workgroup x takes hands of slice x % 8 only (every run-out of them) -- an XCD's L2 then sees an eighth (with the suit-swapped twins: a quarter) of the node's rows instead of
 // all of them (the river's 7.7 MB per node against 4 MB of L2: 250 MB fetched per node, profiles/r05_br.md).  gridDim.x = 8 * ceil(run-outs * ceil(n_hands / 8) / kBrBlock).
 // The thread's lane h of the n = run-outs * n_hands; false: it has none (the slice is empty -- fewer than eight hands -- or the thread is past its end).
@@ -1236,23 +1213,17 @@ __global__ __launch_bounds__(kBrBlock) void k_br_opp_reach_jobs(const void *__re
     const double qh = j.q[h];
     for (uint32_t a = 0; a < j.row.n_actions; a++) j.q_out[(size_t)a * n_pad + h] = qh * (double)sig[a];
 }
-__global__ __launch_bounds__(kBrBlock) void k_br_sum(const double *__restrict__ vch, uint32_t n_actions, uint32_t n, uint32_t n_pad, double *__restrict__ v) {
-    br_sum_body(vch, n_actions, n, n_pad, v);
-}
 __global__ __launch_bounds__(kBrBlock) void k_br_sum_jobs(const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad) {
     const BrJob j = jobs[blockIdx.y];
     br_sum_body(j.vch, j.n_children, n, n_pad, j.v);
-}
-template <int DT>
-__global__ __launch_bounds__(kBrBlock) void k_br_own(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start, const uint32_t *__restrict__ order,
-                                                     uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch, int mode, double *__restrict__ v) {
-    br_own_body<DT>(ssum, row, start, order, n_clusters, n_pad, vch, mode, v);
 }
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_own_jobs(const void *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n_pad, int mode) {
     const BrJob j = jobs[blockIdx.y];
     br_own_body<DT>(ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, mode, j.v);
 }
+// The one kind with a one-node entry beside its job entry, the node's fields as kernel arguments: the depth-first walk launches it, because the i32 instantiation ran 8 %
+// longer per launch from a job row there (100.3 against 92.5 us at 200 combos a side, profiles/br_launcher.md)
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_own_wave(const void *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start, const uint32_t *__restrict__ order,
                                                           uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch, int mode, double *__restrict__ v) {
@@ -1263,32 +1234,12 @@ __global__ __launch_bounds__(kBrBlock) void k_br_own_wave_jobs(const void *__res
     const BrJob j = jobs[blockIdx.y];
     br_own_wave_body<DT>(ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, mode, j.v);
 }
-// a one-node entry's payoffs as a kernel argument: one scalar without rake (the argument block the entry has always had), three with it
-template <bool RAKED> struct BrPay { double value; };
-template <> struct BrPay<true> { double value, vt, vl; };
-template <bool RAKED> __device__ __forceinline__ double br_pay_tie(const BrPay<RAKED> &) { return 0.0; }
-template <> __device__ __forceinline__ double br_pay_tie<true>(const BrPay<true> &p) { return p.vt; }
-template <bool RAKED> __device__ __forceinline__ double br_pay_lose(const BrPay<RAKED> &) { return 0.0; }
-template <> __device__ __forceinline__ double br_pay_lose<true>(const BrPay<true> &p) { return p.vl; }
-template <bool RAKED>
-__global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
-                                                                 uint32_t n_p, const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
-                                                                 int uncontested, BrPay<RAKED> pay, double *__restrict__ v) {
-    br_terminal_sorted_body<RAKED>(hands_p, mask_p, pw, n_p, q, n_o, bmask, ix, uncontested, pay.value, br_pay_tie(pay), br_pay_lose(pay), v);
-}
 template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_sorted_jobs(const uint8_t *__restrict__ hands_p, const uint64_t *__restrict__ mask_p, const double *__restrict__ pw,
                                                                       uint32_t n_p, uint32_t n_o, const uint64_t *__restrict__ bmask, BrIndex ix,
                                                                       const BrJob *__restrict__ jobs) {
     const BrJob j = jobs[blockIdx.y];
     br_terminal_sorted_body<RAKED>(hands_p, mask_p, pw, n_p, j.q, n_o, bmask, ix, j.uncontested, j.value, RAKED ? j.value_tie : 0.0, RAKED ? j.value_lose : 0.0, j.v);
-}
-template <bool RAKED>
-__global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
-                                                                 uint32_t n_p, const uint64_t *__restrict__ mask_o, const uint32_t *__restrict__ score_o,
-                                                                 const double *__restrict__ q, uint32_t n_o, const uint64_t *__restrict__ bmask, int uncontested,
-                                                                 BrPay<RAKED> pay, double *__restrict__ v) {
-    br_terminal_boards_body<RAKED>(mask_p, score_p, pw, n_p, mask_o, score_o, q, n_o, bmask, uncontested, pay.value, br_pay_tie(pay), br_pay_lose(pay), v);
 }
 template <bool RAKED>
 __global__ __launch_bounds__(kBrBlock) void k_br_terminal_boards_jobs(const uint64_t *__restrict__ mask_p, const uint32_t *__restrict__ score_p, const double *__restrict__ pw,
@@ -1321,13 +1272,7 @@ __device__ __forceinline__ void br_own_reach_lane(const void *__restrict__ regre
     for (int a = 0; a < RS_MAX_ACTIONS; a++)
         if ((uint32_t)a < row.n_actions) pi_out[(size_t)a * n_pad + h] = ph * (double)sig[a];
 }
-template <int DT>
-__global__ __launch_bounds__(kBrBlock) void k_br_own_reach(const void *__restrict__ regrets, BrNodeRow row, const uint32_t *__restrict__ cid, uint32_t n, uint32_t n_pad,
-                                                           const double *__restrict__ pi, double *__restrict__ pi_out) {
-    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
-    if (h < n) br_own_reach_lane<DT>(regrets, row, cid, h, n_pad, pi, pi_out);
-}
-// (level plan) sliced over the XCDs by hand as k_br_opp_reach_jobs: the regret rows are gathered by cluster id just as the strategy sums are there
+// sliced over the XCDs by hand as k_br_opp_reach_jobs: the regret rows are gathered by cluster id just as the strategy sums are there
 template <int DT>
 __global__ __launch_bounds__(kBrBlock) void k_br_own_reach_jobs(const void *__restrict__ regrets, const BrJob *__restrict__ jobs, uint32_t n, uint32_t n_pad, uint32_t n_hands) {
     const BrJob j = jobs[blockIdx.y];
@@ -1438,19 +1383,9 @@ __device__ __forceinline__ void br_cfr_own_wave_body(float *__restrict__ regrets
         if (lane == 0) br_cfr_store(regrets, ssum, row, c, r, sig, s, P, rmplus);
     }
 }
-__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start,
-                                                         const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
-                                                         const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
-    br_cfr_own_body(regrets, ssum, row, start, order, n_clusters, n_pad, vch, pi, rmplus, v);
-}
 __global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_jobs(float *__restrict__ regrets, float *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n_pad, int rmplus) {
     const BrJob j = jobs[blockIdx.y];
     br_cfr_own_body(regrets, ssum, j.row, j.start, j.order, j.n_clusters, n_pad, j.vch, j.q, rmplus, j.v);
-}
-__global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave(float *__restrict__ regrets, float *__restrict__ ssum, BrNodeRow row, const uint32_t *__restrict__ start,
-                                                              const uint32_t *__restrict__ order, uint32_t n_clusters, uint32_t n_pad, const double *__restrict__ vch,
-                                                              const double *__restrict__ pi, int rmplus, double *__restrict__ v) {
-    br_cfr_own_wave_body(regrets, ssum, row, start, order, n_clusters, n_pad, vch, pi, rmplus, v);
 }
 __global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave_jobs(float *__restrict__ regrets, float *__restrict__ ssum, const BrJob *__restrict__ jobs, uint32_t n_pad,
                                                                    int rmplus) {
@@ -1459,7 +1394,7 @@ __global__ __launch_bounds__(kBrBlock) void k_br_cfr_own_wave_jobs(float *__rest
 }
 
 // ---- the node report (rs_node_report): per (prefix of the node's round, hand) what RS_BR_AVERAGE's walk holds at a requested node ------------------------------------
-// k_br_own_real_cols / _last's fold with the sums kept instead of compared: A + 2 lane rows -- the children's values vch[a], the node's own value row, the mass row (an
+// k_br_own_real_cols_jobs / _last_jobs' fold with the sums kept instead of compared: A + 2 lane rows -- the children's values vch[a], the node's own value row, the mass row (an
 // uncontested leaf of value 1.0 on the node's q: the kBrMass job before this one) -- are added up over the run-outs of the pair's prefix, ascending from 0.0, lanes that are
 // no deal not added; the last row is the traverser's own reach pi on the pair's first deal.  out: [A + 3][n_pairs], rows cfv[0 .. A), v, mass, own.
 // Under RS_BR_AVERAGE no own node folds its opponent children (BrPlan's `folds`), so every child row and the node's own row stand written when the report runs: plain rows.
@@ -1525,20 +1460,10 @@ __device__ __forceinline__ void br_report_last_body(const uint64_t *__restrict__
         if ((uint32_t)row < n_actions + 2) out[(size_t)row * n + lane] = deal ? 0.0 + t[row] : 0.0;
     out[(size_t)(n_actions + 2) * n + lane] = deal ? own : 0.0;
 }
-__global__ __launch_bounds__(kBrBlock) void k_br_report_cols(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
-                                                             uint32_t pp, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v,
-                                                             const double *__restrict__ mass, const double *__restrict__ pi, double *__restrict__ out) {
-    br_report_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, n_actions, vch, v, mass, pi, out);
-}
 __global__ __launch_bounds__(kBrBlock) void k_br_report_cols_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n_pairs,
                                                                   uint32_t pp, uint32_t n_pad, const BrJob *__restrict__ jobs) {
     const BrJob *__restrict__ jp = jobs + blockIdx.y;
     br_report_cols_body(mask_p, bmask, n_hands, n_pairs, pp, n_pad, jp->n_children, jp->vch, jp->v, jp->sum_src[0], jp->q, jp->q_out);
-}
-__global__ __launch_bounds__(kBrBlock) void k_br_report_last(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n, uint32_t n_pad,
-                                                             uint32_t n_actions, const double *__restrict__ vch, const double *__restrict__ v, const double *__restrict__ mass,
-                                                             const double *__restrict__ pi, double *__restrict__ out) {
-    br_report_last_body(mask_p, bmask, n_hands, n, n_pad, n_actions, vch, v, mass, pi, out);
 }
 __global__ __launch_bounds__(kBrBlock) void k_br_report_last_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
                                                                   uint32_t n_pad, const BrJob *__restrict__ jobs) {
@@ -1573,8 +1498,8 @@ __global__ __launch_bounds__(kBrBlock) void k_br_gadget_reach(const float *__res
 }
 // the opponent's sweep, behind the root's value job: one THREAD per hand folds the root row vF (FOLLOW) and alt * mass (TERMINATE) over the run-outs, ascending from 0.0,
 // lanes that are no deal not added (br_report_cols_body's test), kBrRealFlight loads of each row in flight; sigma is known before the fold, so the lanes get their v while
-// their values are in registers; then the hand's four cells.  The last round (NB = 1) is the same lane text once: element-wise, as k_br_report_last is.
-// (A thread per hand rather than k_br_report_cols' workgroup of 64 hands with waves sharing rows: there are two rows, not A + 2, their sums meet in U, and the kernel runs
+// their values are in registers; then the hand's four cells.  The last round (NB = 1) is the same lane text once: element-wise, as k_br_report_last_jobs is.
+// (A thread per hand rather than k_br_report_cols_jobs' workgroup of 64 hands with waves sharing rows: there are two rows, not A + 2, their sums meet in U, and the kernel runs
 // once per sweep over at most 1 326 hands -- neighbouring threads read neighbouring hands of a run-out either way.)
 __global__ __launch_bounds__(kBrBlock) void k_br_gadget_own(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t NB,
                                                             float *__restrict__ regret, float *__restrict__ ssum, const double *__restrict__ alt,
@@ -1648,7 +1573,7 @@ __global__ __launch_bounds__(kBrBlock) void k_br_gadget_discount(float *__restri
 // no XCD slicing.  An early-round node's lock (A * n_prefix * n_hands doubles) stays in cache; a last-round node's rows are as long as a lane row.  Everything indexed
 // by the action is unrolled to RS_MAX_ACTIONS under the action count as a predicate (current_sigma's reason: indexed by a run-time count it becomes scratch).
 // reach, either side: out[a][lane] = in[lane] * lock[a][f][h].  The opponent's q at its locked node and the traverser's own pi at its own (full-width sweep, node report).
-// A lane that is no deal takes whatever the lock holds there, as k_br_opp_reach takes cluster 0's strategy: its reach is never looked at.
+// A lane that is no deal takes whatever the lock holds there, as k_br_opp_reach_jobs takes cluster 0's strategy: its reach is never looked at.
 __device__ __forceinline__ void br_lock_reach_body(const double *__restrict__ lock, uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions,
                                                    const double *__restrict__ in, double *__restrict__ out /*[A][n_pad]*/) {
     const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
@@ -1690,18 +1615,9 @@ __device__ __forceinline__ void br_lock_value_body(const uint64_t *__restrict__ 
 }
 // a lock job (kBrLockReach, kBrLockValue): sum_src[0] = the lock's rows on the device, n_clusters = pp, n_children = A; a reach job carries its side's shape with it (one
 // launch takes the opponent's q jobs and the traverser's pi jobs of a depth): n_sets = n_hands, kmax = the side's lanes, row.pitch = its n_pad
-__global__ __launch_bounds__(kBrBlock) void k_br_lock_reach(const double *__restrict__ lock, uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions,
-                                                            const double *__restrict__ in, double *__restrict__ out) {
-    br_lock_reach_body(lock, pp, n_hands, n, n_pad, n_actions, in, out);
-}
 __global__ __launch_bounds__(kBrBlock) void k_br_lock_reach_jobs(const BrJob *__restrict__ jobs) {
     const BrJob *__restrict__ jp = jobs + blockIdx.y;
     br_lock_reach_body(jp->sum_src[0], jp->n_clusters, jp->n_sets, jp->kmax, jp->row.pitch, jp->n_children, jp->q, jp->q_out);
-}
-__global__ __launch_bounds__(kBrBlock) void k_br_lock_value(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, const double *__restrict__ lock,
-                                                            uint32_t pp, uint32_t n_hands, uint32_t n, uint32_t n_pad, uint32_t n_actions, const double *__restrict__ vch,
-                                                            double *__restrict__ v) {
-    br_lock_value_body(mask_p, bmask, lock, pp, n_hands, n, n_pad, n_actions, vch, v);
 }
 __global__ __launch_bounds__(kBrBlock) void k_br_lock_value_jobs(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t n,
                                                                  uint32_t n_pad, const BrJob *__restrict__ jobs) {
@@ -1796,9 +1712,12 @@ struct BrRun {
     int last_launches = 0;
     DevBuf<double> ws;                        // the walk's workspace, allocated by the first br_execute and kept (a 60 GB allocation takes seconds): level plan or depth-first
     bool ws_levels = false;
+    DevBuf<BrJob> job_table;                  // a traverser's jobs on the device: kept with the workspace and grown when a plan holds more (an allocation per pass costs a
+                                              // launch-bound sweep a fifth of its time, profiles/br_launcher.md); like the per-pass table it replaces, not in the ledger
     void release_workspace() {
         if (ws) (void)hipStreamSynchronize(t->stream);
         ws.reset();
+        job_table.reset();
         q_level.clear();
         v_level.clear();
         pi_level.clear();
@@ -2077,9 +1996,8 @@ struct BrRun {
     }
 
     // The launcher: for every kind the ONE place that knows its grid, block and LDS size, its attributes, the instantiation for the cell type and the leaf form.  d_jobs[0 .. nj)
-    // are the launch's jobs (one grid row each), h the same jobs on the host; r is the round of a kind that is launched per round.  The depth-first walk passes no d_jobs and
-    // one job: the node goes to the kind's one-node entry, its pointers as kernel arguments (what the walk has always done; the _jobs kernels with a one-row grid would
-    // compute the same bits, but whether they are as fast has not been measured: profiles/br_launcher.md).
+    // are the launch's jobs (one grid row each), h the same jobs on the host; r is the round of a kind that is launched per round.  The level plan passes a run of equal key,
+    // the depth-first walk one row of the same table: the same kernels with a one-row grid (timed against one-node entries in profiles/br_launcher.md; kBrOwnWave kept its own).
     int n_launches = 0;
     void launch(BrKind kind, int r, const BrJob *d_jobs, uint32_t nj, const BrJob *h) {
         if (err != hipSuccess) return;
@@ -2094,7 +2012,6 @@ struct BrRun {
             return m;
         };
         auto n_clusters = [](const BrJob &j) { return j.n_clusters; };
-        const BrJob &j = h[0];   // the node of a one-node launch
         switch (kind) {
         case kBrReachGrouped: {
             const BrGroups &g = op.groups[r];
@@ -2105,20 +2022,13 @@ struct BrRun {
             break;
         }
         case kBrReach: {
-            if (!d_jobs) {
-                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_opp_reach), dim3(grid1(op.n)), block, 0, s, ssum, j.row, j.cid, op.n, op.n_pad, j.q, j.q_out);
-                break;
-            }
             const auto k = RS_BR_PICK(t->dtype, k_br_opp_reach_jobs);
             hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((op.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, op.n, op.n_pad, op.n_hands);
             break;
         }
         case kBrReachOwn: {
-            if (!d_jobs) hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own_reach), dim3(grid1(me.n)), block, 0, s, ssum, j.row, j.cid, me.n, me.n_pad, j.q, j.q_out);
-            else {
-                const auto k = RS_BR_PICK(t->dtype, k_br_own_reach_jobs);
-                hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((me.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, me.n, me.n_pad, me.n_hands);
-            }
+            const auto k = RS_BR_PICK(t->dtype, k_br_own_reach_jobs);
+            hipLaunchKernelGGL(k, dim3(8u * grid1(NB * ((me.n_hands + 7u) / 8u)), nj), block, 0, s, ssum, d_jobs, me.n, me.n_pad, me.n_hands);
             break;
         }
         case kBrMass:   // the mass row of a requested node: the leaf kernels of the run's showdown mode on the node's q
@@ -2126,7 +2036,6 @@ struct BrRun {
             // (small ranges keep a workgroup per (run-out, leaf): the loop's scans are unrolled for 1 326 hands whatever the range holds -- 200 combos: 0.047 against 0.059 s per call)
             const uint32_t most_hands = std::max(me.n_hands, op.n_hands);
             const bool rk = raked && kind == kBrLeaf;   // a raked run's tree terminals go to the RAKED instantiations; mass rows are no terminals (uncontested, 1.0)
-            const BrPay<true> pay3{j.value, j.value_tie, j.value_lose};
             if (sorted && ws_levels && most_hands <= uint32_t(kBrHandsPerThread) * kBrBlock && op.n_hands <= uint32_t(kBrChunkMax) * 64u) {
                 // the level plan's leaf loop: a workgroup per run-out (and slice of the leaves, when run-outs alone do not fill the card)
                 const size_t lds = br_sorted_leaf_lds(op.n_hands) + (((size_t(op.n_hands) + 3) & ~size_t(3)) + 52 * kBrCardHolders) * sizeof(uint16_t) + 64;
@@ -2160,33 +2069,19 @@ struct BrRun {
 #undef RS_LEAF_LOOP
 #undef RS_LEAF_LOOP_
             } else if (sorted) {   // a workgroup per (run-out, leaf)
-                if (!d_jobs && rk)
-                    hipLaunchKernelGGL(k_br_terminal_sorted<true>, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands,
-                                       d_bmask, me.index, j.uncontested, pay3, j.v);
-                else if (!d_jobs)
-                    hipLaunchKernelGGL(k_br_terminal_sorted<false>, dim3(NB), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands, me.d_mask, me.d_pw, me.n_hands, j.q, op.n_hands,
-                                       d_bmask, me.index, j.uncontested, BrPay<false>{j.value}, j.v);
-                else
-                    hipLaunchKernelGGL(rk ? k_br_terminal_sorted_jobs<true> : k_br_terminal_sorted_jobs<false>, dim3(NB, nj), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands,
-                                       me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask, me.index, d_jobs);
+                hipLaunchKernelGGL(rk ? k_br_terminal_sorted_jobs<true> : k_br_terminal_sorted_jobs<false>, dim3(NB, nj), block, br_sorted_leaf_lds(op.n_hands), s, me.d_hands,
+                                   me.d_mask, me.d_pw, me.n_hands, op.n_hands, d_bmask, me.index, d_jobs);
             } else {
                 const size_t lds = size_t(op.n_hands) * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
-                if (!d_jobs && rk)
-                    hipLaunchKernelGGL(k_br_terminal_boards<true>, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
-                                       op.n_hands, d_bmask, j.uncontested, pay3, j.v);
-                else if (!d_jobs)
-                    hipLaunchKernelGGL(k_br_terminal_boards<false>, dim3(grid1(me.n_hands), NB), block, lds, s, me.d_mask, me.d_score, me.d_pw, me.n_hands, op.d_mask, op.d_score, j.q,
-                                       op.n_hands, d_bmask, j.uncontested, BrPay<false>{j.value}, j.v);
-                else
-                    hipLaunchKernelGGL(rk ? k_br_terminal_boards_jobs<true> : k_br_terminal_boards_jobs<false>, dim3(grid1(me.n_hands), NB, nj), block, lds, s, me.d_mask, me.d_score,
-                                       me.d_pw, me.n_hands, op.d_mask, op.d_score, op.n_hands, d_bmask, d_jobs);
+                hipLaunchKernelGGL(rk ? k_br_terminal_boards_jobs<true> : k_br_terminal_boards_jobs<false>, dim3(grid1(me.n_hands), NB, nj), block, lds, s, me.d_mask, me.d_score,
+                                   me.d_pw, me.n_hands, op.d_mask, op.d_score, op.n_hands, d_bmask, d_jobs);
             }
             break;
         }
         case kBrOwnWave: {
-            if (!d_jobs) {
-                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own_wave), dim3(br_wave_blocks(j.n_clusters)), block, 0, s, ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch,
-                                   mode, j.v);
+            if (!ws_levels) {   // depth first: the kind's one-node entry (see there)
+                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own_wave), dim3(br_wave_blocks(h->n_clusters)), block, 0, s, ssum, h->row, h->start, h->order, h->n_clusters, me.n_pad,
+                                   h->vch, mode, h->v);
                 break;
             }
             const auto k = RS_BR_PICK(t->dtype, k_br_own_wave_jobs);
@@ -2205,64 +2100,42 @@ struct BrRun {
         case kBrOwnReal: {
             const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
             const dim3 cols_grid((n_pairs + kBrRealPairs - 1) / kBrRealPairs, nj);
-            if (pp == 1 && !d_jobs) hipLaunchKernelGGL(k_br_own_real_last, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v);
-            else if (pp == 1) hipLaunchKernelGGL(k_br_own_real_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
-            else if (!d_jobs) hipLaunchKernelGGL(k_br_own_real_cols, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, j.n_children, j.vch, j.v);
+            if (pp == 1) hipLaunchKernelGGL(k_br_own_real_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
             else hipLaunchKernelGGL(k_br_own_real_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
             break;
         }
-        case kBrOwnCfrWave: {
-            if (!d_jobs)
-                hipLaunchKernelGGL(k_br_cfr_own_wave, dim3(br_wave_blocks(j.n_clusters)), block, 0, s, cfr_regrets, cfr_ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch,
-                                   j.q, cfr_rmplus, j.v);
-            else hipLaunchKernelGGL(k_br_cfr_own_wave_jobs, dim3(br_wave_blocks(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
+        case kBrOwnCfrWave:
+            hipLaunchKernelGGL(k_br_cfr_own_wave_jobs, dim3(br_wave_blocks(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
             break;
-        }
-        case kBrOwnCfrThread: {
-            if (!d_jobs)
-                hipLaunchKernelGGL(k_br_cfr_own, dim3(grid1(j.n_clusters)), block, 0, s, cfr_regrets, cfr_ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch, j.q,
-                                   cfr_rmplus, j.v);
-            else hipLaunchKernelGGL(k_br_cfr_own_jobs, dim3(grid1(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
+        case kBrOwnCfrThread:
+            hipLaunchKernelGGL(k_br_cfr_own_jobs, dim3(grid1(most(n_clusters)), nj), block, 0, s, cfr_regrets, cfr_ssum, d_jobs, me.n_pad, cfr_rmplus);
             break;
-        }
         case kBrOwnThread: {
-            if (!d_jobs) {
-                hipLaunchKernelGGL(RS_BR_PICK(t->dtype, k_br_own), dim3(grid1(j.n_clusters)), block, 0, s, ssum, j.row, j.start, j.order, j.n_clusters, me.n_pad, j.vch, mode, j.v);
-                break;
-            }
             const auto k = RS_BR_PICK(t->dtype, k_br_own_jobs);
             hipLaunchKernelGGL(k, dim3(grid1(most(n_clusters)), nj), block, 0, s, ssum, d_jobs, me.n_pad, mode);
             break;
         }
         case kBrLockReach:   // the jobs carry their side's shape: the grid is sized by the longest lane row
-            if (!d_jobs) hipLaunchKernelGGL(k_br_lock_reach, dim3(grid1(j.kmax)), block, 0, s, j.sum_src[0], j.n_clusters, j.n_sets, j.kmax, j.row.pitch, j.n_children, j.q, j.q_out);
-            else hipLaunchKernelGGL(k_br_lock_reach_jobs, dim3(grid1(most([](const BrJob &j) { return j.kmax; })), nj), block, 0, s, d_jobs);
+            hipLaunchKernelGGL(k_br_lock_reach_jobs, dim3(grid1(most([](const BrJob &j) { return j.kmax; })), nj), block, 0, s, d_jobs);
             break;
         case kBrLockValue:
-            if (!d_jobs)
-                hipLaunchKernelGGL(k_br_lock_value, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, j.sum_src[0], j.n_clusters, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v);
-            else hipLaunchKernelGGL(k_br_lock_value_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
+            hipLaunchKernelGGL(k_br_lock_value_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
             break;
         case kBrSum:
-            if (!d_jobs) hipLaunchKernelGGL(k_br_sum, dim3(grid1(me.n)), block, 0, s, j.vch, j.n_children, me.n, me.n_pad, j.v);
-            else hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), block, 0, s, d_jobs, me.n, me.n_pad);
+            hipLaunchKernelGGL(k_br_sum_jobs, dim3(grid1(me.n), nj), block, 0, s, d_jobs, me.n, me.n_pad);
             break;
         case kBrReport: {
             const uint32_t pp = per_prefix[r], n_pairs = me.n / pp;
             const dim3 cols_grid((n_pairs + kBrRealPairs - 1) / kBrRealPairs, nj);
-            if (pp == 1 && !d_jobs)
-                hipLaunchKernelGGL(k_br_report_last, dim3(grid1(me.n)), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, j.n_children, j.vch, j.v, j.sum_src[0], j.q, j.q_out);
-            else if (pp == 1) hipLaunchKernelGGL(k_br_report_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
-            else if (!d_jobs)
-                hipLaunchKernelGGL(k_br_report_cols, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, j.n_children, j.vch, j.v, j.sum_src[0], j.q, j.q_out);
+            if (pp == 1) hipLaunchKernelGGL(k_br_report_last_jobs, dim3(grid1(me.n), nj), block, 0, s, me.d_mask, d_bmask, me.n_hands, me.n, me.n_pad, d_jobs);
             else hipLaunchKernelGGL(k_br_report_cols_jobs, cols_grid, block, 0, s, me.d_mask, d_bmask, me.n_hands, n_pairs, pp, me.n_pad, d_jobs);
             break;
         }
         case kBrGadgetReach:   // one job, whichever tree order: the same launch
-            hipLaunchKernelGGL(k_br_gadget_reach, dim3(grid1(op.n)), block, 0, s, d_g_regret, d_g_alt, op.n_hands, op.n, j.q, j.q_out, j.v);
+            hipLaunchKernelGGL(k_br_gadget_reach, dim3(grid1(op.n)), block, 0, s, d_g_regret, d_g_alt, op.n_hands, op.n, h->q, h->q_out, h->v);
             break;
         case kBrGadgetOwn:
-            hipLaunchKernelGGL(k_br_gadget_own, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, d_g_regret, d_g_ssum, d_g_alt, j.sum_src[0], j.v, cfr_rmplus);
+            hipLaunchKernelGGL(k_br_gadget_own, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, d_g_regret, d_g_ssum, d_g_alt, h->sum_src[0], h->v, cfr_rmplus);
             break;
         case kBrKinds:   // a count, no kind
             return;
@@ -2271,45 +2144,42 @@ struct BrRun {
         ++n_launches;
     }
 
-    // depth first: a node's launches around its children's, one node each and straight from the host's jobs
+    // row `at` of the uploaded job table as a launch of its own: every launch of the depth-first order
+    void one(const BrPlan &pl, int at) { launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, job_table + at, 1, &pl.jobs[size_t(at)]); }
+    // depth first: a node's launches around its children's
     void walk(const BrPlan &pl, int id) {
         if (err != hipSuccess) return;
         const rs_tree_node &n = tree->nodes[size_t(id)];
         if (n.kind != RS_NODE_TERMINAL && n.kind != RS_NODE_ACTION) return walk(pl, n.children[0]);   // chance nodes pass through (cfr.rs:306-313)
-        auto one = [&](int at) { launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, nullptr, 1, &pl.jobs[size_t(at)]); };
         const bool own = n.kind == RS_NODE_ACTION && int(n.player) == p;
-        if (!own) one(pl.job_at[size_t(id)]);   // a leaf, or the reach of an opponent node's children
-        else if (pl.own_reach_at[size_t(id)] >= 0) one(pl.own_reach_at[size_t(id)]);   // full-width sweep: the traverser's own reach of its children
+        if (!own) one(pl, pl.job_at[size_t(id)]);   // a leaf, or the reach of an opponent node's children
+        else if (pl.own_reach_at[size_t(id)] >= 0) one(pl, pl.own_reach_at[size_t(id)]);   // full-width sweep, node report: the traverser's own reach of its children
         if (n.kind == RS_NODE_TERMINAL) return;
         for (int a = 0; a < n.n_children; ++a) walk(pl, n.children[a]);
-        one(own ? pl.job_at[size_t(id)] : pl.sum_at[size_t(id)]);
+        one(pl, own ? pl.job_at[size_t(id)] : pl.sum_at[size_t(id)]);
         if (pl.report_at[size_t(id)] >= 0) {   // node report: while the depth's buffers are this node's
-            one(pl.mass_at[size_t(id)]);
-            one(pl.report_at[size_t(id)]);
+            one(pl, pl.mass_at[size_t(id)]);
+            one(pl, pl.report_at[size_t(id)]);
         }
     }
 
-    // one traverser's pass: the plan, the launches in the tree order the workspace was made for (the level plan after one upload of its jobs), the root's values back
+    // one traverser's pass: the plan, one upload of its jobs, the launches in the tree order the workspace was made for, the root's values back
     int run_traverser(double *root_host) {
         BrPlan pl;
         if (int rc = build_plan(pl)) return rc;
-        DevBuf<BrJob> d_jobs;
         n_launches = 0;
-        auto one_gadget = [&](int at) {
-            if (at >= 0) launch(pl.entries[size_t(at)].kind, pl.entries[size_t(at)].round, nullptr, 1, &pl.jobs[size_t(at)]);
-        };
-        if (!ws_levels) {
-            one_gadget(pl.gadget_reach_at);
+        if (job_table.bytes() < pl.jobs.size() * sizeof(BrJob)) err = job_table.alloc(pl.jobs.size());   // (no pass is in flight: each ends with a stream synchronise)
+        if (err == hipSuccess) err = hipMemcpyAsync(job_table, pl.jobs.data(), pl.jobs.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
+        if (!ws_levels) {   // the gadget's jobs above the root (a resolver's sweeps only), the tree between them
+            if (pl.gadget_reach_at >= 0) one(pl, pl.gadget_reach_at);
             walk(pl, 0);
-            one_gadget(pl.gadget_mass_at);
-            one_gadget(pl.gadget_own_at);
+            if (pl.gadget_mass_at >= 0) one(pl, pl.gadget_mass_at);
+            if (pl.gadget_own_at >= 0) one(pl, pl.gadget_own_at);
         } else {   // reach downwards by depth, the leaves in slices of 16 384, values upwards by depth: the plan's order
-            err = d_jobs.alloc(pl.jobs.size());
-            if (err == hipSuccess) err = hipMemcpyAsync(d_jobs, pl.jobs.data(), pl.jobs.size() * sizeof(BrJob), hipMemcpyHostToDevice, t->stream);
             for (size_t lo = 0, hi; lo < pl.jobs.size() && err == hipSuccess; lo = hi) {
                 const size_t most = pl.entries[lo].kind == kBrLeaf || pl.entries[lo].kind == kBrMass ? 16384 : pl.jobs.size();
                 for (hi = lo + 1; hi < pl.jobs.size() && hi - lo < most && pl.entries[hi].key == pl.entries[lo].key; ++hi) {}
-                launch(pl.entries[lo].kind, pl.entries[lo].round, d_jobs + lo, uint32_t(hi - lo), &pl.jobs[lo]);
+                launch(pl.entries[lo].kind, pl.entries[lo].round, job_table + lo, uint32_t(hi - lo), &pl.jobs[lo]);
             }
         }
         if (err == hipSuccess) err = hipMemcpyAsync(root_host, pl.root, side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
@@ -2317,7 +2187,7 @@ struct BrRun {
             gadget_term.resize(side[p].n);
             if (err == hipSuccess) err = hipMemcpyAsync(gadget_term.data(), d_g_row[p], side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
         }
-        const hipError_t done = hipStreamSynchronize(t->stream);   // the plan and d_jobs are freed on return: after an error too, nothing queued may still touch them
+        const hipError_t done = hipStreamSynchronize(t->stream);   // the plan is freed on return and the next pass overwrites the job table: after an error too, nothing queued may still touch them
         if (err == hipSuccess) err = done;
         return err == hipSuccess ? RS_OK : hip_fail(err, ws_levels ? "rs_best_response (level plan)" : "rs_best_response");
     }
@@ -2760,7 +2630,7 @@ int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_bo
             if (!s.n_clusters[r]) continue;   // the player has no node in this round
             if (!src) return fail(RS_ERR_INVALID, "rs_best_response: no cluster ids for round " + std::to_string(r) + " player " + std::to_string(p));
             // lane-level ids and, per info set, its lanes in ascending order.  A blocked lane (its hand uses a card of the run-out: no such deal) belongs to no
-            // info set: it is listed in an extra segment after the last cluster (k_br_own writes its 0) and looks up cluster 0 where an id is needed but not used
+            // info set: it is listed in an extra segment after the last cluster (k_br_own_jobs writes its 0) and looks up cluster 0 where an id is needed but not used
             const uint32_t NC = s.n_clusters[r];
             std::vector<uint32_t> cv(s.n), seg(s.n), start(size_t(NC) + 2, 0), order(s.n);
             for (size_t b = 0; b < NB; ++b)

@@ -20,7 +20,7 @@ from oracle import np_restate as npr
 from oracle import orc
 from rustsolver_amd import _lib as L
 from rustsolver_amd import abstraction as ab
-from test_np_br_cpu import ATOL, MARGIN, RIVER, RTOL, TURN, check_margins, exact_tie_game, combos_of, pick_ranges, prefixes_of, random_cids, sizes_of
+from test_np_br_cpu import ATOL, MARGIN, RIVER, RTOL, TURN, check_margins, exact_tie_game, combos_of, disjoint_ranges, pick_ranges, prefixes_of, random_cids, sizes_of
 
 pytestmark = pytest.mark.gpu
 
@@ -376,11 +376,16 @@ def test_first_maximum_not_last_on_an_exact_tie_on_the_device():
         assert last[0] > got[mode][0] + 10.0, (mode, got[mode], last)
 
 
-@pytest.mark.parametrize("n0,n1", [(1, 40), (40, 1), (1, 1)])
+# ranges of 1, 7, 8 and 9 hands: the reach kernels deal the hands out to eight slices (br_xcd_sliced_lane) -- slices that are empty, of one hand, and of one and two hands
+SLICE_RANGES = [(1, 9), (7, 8), (8, 7), (9, 1)]
+
+
+@pytest.mark.parametrize("n0,n1", [(1, 40), (40, 1), (1, 1)] + SLICE_RANGES)
 def test_one_hand_ranges_from_the_turn(n0, n1):
-    """a range of one hand on either side: two of the 48 turn cards block it (no deal in those run-outs: the lane carries nothing and belongs to no info set)"""
+    """a range of one hand on either side: two of the 48 turn cards block it (no deal in those run-outs: the lane carries nothing and belongs to no info set); and the
+    ranges of SLICE_RANGES, hands that share no card, in both tree orders"""
     rng = np.random.Generator(np.random.PCG64(50 + n0))
-    h = pick_ranges(rng, TURN, n0, n1)
+    h = disjoint_ranges(rng, TURN, n0, n1) if (n0, n1) in SLICE_RANGES else pick_ranges(rng, TURN, n0, n1)
     if n0 == n1 == 1:
         h[1] = combos_of(TURN)[7:8] if tuple(h[0][0]) != tuple(combos_of(TURN)[7]) else combos_of(TURN)[900:901]
     cids = random_cids(rng, TURN, h, [(min(n0, 4), min(n1, 4)), (3, 5)])

@@ -103,7 +103,7 @@ def same_reports(a, b):
 
 
 @pytest.mark.timeout(120)
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", CASES + ["turn_slices_7_8"])
 def test_locks_that_no_table_can_express_equal_the_restatement(name):
     """best response in every mode, every node-report row and one full-width sweep per traverser.  Without the feature nothing here can pass: the wrappers have no locks=
     and no table row plays a strategy that differs inside a cluster"""
@@ -158,7 +158,7 @@ def test_locks_that_no_table_can_express_equal_the_restatement(name):
 
 
 @pytest.mark.timeout(120)
-@pytest.mark.parametrize("name", ["river_wave_35", "turn_imperfect_recall", "flop_three_rounds"])
+@pytest.mark.parametrize("name", ["river_wave_35", "turn_imperfect_recall", "flop_three_rounds", "turn_slices_7_8"])
 def test_both_tree_orders_repeats_and_lock_order_give_the_same_bits(name):
     s, dev = device_of(name)
     nodes = s["nodes"]

@@ -16,7 +16,7 @@ import rustsolver_amd as rs
 from oracle import np_br as nbr
 from rustsolver_amd import _lib as L
 from test_gpu_br_pinned import depth_first
-from test_gpu_range_cfr import Device, same_tables, trainer_game
+from test_gpu_range_cfr import SLICES, Device, same_tables, trainer_game
 from test_node_report_cpu import CASES, close, report_case, restated, rows_of, setup
 
 pytestmark = pytest.mark.gpu
@@ -59,7 +59,7 @@ def compare(got, want, what):
             close(x, y, (what, i, row))
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", CASES + SLICES)
 def test_report_equals_the_restatement(name):
     """every action node, both traversers, average and current strategies, rank-order and pair-loop leaves"""
     s, dev = device_of(name)
@@ -75,7 +75,7 @@ def test_report_equals_the_restatement(name):
     dev.close()
 
 
-@pytest.mark.parametrize("name", ["river_wave_35", "turn_imperfect_recall", "flop_three_rounds"])
+@pytest.mark.parametrize("name", ["river_wave_35", "turn_imperfect_recall", "flop_three_rounds"] + SLICES)
 def test_both_tree_orders_repeats_and_subsets_give_the_same_bits(name):
     s, dev = device_of(name)
     ids = action_ids(s["nodes"])

@@ -108,7 +108,7 @@ def check_reports(dev, s, sig, rake, what, game=None, walks=(False,), **kw):
 
 
 @pytest.mark.timeout(180)
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", CASES + ["turn_slices_7_8"])                       # ... and 7 x 8 hands: the depth-first walk's leaf jobs lie at rows beyond the table's first
 def test_raked_walks_equal_the_restatement(name):
     """best response in every mode, every node-report row and one full-width sweep per traverser under rake; once with weighted ranges and once around a lock.  Without
     the feature nothing here can run: the wrappers have no rake= and the library no _raked entry points"""

@@ -15,8 +15,8 @@ from oracle import np_br as nbr
 from oracle import np_restate as npr
 from rustsolver_amd import _lib as L
 from rustsolver_amd import abstraction as ab
-from test_gpu_br_pinned import GDT, MODES, TRAINER_CASES, close, depth_first, edge_sums, python_cluster_ids
-from test_np_br_cpu import ATOL, RIVER, RTOL, TURN, combos_of, lane_cids, pick_ranges, random_cids, sizes_of
+from test_gpu_br_pinned import GDT, MODES, SLICE_RANGES, TRAINER_CASES, close, depth_first, edge_sums, python_cluster_ids
+from test_np_br_cpu import ATOL, RIVER, RTOL, TURN, combos_of, disjoint_ranges, lane_cids, pick_ranges, random_cids, sizes_of
 from test_range_cfr_cpu import RIVER_TREE, TURN_TREE, adopt_tree, compare_cells, random_tables
 
 pytestmark = pytest.mark.gpu
@@ -69,12 +69,18 @@ def make_case(name):
     if name == "turn_one_hand":                     # a range of one hand: two turn cards block it
         h = pick_ranges(rng, TURN, 1, 7)
         return TURN, h, random_cids(rng, TURN, h, [(1, 3), (2, 4)]), [(1, 3), (2, 4)], TURN_TREE
+    if name in SLICES:                              # 1, 7, 8 and 9 hands a side: empty and uneven slices of the reach kernels' lane mapping (br_xcd_sliced_lane)
+        n0, n1 = (int(x) for x in name.split("_")[2:])
+        h = disjoint_ranges(rng, TURN, n0, n1)
+        sizes = [(min(n0, 3), min(n1, 4)), (5, 6)]
+        return TURN, h, random_cids(rng, TURN, h, sizes), sizes, TURN_TREE
     if name == "turn_no_opponent":
         h = no_opponent_game()
         return TURN, h, random_cids(rng, TURN, h, [(4, 2), (5, 3)]), [(4, 2), (5, 3)], TURN_TREE
     raise KeyError(name)
 
 
+SLICES = ["turn_slices_%d_%d" % r for r in SLICE_RANGES]
 CASES = ["river_lanes", "river_wave_35", "river_runs_8_9", "turn_imperfect_recall", "turn_lanes", "river_unused_cluster", "turn_one_hand", "turn_no_opponent"]
 # the form of the LAST round's own nodes per player (wave per info set?).  turn_lanes' first round (9 and 7 info sets over 48 run-outs) is in the wave form all the
 # same; test_gpu_range_cfr_edges.FORMS keys the forms per (round, player)
@@ -145,7 +151,7 @@ def compare_sweep(nodes, game, cids, p, before, got, want, what):
     return cells, differ, worst
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", CASES + SLICES)
 def test_one_sweep_equals_the_restatement(name):
     """from random and from zero tables, both traversers, plain and RM+, rank-order and pair-loop leaves; the same call twice gives the same bits"""
     board0, h, cids, sizes, tree = make_case(name)
@@ -183,7 +189,7 @@ def test_one_sweep_equals_the_restatement(name):
     dev.close()
 
 
-@pytest.mark.parametrize("name", ["turn_imperfect_recall", "turn_lanes"])
+@pytest.mark.parametrize("name", ["turn_imperfect_recall", "turn_lanes"] + SLICES)
 def test_level_plan_and_depth_first_walk_give_the_same_bits(name):
     board0, h, cids, sizes, tree = make_case(name)
     nodes, _ = npr.build_tree(n_board_cards=len(board0), bet_sizes=tree[0], raise_sizes=tree[1])

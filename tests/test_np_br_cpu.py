@@ -30,6 +30,15 @@ def pick_ranges(rng, board0, n0, n1):
     return [combos[np.sort(rng.choice(len(combos), n, replace=False))] for n in (n0, n1)]
 
 
+def disjoint_ranges(rng, board0, n0, n1):
+    """hands that share no card with the board or with each other: a run-out blocks at most one of them"""
+    combos = combos_of(board0)
+    free = [c for c in range(52) if c not in board0]
+    pairs = np.sort(rng.permutation(free)[: 2 * (n0 + n1)].reshape(-1, 2), axis=1)
+    at = [int(np.flatnonzero((combos == pair).all(axis=1))[0]) for pair in pairs]
+    return [combos[np.sort(at[:n0])], combos[np.sort(at[n0:])]]
+
+
 def prefixes_of(board0):
     K, D = 5 - len(board0), 52 - len(board0)
     return [1, D, D * (D - 1)][: K + 1]

@@ -45,4 +45,4 @@ if "--real" in sys.argv[1:]:
 else:
     for k in range(4):
         e, dt = timed(False)
-        print("exploitability %.6f  %.3f s  launches %d  held %.2f GB" % (e, dt, tr.br_launches(), tr.br_bytes() / 1e9))
+        print("exploitability %.6f  %.4f s  launches %d  held %.2f GB" % (e, dt, tr.br_launches(), tr.br_bytes() / 1e9))
