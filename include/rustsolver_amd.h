@@ -907,6 +907,52 @@ int rs_ochs_round_features(rs_table *table, rs_hand_indexer *indexer, const uint
  * launched or allocated: n_bins outside 1..RS_EHS_MAX_BINS, NULL d_counts.  A bad listed board: as above.  Synchronises. */
 int rs_ehs_preflop_counts(rs_table *table, int n_bins, const uint8_t *d_boards, uint32_t n_boards, uint32_t *d_counts);
 
+/* ---- potential-aware abstraction: next-round bucket histograms and a k-means under the greedy earth mover's distance (rs_potential.hip) ---------------------------------
+ * Ganzfried and Sandholm, "Potential-aware imperfect-recall abstraction with earth mover's distance in imperfect-information games" (AAAI 2014); DESIGN.md section 4.
+ *   row of a hand      hole pair + a board of nb = 3 or 4 cards; n_draws = 50 - nb.  For every card x in neither, bucket(x) = next_buckets[hand_index of
+ *                      (hole, board + x) in the next round's indexer [2, nb + 1]].  The row is the multiset of those buckets: uint32 row[RS_PA_ROW_WORDS], entries
+ *                      `bucket << 8 | count` with count >= 1, ascending by bucket, then zeros.  The counts sum to n_draws.  A WELL-FORMED row is exactly that: m >= 1
+ *                      entries with strictly ascending buckets below n_next and counts >= 1 that sum to n_draws, followed by RS_PA_ROW_WORDS - m zero words.
+ *   metric             ground[n_next][n_next] (finite, >= 0): ground[b][t] is what moving mass from bucket b of a point to bucket t of a mean costs.
+ *                      order[b][.] = the ids 0 .. n_next - 1 sorted stably by ascending ground[b][.] (among equal distances the lower id first).
+ *   distance           of a row p with entries (b_j, c_j), j = 0 .. m - 1, to a dense mean q[n_next] (finite, >= 0) -- the paper's Algorithm 2 in f32 without FMA:
+ *                          rem = copy of q;  target[j] = (float)c_j / (float)n_draws;  tot[j] = 0;  done[j] = false
+ *                          for i = 0 .. n_next - 1, for j = 0 .. m - 1 ascending, unless done[j]:
+ *                              t = order[b_j][i];  a = rem[t];  unless a > 0: next j;  d = ground[b_j][t]
+ *                              a < target[j]:  tot[j] += a * d;  target[j] -= a;  rem[t] = 0
+ *                              otherwise:      tot[j] += target[j] * d;  rem[t] = a - target[j];  target[j] = 0;  done[j] = true
+ *                          dist = ((0.0f + tot[0]) + tot[1]) + ... + tot[m - 1]
+ *                      The per-entry totals summed in entry order are this library's choice (the paper keeps one running total).  Neither symmetric nor a metric.
+ *   k-means            assignment = the first mean with the strictly smallest distance (rs_kmeans_predict's rule).  One Lloyd iteration: assign every datum;
+ *                      changed = the data whose cluster differs from the iteration before (before the first: none, so changed[0] = n); for every cluster k with
+ *                      members: mean[k][b] = (float)((double)sum[k][b] / ((double)members[k] * (double)n_draws)), sum = the integer sum of its members' counts; a
+ *                      cluster without members keeps its mean; the loop stops after an iteration with changed == 0. */
+#define RS_PA_ROW_WORDS 48
+#define RS_PA_MAX_NEXT 8192
+typedef struct rs_pa_metric rs_pa_metric;
+/* indexer = hand_indexer_s::init(2, [2, 3] | [2, 4]), next_indexer = (2, [2, 4] | [2, 5]); d_next_buckets: DEVICE uint32 [rs_hand_indexer_size(next_indexer, 1)];
+ * d_rows: DEVICE uint32 [rs_hand_indexer_size(indexer, 1)][RS_PA_ROW_WORDS].  d_boards[nb][pitch] (pitch = round_up(n_boards, 64)) lists boards: the rows of their hole
+ * pairs are written, the others left as they were.  NULL = the whole round, swept as one board per suit-isomorphism class: every row is written.  Suit-isomorphic copies of
+ * a hand write identical bits: plain stores.  RS_ERR_INVALID before anything is launched: indexers of any other shape pair, n_next outside 1..RS_PA_MAX_NEXT, NULL buffers
+ * with work to do.  A listed board with a repeated card or a byte >= 52 is skipped, and so is a hand one of whose buckets is >= n_next; either raises an error word that this
+ * call reads back: RS_ERR_INVALID, everything else written.  Synchronises. */
+int rs_next_round_histograms(rs_table *table, rs_hand_indexer *indexer, rs_hand_indexer *next_indexer, const uint32_t *d_next_buckets, int n_next,
+                             const uint8_t *d_boards, uint32_t n_boards, uint32_t *d_rows);
+/* ground: HOST [n_next][n_next], 1 <= n_next <= RS_PA_MAX_NEXT; a value that is negative or not finite is RS_ERR_INVALID.  `order` is built here, once, and both are
+ * uploaded to the table's device.  table == NULL gives a host-only metric: rs_pa_distance takes it, the device calls refuse it. */
+int rs_pa_metric_create(rs_table *table, const float *ground, int n_next, rs_pa_metric **out);
+void rs_pa_metric_destroy(rs_pa_metric *metric);
+/* one distance on the host (no GPU needed).  RS_ERR_INVALID: a row that is not well-formed, a mean value that is negative or not finite */
+int rs_pa_distance(const rs_pa_metric *metric, const uint32_t *row /* HOST [RS_PA_ROW_WORDS] */, int n_draws, const float *mean /* HOST [n_next] */, float *out);
+/* d_rows: DEVICE [.][RS_PA_ROW_WORDS]; datum i is row d_sel[i] (d_sel == NULL: row i); means: HOST [n_means][n_next]; d_clusters[n] / d_min_dist[n]: DEVICE, either may
+ * be NULL.  A row that is not well-formed raises the error word: its outputs are left as they were and the call returns RS_ERR_INVALID after the others are done.
+ * Both synchronise.  rs_pa_fit: means in/out, changed: HOST [iterations], iterations_run (may be NULL) = the iterations done; d_clusters and d_min_dist are those of the
+ * last assignment (a datum whose row is not well-formed belongs to no cluster: d_clusters = 0xFFFFFFFF). */
+int rs_pa_predict(rs_table *table, const rs_pa_metric *metric, const uint32_t *d_rows, const uint32_t *d_sel, size_t n, int n_draws, const float *means, int n_means,
+                  uint32_t *d_clusters, float *d_min_dist);
+int rs_pa_fit(rs_table *table, const rs_pa_metric *metric, const uint32_t *d_rows, const uint32_t *d_sel, size_t n, int n_draws, float *means, int n_means, int iterations,
+              uint32_t *d_clusters, float *d_min_dist, uint32_t *changed, int *iterations_run);
+
 /* ---- showdown evaluation on the device ---------------------------------------------------------------
  * d_cards[9][pitch] (u8, pitch = round_up(n_deals, 64)): rows 0-4 the board, 5-6 player 0's hole cards, 7-8 player 1's;
  * card = 4*rank + suit, rank 0..12 = 2..A (cfr.rs:592).  d_sign[lane] = sign(evaluate(hand0) - evaluate(hand1)) exactly as

@@ -28,6 +28,7 @@ DEAL_SEQUENTIAL, DEAL_JOINT = 0, 1   # rs_range_weights.deal (RS_DEAL_*)
 DIST_EMD, DIST_L2 = 0, 1
 EHS_MAX_BINS = 64           # RS_EHS_MAX_BINS
 OCHS_MAX_CLUSTERS, OCHS_NO_CLUSTER = 8, 255   # RS_OCHS_*
+PA_ROW_WORDS, PA_MAX_NEXT = 48, 8192          # RS_PA_*
 K_UPDATE, K_NODE_UTIL, K_REACH, K_CHANCE, K_DISCOUNT, K_STRATEGY, K_TREE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -304,6 +305,12 @@ SYMBOLS = {
     "rs_ehs_round_histograms": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint32, _P]),
     "rs_ochs_round_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_uint32, _P]),
     "rs_ehs_preflop_counts": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P]),
+    "rs_next_round_histograms": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_uint32, _P]),
+    "rs_pa_metric_create": (C.c_int, [_P, _P, C.c_int, _PP]),
+    "rs_pa_metric_destroy": (None, [_P]),
+    "rs_pa_distance": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_float)]),
+    "rs_pa_predict": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, C.c_int, _P, _P]),
+    "rs_pa_fit": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "rs_table_save": (C.c_int, [_P, C.c_char_p]),
     "rs_table_load": (C.c_int, [C.c_char_p, C.c_int, _PP]),
     "rs_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -571,3 +571,148 @@ class Kmeans:
         L.check(L.load().rs_kmeans_fit_growbatch(self.table._h, dist, self._data.ptr, self.n, do.ptr, batch, c.ctypes.data, len(c), self.n_bins, dc.ptr, db.ptr,
                                                  stats.ctypes.data))
         return dc.download(np.uint32, batch), c, db.download(np.float32, 2 * batch).reshape(batch, 2), stats
+
+
+# ---- potential-aware abstraction: next-round histograms and a k-means under the greedy EMD (rs_potential.hip; semantics in include/rustsolver_amd.h) -------------
+PA_ROW_WORDS, PA_MAX_NEXT = L.PA_ROW_WORDS, L.PA_MAX_NEXT
+
+
+class SparseRows:
+    """The device buffer `next_round_histograms` fills: uint32 [rows][PA_ROW_WORDS], entries `bucket << 8 | count` ascending by bucket, then zeros"""
+
+    def __init__(self, table, rows, n_draws, buffer):
+        self.table, self.rows, self.n_draws, self.buffer = table, rows, n_draws, buffer
+
+    @property
+    def ptr(self):
+        return self.buffer.ptr
+
+    @property
+    def nbytes(self):
+        return self.buffer.nbytes
+
+    def download(self, first=0, count=None):
+        """rows first .. first + count (default: all) as uint32 [count][PA_ROW_WORDS] on the host: the turn round is 2.7 GB, so in slices"""
+        count = self.rows - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.rows:
+            raise IndexError("rows %d .. %d of %d" % (first, first + count, self.rows))
+        out = np.empty((count, PA_ROW_WORDS), dtype=np.uint32)
+        if out.size:
+            L.check(L.load().rs_d2h(self.table._h, out.ctypes.data, self.ptr + first * PA_ROW_WORDS * 4, out.nbytes))
+        return out
+
+    def gather(self, indices):
+        """the rows `indices` (a few: initial means), one copy each"""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        return np.concatenate([self.download(int(i), 1) for i in idx]) if len(idx) else np.zeros((0, PA_ROW_WORDS), dtype=np.uint32)
+
+    def dense(self, words, n_next):
+        """rows as they are stored (uint32 [n][PA_ROW_WORDS] or one row) -> float32 [n][n_next] of count / n_draws"""
+        return dense_rows(words, n_next, self.n_draws)
+
+
+def dense_rows(words, n_next, n_draws):
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    one = w.ndim == 1
+    w = w.reshape(-1, PA_ROW_WORDS)
+    out = np.zeros((len(w), n_next), dtype=np.float32)
+    at, j = np.nonzero(w)
+    out[at, (w[at, j] >> 8).astype(np.int64)] = (w[at, j] & 255).astype(np.float32) / np.float32(n_draws)
+    return out[0] if one else out
+
+
+def next_round_histograms(table, indexer, next_indexer, next_buckets, n_next, boards=None, out=None):
+    """A flop ([2, 3], next [2, 4]) or turn ([2, 4], next [2, 5]) hand as the multiset of the next round's buckets over its 47 / 46 next cards.  next_buckets: the next
+    round's bucket file (uint32 [next_indexer.size(1)], values below n_next) as a numpy array or a DeviceBuffer that holds it.  boards: uint8 [n][3 or 4], or None = the
+    whole round.  Rows whose hands lie on no listed board are left as they were (a buffer made here starts at zero).  -> SparseRows"""
+    from .solver import DeviceBuffer
+    nb = indexer.n_cards(indexer.rounds - 1) - 2
+    if out is None:
+        rows = indexer.size(indexer.rounds - 1)
+        out = SparseRows(table, rows, 50 - nb, DeviceBuffer(table, max(rows, 1) * PA_ROW_WORDS * 4))
+        out.buffer.zero()
+    if isinstance(next_buckets, DeviceBuffer):
+        dn = next_buckets
+    else:
+        nbk = np.ascontiguousarray(next_buckets, dtype=np.uint32).reshape(-1)
+        if len(nbk) != next_indexer.size(next_indexer.rounds - 1):
+            raise ValueError("the next round's bucket file has %d entries" % next_indexer.size(next_indexer.rounds - 1))
+        dn = DeviceBuffer.from_numpy(table, nbk)
+    db, n = None, 0
+    if boards is not None:
+        if np.asarray(boards).size == 0:
+            return out
+        db, n = _board_rows(table, boards, nb)
+    L.check(L.load().rs_next_round_histograms(table._h, indexer._h, next_indexer._h, dn.ptr, n_next, db.ptr if db else None, n, out.ptr))
+    return out
+
+
+def ground_distances(table, centers, dist=DIST_EMD):
+    """[K][K] float32 with g[i][j] = the distance of centre i to centre j as rs_kmeans_predict computes it: its d_min_dist with the centres as data and centre j alone"""
+    c = np.ascontiguousarray(centers, dtype=np.float32)
+    if c.ndim != 2:
+        raise ValueError("centers are [k][n_bins]")
+    km = Kmeans(table, c)
+    return np.stack([km.predict(c[j:j + 1], dist)[1] for j in range(len(c))], axis=1) if len(c) else np.zeros((0, 0), dtype=np.float32)
+
+
+class PotentialKmeans:
+    """k-means over SparseRows under the greedy earth mover's distance whose ground distance is `ground` [n_next][n_next] (distances between the next round's centres).
+    table=None gives a host-only object: `distance` works, the device calls do not."""
+
+    def __init__(self, table, rows, ground):
+        g = np.ascontiguousarray(ground, dtype=np.float32)
+        if g.ndim != 2 or g.shape[0] != g.shape[1]:
+            raise ValueError("ground is [n_next][n_next]")
+        h = C.c_void_p()
+        L.check(L.load().rs_pa_metric_create(table._h if table is not None else None, g.ctypes.data, g.shape[0], C.byref(h)))
+        self._h, self.table, self.rows, self.n_next = h, table, rows, g.shape[0]
+
+    def _means(self, means):
+        m = np.array(means, dtype=np.float32, order="C")
+        if m.ndim != 2 or m.shape[1] != self.n_next:
+            raise ValueError("means are [k][n_next]")
+        return m
+
+    def _sel(self, sel):
+        from .solver import DeviceBuffer
+        if sel is None:
+            return None, self.rows.rows
+        s = np.ascontiguousarray(sel, dtype=np.uint32).reshape(-1)
+        return (DeviceBuffer.from_numpy(self.table, s) if len(s) else None), len(s)
+
+    def distance(self, row, mean, n_draws=None):
+        """one distance on the host: row uint32 [PA_ROW_WORDS], mean float32 [n_next]"""
+        r = np.ascontiguousarray(row, dtype=np.uint32).reshape(-1)
+        m = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+        if len(r) != PA_ROW_WORDS or len(m) != self.n_next:
+            raise ValueError("a row of PA_ROW_WORDS words and a mean of n_next values")
+        out = C.c_float()
+        L.check(L.load().rs_pa_distance(self._h, r.ctypes.data, self.rows.n_draws if n_draws is None else n_draws, m.ctypes.data, C.byref(out)))
+        return np.float32(out.value)
+
+    def predict(self, means, sel=None):
+        """-> (clusters uint32 [n], distance to the chosen mean float32 [n]); datum i is row sel[i] (None: every row)"""
+        from .solver import DeviceBuffer
+        m = self._means(means)
+        ds, n = self._sel(sel)
+        dc, dm = DeviceBuffer(self.table, max(n, 1) * 4), DeviceBuffer(self.table, max(n, 1) * 4)
+        L.check(L.load().rs_pa_predict(self.table._h, self._h, self.rows.ptr, ds.ptr if ds else None, n, self.rows.n_draws, m.ctypes.data, len(m), dc.ptr, dm.ptr))
+        return dc.download(np.uint32, n), dm.download(np.float32, n)
+
+    def fit(self, means, iterations=10, sel=None):
+        """the Lloyd loop -> (clusters uint32 [n], new means [k][n_next], distances float32 [n], changed uint32 [iterations run])"""
+        from .solver import DeviceBuffer
+        m = self._means(means)
+        ds, n = self._sel(sel)
+        dc, dm = DeviceBuffer(self.table, max(n, 1) * 4), DeviceBuffer(self.table, max(n, 1) * 4)
+        changed, ran = np.zeros(max(iterations, 1), dtype=np.uint32), C.c_int()
+        L.check(L.load().rs_pa_fit(self.table._h, self._h, self.rows.ptr, ds.ptr if ds else None, n, self.rows.n_draws, m.ctypes.data, len(m), iterations, dc.ptr, dm.ptr,
+                                   changed.ctypes.data, C.byref(ran)))
+        return dc.download(np.uint32, n), m, dm.download(np.float32, n), changed[:ran.value]
+
+    def __del__(self):
+        try:
+            L.load().rs_pa_metric_destroy(self._h)
+        except Exception:
+            pass

@@ -2,12 +2,13 @@
 // the cards and pairs, get_bin over staged thresholds.  The stages of a board's sweep, one copy each: the decode of a listed or numbered board (sweep_board), a run-out's
 // cards (run_out), the 1081 pairs evaluated into keys (fill_keys), their sort (sort_keys), a hole pair's number on the board (hole_pair_number, pair_positions), and the
 // whole uint16 histogram of a board (board_histogram, hist_count) that k_ehs_round_hist and k_preflop_counts end differently.  Host: the thresholds, the histogram's LDS
-// size, and a launch with an error word (launch_checked; grant_lds is defined in rs_ochs.hip).  Cards and suits only ever select under predicates (no array
+// size, and a launch with an error word (launch_checked; grant_lds and class_boards are defined in rs_ochs.hip).  Cards and suits only ever select under predicates (no array
 // indexed by a card), so nothing here costs a kernel scratch.
 #pragma once
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "rs_hand_index.hpp"
 #include "rs_internal.hpp"
@@ -267,11 +268,13 @@ inline void ehs_thresholds(int n_bins, float *thr) {
 
 // dynamic LDS beyond what a launch gets unasked (rs_ochs.hip)
 int grant_lds(const void *kernel, size_t lds, const char *who);
+// one representative board per suit-isomorphism class of the nb-card boards, as SoA rows [nb][pitch] (rs_ochs.hip)
+int class_boards(int nb, std::vector<uint8_t> *rows, uint32_t *n, uint32_t *pitch);
 
 // A launch with an error word: the word allocated and zeroed on the table's stream, launch(word) to enqueue `kernel`, then the launch's own error and the word read
-// back.  A set word is RS_ERR_INVALID: `what` repeats a card or holds a byte that is no card
+// back.  A set word is RS_ERR_INVALID: `what` repeats a card or holds a byte that is no card.  With `word` the word goes there instead and the caller words the refusal
 template <class Launch>
-int launch_checked(rs_table *t, const char *who, const char *kernel, const char *what, Launch launch) {
+int launch_checked(rs_table *t, const char *who, const char *kernel, const char *what, Launch launch, uint32_t *word = nullptr) {
     DevBuf<uint32_t> d_err;
     hipError_t e = d_err.alloc(1);
     if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": error word").c_str());
@@ -284,6 +287,10 @@ int launch_checked(rs_table *t, const char *who, const char *kernel, const char 
     e = hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
     if (e != hipSuccess) return hip_fail(e, who);
+    if (word) {
+        *word = err;
+        return RS_OK;
+    }
     if (err) return fail(RS_ERR_INVALID, std::string(who) + ": " + what + " repeats a card or holds a byte that is not a card (0..51); nothing was written for it");
     return RS_OK;
 }

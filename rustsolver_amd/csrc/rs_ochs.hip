@@ -239,10 +239,6 @@ int grant_lds(const void *kernel, size_t lds, const char *who) {
     return fail(RS_ERR_UNSUPPORTED, std::string(who) + ": the device grants no workgroup " + std::to_string(lds) + " bytes of LDS (" + hipGetErrorString(e) + ")");
 }
 
-}  // namespace rs
-
-namespace {
-
 // one representative board per suit-isomorphism class of the nb-card boards, as SoA rows [nb][pitch]
 int class_boards(int nb, std::vector<uint8_t> *rows, uint32_t *n, uint32_t *pitch) {
     const uint8_t cpr[1] = {(uint8_t)nb};
@@ -267,7 +263,7 @@ int class_boards(int nb, std::vector<uint8_t> *rows, uint32_t *n, uint32_t *pitc
     return RS_OK;
 }
 
-}  // namespace
+}  // namespace rs
 
 extern "C" {
 

@@ -52,8 +52,11 @@ def main():
     ap.add_argument("--bins", type=int, required=True)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None, help="bucket file to write (refuses to overwrite); omitted: nothing is written")
+    ap.add_argument("--centers-out", default=None, help=".npy to write the fitted centres to (refuses to overwrite): what tools/gen_potential.py --next-centers reads")
     ap.add_argument("--no-kmeans", action="store_true", help="histograms and checksum only")
     args = ap.parse_args()
+    if args.centers_out and os.path.exists(args.centers_out):
+        raise SystemExit("gen_emd: %s exists; it is not overwritten" % args.centers_out)
     if rs.device_count() < 1:
         raise SystemExit("gen_emd: no HIP device visible; the engine has no CPU fallback")
     cpr, n_boards, runouts, completions = ROUNDS[args.round]
@@ -95,6 +98,10 @@ def main():
         if args.out:
             ab.write_cluster_file(args.out, clusters)
             print("wrote %s: %d u32" % (args.out, len(clusters)))
+        if args.centers_out:
+            with open(args.centers_out, "xb") as f:
+                np.save(f, centers)
+            print("wrote %s: %d centres" % (args.centers_out, len(centers)))
     print(json.dumps(result))
 
 

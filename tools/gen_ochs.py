@@ -51,12 +51,15 @@ def main():
     ap.add_argument("--opp-clusters", type=int, default=8, help="opponent ranges (1..8; the reference's n_opp_clusters is 8)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None, help="bucket file to write (refuses to overwrite); omitted: nothing is written")
+    ap.add_argument("--centers-out", default=None, help=".npy to write the fitted centres to (refuses to overwrite): what tools/gen_potential.py --next-centers reads")
     ap.add_argument("--no-kmeans", action="store_true", help="opponent ranges, features and checksum only")
     args = ap.parse_args()
     if not 1 <= args.opp_clusters <= ab.OCHS_MAX_CLUSTERS:
         ap.error("--opp-clusters must be 1..%d" % ab.OCHS_MAX_CLUSTERS)
     if args.out and os.path.exists(args.out):
         raise SystemExit("gen_ochs: %s exists; it is not overwritten" % args.out)
+    if args.centers_out and os.path.exists(args.centers_out):
+        raise SystemExit("gen_ochs: %s exists; it is not overwritten" % args.centers_out)
     if rs.device_count() < 1:
         raise SystemExit("gen_ochs: no HIP device visible; the engine has no CPU fallback")
     cpr, n_boards, runouts = ROUNDS[args.round]
@@ -108,6 +111,10 @@ def main():
         if args.out:
             ab.write_cluster_file(args.out, clusters)
             print("wrote %s: %d u32" % (args.out, len(clusters)))
+        if args.centers_out:
+            with open(args.centers_out, "xb") as f:
+                np.save(f, centers)
+            print("wrote %s: %d centres" % (args.centers_out, len(centers)))
     print(json.dumps(result))
 
 
