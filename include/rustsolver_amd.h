@@ -58,7 +58,9 @@ extern "C" {
                                  still 6: node locks (rs_node_locks, rs_node_lock_size, rs_best_response_locked, rs_node_report_locked, rs_range_cfr_create_locked) -- additions
                                  only: a call without locks builds the plan it built and returns the bits it returned;
                                  still 6: rake (rs_rake, rs_rake_payoffs, rs_best_response_raked, rs_node_report_raked, rs_range_cfr_create_raked) -- additions only: a call
-                                 without rake runs the code it ran and returns the bits it returned */
+                                 without rake runs the code it ran and returns the bits it returned;
+                                 still 6: weighted dealing (rs_deal_weights_*, rs_deals_sample_weighted, rs_deal_trainer_set_weights) -- additions only: rs_deals_sample and a
+                                 trainer without weights launch the kernel they launched and deal the bits they dealt */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -305,7 +307,9 @@ int rs_node_report(rs_table *table, const rs_tree *tree, const uint8_t *board0, 
  * weights == NULL is the call without weights.  RS_ERR_INVALID for a weight that is NaN, infinite, zero or negative, a player's weight sum that is not finite, an unknown
  * `deal` and a non-zero `reserved`: refused before anything is allocated or written (`out` and the table are left alone).  A hand that is not in the range is left out of
  * the list, not given weight 0.  Duplicate combos stay allowed without RS_BR_SORTED (k copies of a hand = the hand with weight k) and refused with it.
- * The rs_deal_trainer_* forms stay unweighted: the sampled trainer draws its deals uniformly, and weighted sampling on the dealing stream is a later feature. */
+ * The sampled trainer deals from the same two distributions once rs_deal_trainer_set_weights has attached weights (before its first batch): the weights are quantised to
+ * integers (rs_deal_weights below), the device sampler draws exactly P with W = (double)q, and rs_deal_trainer_best_response, _node_report and _range_cfr then measure
+ * that game -- the one that is dealt.  Without weights the trainer deals and measures the unweighted game, as before. */
 enum { RS_DEAL_SEQUENTIAL = 0, RS_DEAL_JOINT = 1 };
 typedef struct rs_range_weights {
     const double *w[2];   /* [n_hands_p], host; NULL = 1.0 for every hand of that player */
@@ -730,6 +734,37 @@ int rs_card_abs_status(rs_card_abs *abs, rs_table *table);   /* synchronises; RS
 int rs_deals_sample(rs_table *table, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0,
                     uint32_t n_hands_p0, const uint8_t *d_hands_p1, uint32_t n_hands_p1, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err);
 
+/* ---- weighted dealing (an extension): rs_deals_sample with per-hand weights ---------------------------------------------------------
+ * The probabilities are ratios of integers, so a deal is a pure function of (seed, deal number, inputs).  rs_deal_weights holds, per player, the quanta q[i] and their
+ * inclusive prefix sums cum[i], on the host and (with a table) on the table's device.  table == NULL gives a host-only object: rs_deal_weights_quanta works, the
+ * sampler refuses it.  A NULL row = 1.0 for every hand.  With m the largest weight of a row, q[i] = (uint64_t)floor(w[i] / m * 4294967296.0 + 0.5) in IEEE f64, in
+ * that operation order: unit weights give 2^32 each, scaling a row by a power of two changes no bit, Q = sum q < 2^43.  RS_ERR_INVALID, before anything is allocated,
+ * for a weight that is NaN, infinite, zero or negative, a quantum that comes out 0 (the hand weighs less than 2^-33 of the largest: drop it from the range), n_p == 0
+ * or n_p > 1326, and an unknown `deal` (RS_DEAL_SEQUENTIAL or RS_DEAL_JOINT, above).
+ * A draw from a row: u uniform in [0, Q) by rand 0.7's widening multiply on a 64-bit word of the deal's counter hash (len = Q, zone = (Q << clz(Q)) - 1; a rejected
+ * word consumes its counter), the hand is the first index i with u < cum[i].  Counters k = 0, 1, ... of the deal:
+ *   RS_DEAL_SEQUENTIAL  the board is completed as rs_deals_sample does (same counters).  Then player 0, then player 1: up to RS_DEAL_WEIGHTED_TRIES words are spent on
+ *                       draws from the player's row -- a zone-rejected word counts as one of them, a hand that shares a card with anything dealt is rejected.  If none
+ *                       gives a hand the player is dealt exactly: Z = the sum of q over the hands that fit (Z == 0: the deal gives up), u' uniform in [0, Z) by the
+ *                       same widening multiply on the following words, the hand is the first fitting index whose running sum of fitting quanta exceeds u'.  Both
+ *                       branches draw from the same conditional law: P(b, h0, h1) = P(b) q0[h0] / Z0(b) * q1[h1] / Z1(b, h0) exactly, and a deal that exists is
+ *                       always dealt, however peaked the range.
+ *   RS_DEAL_JOINT       an attempt = the board completion, one draw for player 0 from its full row, one for player 1 from its full row (zone-rejected words are
+ *                       redrawn).  If either hand shares a card with the board or the hands share a card the WHOLE attempt is discarded and the next begins with
+ *                       fresh board cards on the next counters (redrawing the hands alone would not be the joint law).  Accepted deals have P = q0[h0] q1[h1] / Z
+ *                       over all deals; an attempt is accepted with probability Z / (Q0 Q1) (sum over run-outs of P(b) times the fitting mass), and there is no
+ *                       exact fallback: very peaked ranges that block each other run into the cap below.
+ * Both: at most 4096 words per deal (counter 4096 stays the prune draw); giving up raises bit 2 of the error word and writes the lowest nine free cards, as
+ * rs_deals_sample.  dw == NULL is rs_deals_sample, bit for bit; RS_ERR_INVALID for a dw without device rows, made for another device, or whose row lengths differ from
+ * n_hands_p0 / n_hands_p1.  The object must outlive every launch that reads it (rs_sync the table before destroying it). */
+#define RS_DEAL_WEIGHTED_TRIES 32
+typedef struct rs_deal_weights rs_deal_weights;
+int rs_deal_weights_create(rs_table *table /* may be NULL: host only */, const double *w0, size_t n0, const double *w1, size_t n1, int deal, rs_deal_weights **out);
+void rs_deal_weights_destroy(rs_deal_weights *dw);
+int rs_deal_weights_quanta(const rs_deal_weights *dw, int player, uint64_t *q /*[n_p]*/);
+int rs_deals_sample_weighted(rs_table *table, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
+                             const uint8_t *d_hands_p1, uint32_t n_hands_p1, const rs_deal_weights *dw, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err);
+
 /* train()'s per-deal prune decision (cfr.rs:213-221): d_flags[pitch] u8, 1 where deal number first_deal + i exceeds prune_threshold
  * (PRUNE_THRESHOLD = 10 000 000, cfr.rs:190) AND its `q: f32 = rng.gen()` -- counter 4096 of the deal's hash, after everything
  * generate_hand can draw -- is > 0.05.  Ready to be an rs_deal_batch.d_prune.  Asynchronous on the table's stream. */
@@ -786,6 +821,11 @@ int rs_deal_trainer_set_tick_br(rs_deal_trainer *trainer, int enable);
  * takes rs_dcfr_factors(alpha, beta, gamma, t / discount_interval) through rs_discount_dcfr instead of the one factor of cfr.rs:248-249 (only the exponents of `params`
  * are read).  i32, f32 and binary16 tables, with or without a communicator: the factors depend on t alone, every rank computes the same.  NULL: back to cfr.rs:248-261. */
 int rs_deal_trainer_set_dcfr(rs_deal_trainer *trainer, const rs_dcfr_params *params);
+/* Weighted hand ranges on the dealing stream (rs_range_weights and rs_deals_sample_weighted above).  Only before the first batch is dealt: RS_ERR_INVALID once a batch
+ * has been dealt or staged.  NULL: unweighted.  Every batch is then dealt by the weighted sampler, on whichever stream deals; deal numbers do not change, so ranks that
+ * set the same weights deal the union batch of one GPU.  rs_deal_trainer_best_response, _node_report and _range_cfr prepare their game with weights (double)q and the
+ * same `deal`; the prepared games kept from earlier calls are dropped here. */
+int rs_deal_trainer_set_weights(rs_deal_trainer *trainer, const rs_range_weights *weights);
 int rs_deal_trainer_last_br(const rs_deal_trainer *trainer, float *out /*[2]*/, uint64_t *iterations);
 int rs_deal_trainer_calc_br(rs_deal_trainer *trainer, float *out /*[2]*/);
 int rs_deal_trainer_best_response(rs_deal_trainer *trainer, int mode, double *out /*[2]*/);

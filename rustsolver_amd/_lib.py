@@ -239,6 +239,11 @@ SYMBOLS = {
     "rs_card_abs_status": (C.c_int, [_P, _P]),
     "rs_deals_sample": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "rs_deals_prune_flags": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _P]),
+    "rs_deal_weights_create": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, _PP]),
+    "rs_deal_weights_destroy": (None, [_P]),
+    "rs_deal_weights_quanta": (C.c_int, [_P, C.c_int, _P]),
+    "rs_deals_sample_weighted": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
+    "rs_deal_trainer_set_weights": (C.c_int, [_P, C.POINTER(RangeWeights)]),
     "rs_deal_trainer_create": (C.c_int, [_P, _PP, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(DealTrainerParams), C.c_int, _PP]),
     "rs_deal_trainer_destroy": (None, [_P]),
     "rs_deal_trainer_table": (C.c_void_p, [_P]),

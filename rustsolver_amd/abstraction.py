@@ -246,8 +246,51 @@ class CardAbstraction:
             pass
 
 
-def sample_deals(table, seed, first_deal, board_mask, hand_ranges, n_deals):
-    """generate_hand (cfr.rs:100-143) for n_deals deals on the GPU -> uint8 [9][n_deals]"""
+class DealWeights:
+    """rs_deal_weights: the integer quanta of a pair of weighted ranges (and, with a table, their prefix sums on its device).  weights = (w0, w1), either None = 1.0 for
+    every hand; n_hands = (n0, n1)"""
+
+    def __init__(self, table, weights, n_hands, deal="sequential"):
+        from .solver import DEALS
+        w = [None if row is None else np.ascontiguousarray(row, dtype=np.float64).reshape(-1) for row in weights]
+        for p in (0, 1):
+            if w[p] is not None and len(w[p]) != n_hands[p]:
+                raise ValueError("one weight per hand: %d weights for the %d hands of player %d" % (len(w[p]), n_hands[p], p))
+        h = C.c_void_p()
+        L.check(L.load().rs_deal_weights_create(None if table is None else table._h, None if w[0] is None else w[0].ctypes.data, n_hands[0],
+                                                None if w[1] is None else w[1].ctypes.data, n_hands[1], DEALS[deal] if isinstance(deal, str) else int(deal), C.byref(h)))
+        self._h, self.n_hands = h, tuple(int(n) for n in n_hands)
+
+    def quanta(self, player):
+        q = np.zeros(self.n_hands[player], dtype=np.uint64)
+        L.check(L.load().rs_deal_weights_quanta(self._h, player, q.ctypes.data))
+        return q
+
+    def destroy(self):
+        if self._h:
+            L.load().rs_deal_weights_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def deal_quanta(weights):
+    """the host quantisation of one row of range weights -> uint64 [n]: q[i] = floor(w[i] / max(w) * 2^32 + 0.5) (rs_deal_weights_create states the refusals)"""
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    dw = DealWeights(None, (w, None), (len(w), 1))
+    try:
+        return dw.quanta(0)
+    finally:
+        dw.destroy()
+
+
+def sample_deals(table, seed, first_deal, board_mask, hand_ranges, n_deals, weights=None, deal="sequential"):
+    """generate_hand (cfr.rs:100-143) for n_deals deals on the GPU -> uint8 [9][n_deals].  weights = (w0, w1), either None: rs_deals_sample_weighted under `deal`
+    ("sequential" or "joint"); weights=None with deal="sequential" is rs_deals_sample"""
     from .solver import DeviceBuffer, deal_pitch
     h0 = np.ascontiguousarray(hand_ranges[0], dtype=np.uint8).reshape(-1, 2)
     h1 = np.ascontiguousarray(hand_ranges[1], dtype=np.uint8).reshape(-1, 2)
@@ -257,7 +300,16 @@ def sample_deals(table, seed, first_deal, board_mask, hand_ranges, n_deals):
     dc.zero()
     de = DeviceBuffer(table, 4)
     de.zero()
-    L.check(L.load().rs_deals_sample(table._h, seed, first_deal, board_mask, d0.ptr, len(h0), d1.ptr, len(h1), n_deals, dc.ptr, de.ptr))
+    if weights is None and deal == "sequential":
+        L.check(L.load().rs_deals_sample(table._h, seed, first_deal, board_mask, d0.ptr, len(h0), d1.ptr, len(h1), n_deals, dc.ptr, de.ptr))
+    else:
+        dw = weights if isinstance(weights, DealWeights) else DealWeights(table, weights if weights is not None else (None, None), (len(h0), len(h1)), deal)
+        try:
+            L.check(L.load().rs_deals_sample_weighted(table._h, seed, first_deal, board_mask, d0.ptr, len(h0), d1.ptr, len(h1), dw._h, n_deals, dc.ptr, de.ptr))
+            table.sync()   # the launch reads dw's rows
+        finally:
+            if dw is not weights:
+                dw.destroy()
     err = int(de.download(np.uint32, 1)[0])
     if err:
         raise RuntimeError("generate_hand: no valid combo for some deal (error word %d)" % err)

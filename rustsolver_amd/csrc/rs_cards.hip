@@ -2,10 +2,12 @@
 //   * rs_hand_indexer: rust_poker::hand_indexer_s (init / size / get_index / get_hand) restated in rs_hand_index.hpp;
 //   * rs_card_abs: one round's ICardAbstraction (ISOMORPHIC / EMD / OCHS, card_abstraction.rs:31-298): generate_maps on the
 //     host at init, get_cluster for whole deal batches on the GPU (index -> bucket file gather -> dense id);
-//   * rs_deals_sample: generate_hand (cfr.rs:100-143) for a batch of deals.
+//   * rs_deals_sample: generate_hand (cfr.rs:100-143) for a batch of deals;
+//   * rs_deal_weights / rs_deals_sample_weighted: the same batch drawn from weighted ranges (integer quanta, prefix sums in LDS).
 // Integer work only; one thread per hand, card rows are SoA ([row][pitch] u8) so loads and stores coalesce.
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -379,12 +381,13 @@ __global__ __launch_bounds__(kBlock) void k_cluster_xlut(ClusterJob job, const u
 // draw*range is <= zone.
 constexpr uint32_t kSampleMaxDraws = 4096;   // every loop below ends: the reference would spin forever on an impossible range
 
-__device__ __forceinline__ void sample_deal(uint64_t seed, uint64_t deal, uint64_t board_mask, const uint8_t *__restrict__ hands0, uint32_t n0,
-                                            const uint8_t *__restrict__ hands1, uint32_t n1, uint8_t (&out)[9], bool &gave_up) {
-    uint64_t used = board_mask;
+// the missing board cards of one deal (cfr.rs:110-122) from counter k on: out[0 .. 5), `used` = their mask; returns the cards held (5 unless the counters ran out)
+// (put(i, card) stores card i: k_deal_sample keeps a byte array, the weighted kernel one packed word)
+template <class Put>
+__device__ __forceinline__ int complete_board(uint64_t seed, uint64_t deal, uint64_t board_mask, uint64_t &used, uint32_t &k, Put put) {
+    used = board_mask;
     int i = 0;
-    for (uint64_t m = board_mask; m; m &= m - 1) out[i++] = (uint8_t)__builtin_ctzll(m);   // :110-113 ascending
-    uint32_t k = 0;
+    for (uint64_t m = board_mask; m; m &= m - 1) put(i++, (uint8_t)__builtin_ctzll(m));   // :110-113 ascending
     const uint32_t zone52 = 0xffffffffu - (0xffffffffu - 52u + 1u) % 52u;
     while (i < 5 && k < kSampleMaxDraws) {
         const uint32_t v = (uint32_t)deal_bits(seed, deal, k++);
@@ -392,9 +395,28 @@ __device__ __forceinline__ void sample_deal(uint64_t seed, uint64_t deal, uint64
         if ((uint32_t)wide > zone52) continue;
         const uint32_t c = (uint32_t)(wide >> 32);
         if (used >> c & 1) continue;
-        out[i++] = (uint8_t)c;
+        put(i++, (uint8_t)c);
         used |= 1ull << c;
     }
+    return i;
+}
+
+// a deal that gave up: keep everything downstream in bounds with the lowest nine free cards
+__device__ __forceinline__ void lowest_free_cards(uint64_t board_mask, uint8_t (&out)[9]) {
+    uint64_t u = board_mask;
+    int j = __builtin_popcountll(board_mask);
+    for (uint32_t c = 0; c < 52 && j < 9; ++c)
+        if (!(u >> c & 1)) {
+            out[j++] = (uint8_t)c;
+            u |= 1ull << c;
+        }
+}
+
+__device__ __forceinline__ void sample_deal(uint64_t seed, uint64_t deal, uint64_t board_mask, const uint8_t *__restrict__ hands0, uint32_t n0,
+                                            const uint8_t *__restrict__ hands1, uint32_t n1, uint8_t (&out)[9], bool &gave_up) {
+    uint64_t used;
+    uint32_t k = 0;
+    int i = complete_board(seed, deal, board_mask, used, k, [&](int at, uint8_t c) { out[at] = c; });
     for (int p = 0; p < 2; ++p) {
         const uint8_t *hands = p == 0 ? hands0 : hands1;
         const uint64_t n = p == 0 ? n0 : n1;
@@ -415,14 +437,32 @@ __device__ __forceinline__ void sample_deal(uint64_t seed, uint64_t deal, uint64
         if (!done) i = -100;
     }
     gave_up = i != 5;
-    if (gave_up) {   // keep everything downstream in bounds: the lowest nine free cards
-        uint64_t u = board_mask;
-        int j = __builtin_popcountll(board_mask);
-        for (uint32_t c = 0; c < 52 && j < 9; ++c)
-            if (!(u >> c & 1)) {
-                out[j++] = (uint8_t)c;
-                u |= 1ull << c;
-            }
+    if (gave_up) lowest_free_cards(board_mask, out);
+}
+
+// what both dealing kernels do with a dealt lane: the error bit, the nine cards, and the trainer's fused form -- what k_showdown_sign and k_deal_prune_flags would compute
+// from the same cards / deal number
+__device__ __forceinline__ void deal_finish(uint64_t seed, uint64_t first_deal, uint32_t l, const uint8_t (&c)[9], bool gave_up, uint32_t pitch, uint8_t *__restrict__ cards,
+                                            uint32_t *__restrict__ err, float *__restrict__ sign, uint8_t *__restrict__ flags, uint64_t prune_threshold) {
+    if (gave_up) atomicOr(err, 4u);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cards[(size_t)i * pitch + l] = c[i];
+    if (sign) {
+        uint32_t m0[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 5; i++) add_card(m0, c[i]);
+        uint32_t m1[4] = {m0[0], m0[1], m0[2], m0[3]};
+        add_card(m0, c[5]);
+        add_card(m0, c[6]);
+        add_card(m1, c[7]);
+        add_card(m1, c[8]);
+        const uint32_t s0 = evaluate_suits(m0), s1 = evaluate_suits(m1);
+        sign[l] = s0 == s1 ? 0.0f : (s0 > s1 ? 1.0f : -1.0f);   // cfr.rs:326-333
+    }
+    if (flags) {
+        const uint64_t deal = first_deal + l;
+        const float q = (float)((uint32_t)deal_bits(seed, deal, kSampleMaxDraws) >> 8) * 5.9604644775390625e-08f;
+        flags[l] = (deal > prune_threshold && q > 0.05f) ? 1 : 0;   // cfr.rs:213-221
     }
 }
 
@@ -434,27 +474,161 @@ __global__ __launch_bounds__(kBlock) void k_deal_sample(uint64_t seed, uint64_t 
         uint8_t c[9];
         bool gave_up;
         sample_deal(seed, first_deal + l, board_mask, hands0, n0, hands1, n1, c, gave_up);
-        if (gave_up) atomicOr(err, 4u);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) cards[(size_t)i * pitch + l] = c[i];
-        // the trainer's fused form: what k_showdown_sign and k_deal_prune_flags would compute from the same cards / deal number
-        if (sign) {
-            uint32_t m0[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 5; i++) add_card(m0, c[i]);
-            uint32_t m1[4] = {m0[0], m0[1], m0[2], m0[3]};
-            add_card(m0, c[5]);
-            add_card(m0, c[6]);
-            add_card(m1, c[7]);
-            add_card(m1, c[8]);
-            const uint32_t s0 = evaluate_suits(m0), s1 = evaluate_suits(m1);
-            sign[l] = s0 == s1 ? 0.0f : (s0 > s1 ? 1.0f : -1.0f);   // cfr.rs:326-333
+        deal_finish(seed, first_deal, l, c, gave_up, pitch, cards, err, sign, flags, prune_threshold);
+    }
+}
+
+// ---- weighted dealing (rs_deal_weights; the header states both distributions) --------------------------------------------------------------------------------------
+// One row of a player in LDS: the inclusive prefix sums of its quanta and its combos (low byte = first card).
+struct WeightedRow {
+    const uint64_t *cum;
+    const uint16_t *hands;
+    uint32_t n;
+    uint64_t Q, zone;   // cum[n - 1] and rand 0.7's acceptance zone for a range of Q
+};
+
+// the first index i with u < cum[i], for u < cum[n - 1]: a binary search, 11 LDS reads at 1326 hands
+__device__ __forceinline__ uint32_t weighted_pick(const uint64_t *cum, uint32_t n, uint64_t u) {
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u < cum[mid]) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// one word spent on a draw from `row`: false when the word is zone-rejected
+__device__ __forceinline__ bool weighted_draw(const WeightedRow &row, uint64_t v, uint32_t &idx) {
+    if (v * row.Q > row.zone) return false;
+    idx = weighted_pick(row.cum, row.n, __umul64hi(v, row.Q));
+    return true;
+}
+
+__device__ __forceinline__ uint64_t combo_mask(uint16_t h) { return 1ull << (h & 0xffu) | 1ull << (h >> 8); }
+
+// RS_DEAL_SEQUENTIAL, one player: up to RS_DEAL_WEIGHTED_TRIES words by rejection against `used`, then the exact draw among the hands that fit.  false: no hand fits
+__device__ __forceinline__ bool deal_player_sequential(uint64_t seed, uint64_t deal, const WeightedRow &row, uint64_t used, uint32_t &k, uint16_t &hand) {
+    uint32_t idx = 0;
+    bool done = false;
+    for (uint32_t tries = 0; !done && tries < RS_DEAL_WEIGHTED_TRIES && k < kSampleMaxDraws; ++tries)
+        done = weighted_draw(row, deal_bits(seed, deal, k++), idx) && !(combo_mask(row.hands[idx]) & used);
+    if (!done) {   // rare and divergent: two walks over the row
+        uint64_t Z = 0, prev = 0;
+        for (uint32_t i = 0; i < row.n; ++i) {
+            const uint64_t c = row.cum[i];
+            if (!(combo_mask(row.hands[i]) & used)) Z += c - prev;
+            prev = c;
         }
-        if (flags) {
-            const uint64_t deal = first_deal + l;
-            const float q = (float)((uint32_t)deal_bits(seed, deal, kSampleMaxDraws) >> 8) * 5.9604644775390625e-08f;
-            flags[l] = (deal > prune_threshold && q > 0.05f) ? 1 : 0;   // cfr.rs:213-221
+        if (Z != 0) {
+            const uint64_t zone = (Z << __builtin_clzll(Z)) - 1;
+            uint64_t u = 0;
+            bool have = false;
+            while (!have && k < kSampleMaxDraws) {
+                const uint64_t v = deal_bits(seed, deal, k++);
+                have = v * Z <= zone;
+                u = __umul64hi(v, Z);
+            }
+            uint64_t run = 0;
+            prev = 0;
+            for (uint32_t i = 0; have && !done && i < row.n; ++i) {
+                const uint64_t c = row.cum[i];
+                if (!(combo_mask(row.hands[i]) & used)) {
+                    run += c - prev;
+                    if (run > u) {
+                        idx = i;
+                        done = true;
+                    }
+                }
+                prev = c;
+            }
         }
+    }
+    if (done) hand = row.hands[idx];
+    return done;
+}
+
+// A weighted deal is built in one word -- card i in byte i of `board` (5 cards), the two hands as u16 -- so that no store has a run-time index (a byte array written at
+// i++ inside these loops went to scratch).  Returns whether the deal was dealt.
+__device__ __forceinline__ int complete_board_packed(uint64_t seed, uint64_t deal, uint64_t board_mask, uint64_t &used, uint32_t &k, uint64_t &board) {
+    board = 0;
+    return complete_board(seed, deal, board_mask, used, k, [&](int at, uint8_t c) { board |= (uint64_t)c << (8 * at); });
+}
+
+__device__ __forceinline__ bool sample_deal_sequential(uint64_t seed, uint64_t deal, uint64_t board_mask, const WeightedRow &row0, const WeightedRow &row1, uint64_t &board,
+                                                       uint16_t &h0, uint16_t &h1) {
+    uint64_t used;
+    uint32_t k = 0;
+    return complete_board_packed(seed, deal, board_mask, used, k, board) == 5 && deal_player_sequential(seed, deal, row0, used, k, h0) &&
+           deal_player_sequential(seed, deal, row1, used | combo_mask(h0), k, h1);
+}
+
+// RS_DEAL_JOINT, one player: a hand from the full row, zone-rejected words redrawn.  false: the counters ran out
+__device__ __forceinline__ bool deal_player_joint(uint64_t seed, uint64_t deal, const WeightedRow &row, uint32_t &k, uint16_t &hand) {
+    uint32_t idx = 0;
+    bool drawn = false;
+    while (!drawn && k < kSampleMaxDraws) drawn = weighted_draw(row, deal_bits(seed, deal, k++), idx);
+    if (drawn) hand = row.hands[idx];
+    return drawn;
+}
+
+// whole attempts (board, one hand per player from its full row) until one is a deal
+__device__ __forceinline__ bool sample_deal_joint(uint64_t seed, uint64_t deal, uint64_t board_mask, const WeightedRow &row0, const WeightedRow &row1, uint64_t &board,
+                                                  uint16_t &h0, uint16_t &h1) {
+    uint32_t k = 0;
+    while (k < kSampleMaxDraws) {
+        uint64_t used;
+        if (complete_board_packed(seed, deal, board_mask, used, k, board) != 5) return false;
+        if (!deal_player_joint(seed, deal, row0, k, h0) || !deal_player_joint(seed, deal, row1, k, h1)) return false;
+        const uint64_t m0 = combo_mask(h0), m1 = combo_mask(h1);
+        if (!(m0 & used) && !(m1 & used) && !(m0 & m1)) return true;
+    }
+    return false;
+}
+
+// k_deal_sample with a distribution.  Each workgroup stages both rows of prefix sums (8 B a hand) and both hand lists (2 B a hand) in LDS once -- 26 520 bytes at two full
+// ranges -- and every draw after that reads LDS alone.  lds: cum0[n0], cum1[n1], then hands0[n0], hands1[n1] as u16.
+__global__ __launch_bounds__(kBlock) void k_deal_sample_weighted(uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *__restrict__ hands0, uint32_t n0,
+                                                                 const uint8_t *__restrict__ hands1, uint32_t n1, const uint64_t *__restrict__ cum0,
+                                                                 const uint64_t *__restrict__ cum1, int joint, uint32_t n, uint32_t pitch, uint8_t *__restrict__ cards,
+                                                                 uint32_t *__restrict__ err, float *__restrict__ sign, uint8_t *__restrict__ flags, uint64_t prune_threshold) {
+    extern __shared__ uint64_t weighted_lds[];
+    uint64_t *l_cum0 = weighted_lds, *l_cum1 = weighted_lds + n0;
+    uint16_t *l_h0 = reinterpret_cast<uint16_t *>(weighted_lds + n0 + n1), *l_h1 = l_h0 + n0;
+    for (uint32_t i = threadIdx.x; i < n0; i += kBlock) {
+        l_cum0[i] = cum0[i];
+        l_h0[i] = (uint16_t)(hands0[2 * i] | hands0[2 * i + 1] << 8);
+    }
+    for (uint32_t i = threadIdx.x; i < n1; i += kBlock) {
+        l_cum1[i] = cum1[i];
+        l_h1[i] = (uint16_t)(hands1[2 * i] | hands1[2 * i + 1] << 8);
+    }
+    __syncthreads();
+    const uint64_t Q0 = l_cum0[n0 - 1], Q1 = l_cum1[n1 - 1];
+    const WeightedRow row0 = {l_cum0, l_h0, n0, Q0, (Q0 << __builtin_clzll(Q0)) - 1}, row1 = {l_cum1, l_h1, n1, Q1, (Q1 << __builtin_clzll(Q1)) - 1};
+    for (uint32_t l = blockIdx.x * kBlock + threadIdx.x; l < n; l += gridDim.x * kBlock) {
+        uint64_t board = 0;
+        uint16_t h0 = 0, h1 = 0;
+        const bool dealt = joint ? sample_deal_joint(seed, first_deal + l, board_mask, row0, row1, board, h0, h1)
+                                 : sample_deal_sequential(seed, first_deal + l, board_mask, row0, row1, board, h0, h1);
+        uint8_t c[9];
+        if (dealt) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) c[i] = (uint8_t)(board >> (8 * i));
+            c[5] = (uint8_t)(h0 & 0xffu);
+            c[6] = (uint8_t)(h0 >> 8);
+            c[7] = (uint8_t)(h1 & 0xffu);
+            c[8] = (uint8_t)(h1 >> 8);
+        } else {   // the lowest nine free cards, board first (lowest_free_cards with constant indices)
+            uint64_t left = board_mask, free_cards = ~board_mask;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                uint64_t &from = left ? left : free_cards;
+                c[i] = (uint8_t)__builtin_ctzll(from);
+                from &= from - 1;
+            }
+        }
+        deal_finish(seed, first_deal, l, c, !dealt, pitch, cards, err, sign, flags, prune_threshold);
     }
 }
 
@@ -1035,5 +1209,123 @@ int deals_sample_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t fir
                        n_hands_p1, n_deals, uint32_t(round_up(n_deals, kLanePad)), d_cards, d_err, d_sign, d_flags, prune_threshold);
     RS_HIP(hipGetLastError(), "k_deal_sample");
     return RS_OK;
+}
+}  // namespace rs
+
+// ---- weighted dealing: the quanta of a pair of ranges (host), their prefix sums on the device, and k_deal_sample_weighted --------------------------------------------
+struct rs_deal_weights {
+    int deal = RS_DEAL_SEQUENTIAL;
+    int device = -1;                       // -1: host only (made without a table)
+    std::vector<uint64_t> q[2], cum[2];    // quanta and their inclusive prefix sums
+    rs::DevBuf<uint64_t> d_cum[2];
+};
+
+extern "C" {
+int rs_deal_weights_create(rs_table *t, const double *w0, size_t n0, const double *w1, size_t n1, int deal, rs_deal_weights **out) {
+    if (!out) return fail(RS_ERR_INVALID, "rs_deal_weights_create: NULL argument");
+    if (deal != RS_DEAL_SEQUENTIAL && deal != RS_DEAL_JOINT) return fail(RS_ERR_INVALID, "rs_range_weights: deal is RS_DEAL_SEQUENTIAL or RS_DEAL_JOINT");
+    const double *w[2] = {w0, w1};
+    const size_t n[2] = {n0, n1};
+    std::vector<uint64_t> q[2], cum[2];
+    for (int p = 0; p < 2; ++p) {
+        if (n[p] == 0 || n[p] > 1326) return fail(RS_ERR_INVALID, "rs_deal_weights_create: 1..1326 hands per range");
+        double m = 1.0;
+        if (w[p]) {
+            m = 0.0;
+            for (size_t h = 0; h < n[p]; ++h) {
+                const double x = w[p][h];
+                if (!(x > 0.0) || !std::isfinite(x))
+                    return fail(RS_ERR_INVALID, "rs_range_weights: weight " + std::to_string(h) + " of player " + std::to_string(p) +
+                                                    " is not finite and > 0 (a hand that is not in the range is left out of the list)");
+                m = std::max(m, x);
+            }
+        }
+        q[p].resize(n[p]);
+        cum[p].resize(n[p]);
+        uint64_t sum = 0;
+        for (size_t h = 0; h < n[p]; ++h) {
+            const double x = w[p] ? w[p][h] : 1.0;
+            const uint64_t qh = (uint64_t)std::floor(x / m * 4294967296.0 + 0.5);
+            if (qh == 0)
+                return fail(RS_ERR_INVALID, "rs_deal_weights_create: weight " + std::to_string(h) + " of player " + std::to_string(p) +
+                                                " is below 2^-33 of the player's largest and quantises to 0 (drop the hand from the range)");
+            q[p][h] = qh;
+            cum[p][h] = sum += qh;
+        }
+    }
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate): the upload below synchronises
+    rs_deal_weights *dw = new (std::nothrow) rs_deal_weights();
+    if (!dw) return fail(RS_ERR_OOM, "rs_deal_weights_create: out of memory");
+    dw->deal = deal;
+    for (int p = 0; p < 2; ++p) dw->q[p] = std::move(q[p]), dw->cum[p] = std::move(cum[p]);
+    if (t) {
+        hipError_t e = hipSetDevice(t->device);
+        for (int p = 0; p < 2 && e == hipSuccess; ++p) {
+            e = dw->d_cum[p].alloc(n[p]);
+            if (e == hipSuccess) e = hipMemcpy(dw->d_cum[p], dw->cum[p].data(), n[p] * sizeof(uint64_t), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            delete dw;
+            return hip_fail(e, "rs_deal_weights_create");
+        }
+        dw->device = t->device;
+    }
+    *out = dw;
+    return RS_OK;
+}
+
+void rs_deal_weights_destroy(rs_deal_weights *dw) { delete dw; }
+
+int rs_deal_weights_quanta(const rs_deal_weights *dw, int player, uint64_t *q) {
+    if (!dw || !q || player < 0 || player > 1) return fail(RS_ERR_INVALID, "rs_deal_weights_quanta: NULL argument or a player that is not 0 or 1");
+    std::copy(dw->q[player].begin(), dw->q[player].end(), q);
+    return RS_OK;
+}
+
+int rs_deals_sample_weighted(rs_table *t, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
+                             const uint8_t *d_hands_p1, uint32_t n_hands_p1, const rs_deal_weights *dw, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err) {
+    if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
+    return rs::deals_sample_weighted_on(t, t ? t->stream : nullptr, seed, first_deal, board_mask, d_hands_p0, n_hands_p0, d_hands_p1, n_hands_p1, dw, n_deals, d_cards,
+                                        d_err, nullptr, nullptr, 0);
+}
+}  // extern "C"
+
+namespace rs {
+// every workgroup stages the rows once, so the grid stops at what a full-range launch keeps resident: 5 workgroups of 26.5 KB LDS on each of 256 CUs
+constexpr uint32_t kWeightedMaxGrid = 1280;
+
+int deals_sample_weighted_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
+                             const uint8_t *d_hands_p1, uint32_t n_hands_p1, const rs_deal_weights *dw, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err, float *d_sign,
+                             uint8_t *d_flags, uint64_t prune_threshold) {
+    if (!dw)
+        return deals_sample_on(t, stream, seed, first_deal, board_mask, d_hands_p0, n_hands_p0, d_hands_p1, n_hands_p1, n_deals, d_cards, d_err, d_sign, d_flags,
+                               prune_threshold);
+    if (!t || !d_hands_p0 || !d_hands_p1 || !d_cards) return fail(RS_ERR_INVALID, "rs_deals_sample_weighted: NULL argument");
+    if (dw->device != t->device) return fail(RS_ERR_INVALID, "rs_deals_sample_weighted: the weights were not made for this table's device");
+    if (dw->q[0].size() != n_hands_p0 || dw->q[1].size() != n_hands_p1)
+        return fail(RS_ERR_INVALID, "rs_deals_sample_weighted: the weights were made for " + std::to_string(dw->q[0].size()) + " and " + std::to_string(dw->q[1].size()) +
+                                        " hands, the ranges have " + std::to_string(n_hands_p0) + " and " + std::to_string(n_hands_p1));
+    if (board_mask >> 52) return fail(RS_ERR_INVALID, "rs_deals_sample: board mask has bits beyond card 51");
+    const int n_board = __builtin_popcountll(board_mask);
+    if (n_board < 3 || n_board > 5) return fail(RS_ERR_INVALID, "invalid board mask");   // options.rs:41
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    if (!d_err) {
+        if (!t->d_err_sink) RS_HIP(t->d_err_sink.alloc(1), "rs_deals_sample: error word");
+        d_err = t->d_err_sink;   // nobody reads it
+    }
+    if (n_deals == 0) return RS_OK;
+    const size_t lds = round_up(size_t(n_hands_p0 + n_hands_p1) * (sizeof(uint64_t) + sizeof(uint16_t)), sizeof(uint64_t));   // at most 26 520 bytes (1326 hands each)
+    const dim3 grid(std::max(1u, std::min((n_deals + kBlock - 1) / kBlock, kWeightedMaxGrid)));
+    hipLaunchKernelGGL(k_deal_sample_weighted, grid, dim3(kBlock), lds, stream, seed, first_deal, board_mask, d_hands_p0, n_hands_p0, d_hands_p1, n_hands_p1,
+                       (const uint64_t *)dw->d_cum[0], (const uint64_t *)dw->d_cum[1], dw->deal == RS_DEAL_JOINT ? 1 : 0, n_deals, uint32_t(round_up(n_deals, kLanePad)),
+                       d_cards, d_err, d_sign, d_flags, prune_threshold);
+    RS_HIP(hipGetLastError(), "k_deal_sample_weighted");
+    return RS_OK;
+}
+
+// the weights a prepared game takes for what `dw` deals: (double)q per hand, exact (q <= 2^32)
+void deal_weights_as_doubles(const rs_deal_weights *dw, std::vector<double> (&w)[2], int *deal) {
+    for (int p = 0; p < 2; ++p) w[p].assign(dw->q[p].begin(), dw->q[p].end());
+    *deal = dw->deal;
 }
 }  // namespace rs

@@ -518,6 +518,11 @@ int card_abs_clusters_on(rs_card_abs *abs, rs_table *t, hipStream_t stream, cons
 int deals_sample_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
                     const uint8_t *d_hands_p1, uint32_t n_hands_p1, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err, float *d_sign /* fused showdown signs, may be null */,
                     uint8_t *d_flags /* fused per-deal prune flags, may be null */, uint64_t prune_threshold);
+// ... with per-hand weights (rs_deal_weights, rs_cards.hip); dw == nullptr is deals_sample_on
+int deals_sample_weighted_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t first_deal, uint64_t board_mask, const uint8_t *d_hands_p0, uint32_t n_hands_p0,
+                             const uint8_t *d_hands_p1, uint32_t n_hands_p1, const rs_deal_weights *dw, uint32_t n_deals, uint8_t *d_cards, uint32_t *d_err, float *d_sign,
+                             uint8_t *d_flags, uint64_t prune_threshold);
+void deal_weights_as_doubles(const rs_deal_weights *dw, std::vector<double> (&w)[2], int *deal);   // (double)q of both players and the RS_DEAL_* mode
 int deal_prune_flags_on(rs_table *t, hipStream_t stream, uint64_t seed, uint64_t first_deal, uint64_t prune_threshold, uint32_t n_deals, uint8_t *d_flags);
 int table_copy_node_raw(rs_table *t, int node, int which /* 0 regrets, 1 strategy_sum */, void *host /* [A][lanes], table element type */, int dir /* 0 up, 1 down */);
 void solver_release_device(struct rs_solver *s);   // frees a solver's device state and detaches it from its table

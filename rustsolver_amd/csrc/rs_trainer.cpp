@@ -46,6 +46,11 @@ struct rs_deal_trainer {
     float last_br[2] = {0.0f, 0.0f};
     uint64_t last_br_t = 0;
     bool have_br = false;
+    // weighted hand ranges (rs_deal_trainer_set_weights): what deal_into samples from, and the same game as rs_range_weights ((double)q) for the measuring calls
+    rs_deal_weights *deal_weights = nullptr;
+    std::vector<double> br_w[2];
+    rs_range_weights br_weights{};
+    const rs_range_weights *game_weights() const { return deal_weights ? &br_weights : nullptr; }
     uint32_t world = 1, rank = 0;  // data-parallel training: this rank's share of every global batch
     // The NEXT batch is dealt (sample -> clusters -> showdown) into staging buffers on a second stream while the current one is swept -- the
     // sweep kernels leave most wave slots of a CU idle -- and swapped in with device-to-device copies.  Same deal numbers, same results.
@@ -80,6 +85,7 @@ void rs_deal_trainer_destroy(rs_deal_trainer *tr) {
     if (tr->deal_stream) (void)hipStreamSynchronize(tr->deal_stream);   // a sort dealt ahead may still be writing the solver's records
     if (tr->solver) rs_solver_destroy(tr->solver);
     if (tr->table) (void)rs_sync(tr->table);   // nothing on the table's stream uses the trainer's buffers any more
+    rs_deal_weights_destroy(tr->deal_weights);
     rs_table *table = tr->table;
     rs_tree *tree = tr->tree;
     delete tr;   // its buffers, events and dealing stream, before the table they were made for
@@ -295,8 +301,9 @@ static int deal_into(rs_deal_trainer *tr, hipStream_t stream, uint8_t *cards, co
     *first = first_deal;
     // one launch deals the cards, compares the two hands (cfr.rs:323-333) and -- when dealing straight into the live buffers -- draws the prune flags
     const bool live = cards == tr->d_cards;
-    if (int rc = deals_sample_on(tr->table, stream, tr->params.seed, first_deal, tr->params.board_mask, tr->d_hands[0], tr->n_hands[0], tr->d_hands[1],
-                                 tr->n_hands[1], n, cards, tr->d_err, sign, live ? tr->d_prune : (tr->ahead ? tr->s_prune : nullptr), tr->params.prune_threshold))
+    if (int rc = deals_sample_weighted_on(tr->table, stream, tr->params.seed, first_deal, tr->params.board_mask, tr->d_hands[0], tr->n_hands[0], tr->d_hands[1],
+                                          tr->n_hands[1], tr->deal_weights, n, cards, tr->d_err, sign, live ? tr->d_prune : (tr->ahead ? tr->s_prune : nullptr),
+                                          tr->params.prune_threshold))
         return rc;
     for (int r = 0; r < tr->n_rounds; ++r)
         if (int rc = card_abs_clusters_on(tr->abs[r], tr->table, stream, cards, n, cluster[r][0], cluster[r][1])) return rc;
@@ -504,7 +511,7 @@ int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
     const int which = (mode & RS_BR_SORTED) ? 1 : 0;
     if (!tr->br_prepared[which])
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, nullptr, &tr->br_prepared[which]))
+                                    which == 1, tr->game_weights(), &tr->br_prepared[which]))
             return rc;
     return rs::br_execute(tr->br_prepared[which], mode & ~RS_BR_SORTED, out);
 }
@@ -519,7 +526,7 @@ int rs_deal_trainer_node_report(rs_deal_trainer *tr, int mode, int traverser, co
     const int which = (mode & RS_BR_SORTED) ? 1 : 0;
     if (!tr->br_prepared[which])
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, nullptr, &tr->br_prepared[which]))
+                                    which == 1, tr->game_weights(), &tr->br_prepared[which]))
             return rc;
     return rs::br_report(tr->br_prepared[which], mode & ~RS_BR_SORTED, traverser, nodes, n_nodes, out, out_doubles);
 }
@@ -539,7 +546,7 @@ int rs_deal_trainer_range_cfr(rs_deal_trainer *tr, uint64_t iterations, const rs
     if (!tr->cfr_prepared[which]) {
         rs::BrRun *run = nullptr;
         if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, nullptr, &run))
+                                    which == 1, tr->game_weights(), &run))
             return rc;
         if (int rc = rs::br_cfr_mark(run)) {
             rs::br_free(run);
@@ -566,6 +573,33 @@ int rs_deal_trainer_br_release(rs_deal_trainer *tr) {
 }
 int rs_deal_trainer_br_launches(const rs_deal_trainer *tr, int sorted) {   // launches of the last best-response call (level plan), -1: depth-first walk or no call yet
     return tr ? rs::br_last_launches(tr->br_prepared[sorted ? 1 : 0]) : -1;
+}
+
+// weighted hand ranges on the dealing stream: only while no batch has been dealt or staged (every batch of a trainer comes from one distribution)
+int rs_deal_trainer_set_weights(rs_deal_trainer *tr, const rs_range_weights *weights) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
+    if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_weights: trainer is NULL");
+    if (tr->batches > 0 || tr->staged) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_weights: attach the weights before the trainer's first batch");
+    if (int rc = rs::br_check_weights(weights, tr->n_hands[0], tr->n_hands[1])) return rc;
+    rs_deal_weights *dw = nullptr;
+    if (weights)
+        if (int rc = rs_deal_weights_create(tr->table, weights->w[0], tr->n_hands[0], weights->w[1], tr->n_hands[1], weights->deal, &dw)) return rc;
+    for (int k = 0; k < 2; ++k) {   // the prepared games were made for the distribution before
+        if (tr->br_prepared[k]) rs::br_free(tr->br_prepared[k]);
+        if (tr->cfr_prepared[k]) rs::br_free(tr->cfr_prepared[k]);
+        tr->br_prepared[k] = tr->cfr_prepared[k] = nullptr;
+    }
+    rs_deal_weights_destroy(tr->deal_weights);
+    tr->deal_weights = dw;
+    tr->br_weights = rs_range_weights{};
+    if (dw) {
+        int deal = RS_DEAL_SEQUENTIAL;
+        rs::deal_weights_as_doubles(dw, tr->br_w, &deal);
+        tr->br_weights.w[0] = tr->br_w[0].data();
+        tr->br_weights.w[1] = tr->br_w[1].data();
+        tr->br_weights.deal = deal;
+    }
+    return RS_OK;
 }
 
 int rs_deal_trainer_attach_comm(rs_deal_trainer *tr, rs_comm *comm) {

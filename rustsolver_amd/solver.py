@@ -813,8 +813,12 @@ class DealTrainer:
 
     def __init__(self, tree, card_abs, hand_ranges, board_mask, deals_per_batch, seed=0, scale=100.0, mode=L.UPD_CLAMP_I64,
                  opp_mode=L.OPP_SAMPLE, discount_interval=MCCFRTrainer.DISCOUNT_INTERVAL, discount_cap=MCCFRTrainer.DISCOUNT_CAP,
-                 use_graph=False, fuse_subtrees=None, device=0, world=1, rank=0, prune_threshold=10_000_000, forms=None, prefetch=None, dtype=L.I32):
-        """prune_threshold: cfr.rs:190 PRUNE_THRESHOLD (None = never prune).  forms: rs_kernel_forms fields by name, as for MCCFRTrainer.  world / rank: data-parallel training on replicated tables (one process per GPU): this rank deals its share of every global
+                 use_graph=False, fuse_subtrees=None, device=0, world=1, rank=0, prune_threshold=10_000_000, forms=None, prefetch=None, dtype=L.I32,
+                 weights=None, deal="sequential"):
+        """weights = (w0, w1), either None: per-hand range weights the deals are drawn with (rs_deal_trainer_set_weights; deal: "sequential" or "joint", as
+        InfosetTable.best_response_rounds); best_response(), node_report() and train_full_width() then work on the weighted game.  A weight of exactly 0.0 raises ValueError: drop
+        the hand from the range before the card abstractions are built, they are made from the same lists.
+        prune_threshold: cfr.rs:190 PRUNE_THRESHOLD (None = never prune).  forms: rs_kernel_forms fields by name, as for MCCFRTrainer.  world / rank: data-parallel training on replicated tables (one process per GPU): this rank deals its share of every global
         batch; attach_comm() makes every rank apply the deltas of the union batch."""
         if fuse_subtrees is None:
             fuse_subtrees = bool(L.load().rs_jit_available())
@@ -841,6 +845,20 @@ class DealTrainer:
         self.n_deals = deals_per_batch
         self._n_hands, self._n_board0 = (len(h0), len(h1)), bin(board_mask).count("1")
         self.infosets = InfosetTable(C.c_void_p(L.load().rs_deal_trainer_table(h)), owned=False)
+        if weights is not None or deal != "sequential":
+            self.set_weights(weights, deal)
+
+    def set_weights(self, weights, deal="sequential"):
+        """rs_deal_trainer_set_weights: only before the first batch.  weights=None with deal="sequential": back to unweighted dealing"""
+        w = [None, None]
+        for p, row in enumerate(weights if weights is not None else (None, None)):
+            if row is not None:
+                w[p] = np.ascontiguousarray(row, dtype=np.float64).reshape(-1)
+                if len(w[p]) != self._n_hands[p]:
+                    raise ValueError("one weight per hand: %d weights for the %d hands of player %d" % (len(w[p]), self._n_hands[p], p))
+                if (w[p] == 0.0).any():
+                    raise ValueError("a hand of weight 0.0 is not in the range: drop it from the hand list (and build the card abstractions from that list)")
+        L.check(L.load().rs_deal_trainer_set_weights(self._h, _range_weights(w, deal)))
 
     def train(self, n_batches):
         L.check(L.load().rs_deal_trainer_train(self._h, n_batches))
