@@ -963,6 +963,8 @@ int rs_ehs_preflop_counts(rs_table *table, int n_bins, const uint8_t *d_boards, 
  *                              otherwise:      tot[j] += target[j] * d;  rem[t] = a - target[j];  target[j] = 0;  done[j] = true
  *                          dist = ((0.0f + tot[0]) + tot[1]) + ... + tot[m - 1]
  *                      The per-entry totals summed in entry order are this library's choice (the paper keeps one running total).  Neither symmetric nor a metric.
+ *                      `a > 0` is the IEEE f32 comparison, on the device as on the host: a subnormal is positive and is taken from, -0.0 is not; nothing is flushed to
+ *                      zero.  A total may overflow to +inf (never to NaN: no ground entry is infinite); among means at +inf the first is chosen, as among any equals.
  *   k-means            assignment = the first mean with the strictly smallest distance (rs_kmeans_predict's rule).  One Lloyd iteration: assign every datum;
  *                      changed = the data whose cluster differs from the iteration before (before the first: none, so changed[0] = n); for every cluster k with
  *                      members: mean[k][b] = (float)((double)sum[k][b] / ((double)members[k] * (double)n_draws)), sum = the integer sum of its members' counts; a

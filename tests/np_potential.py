@@ -115,9 +115,10 @@ def order_of(ground):
     return np.argsort(np.asarray(ground, dtype=F32), axis=1, kind="stable")
 
 
-def distances(rows, means, ground, n_draws, exits=True, order=None, ranks=None):
+def distances(rows, means, ground, n_draws, exits=True, order=None, ranks=None, trace=None):
     """rows uint32 [P][ROW_WORDS], means float32 [P][n_next], pair by pair -> float32 [P].  exits: stop once, in every pair, every entry is done or no bucket is
-    positive.  ranks (a list): gets the number of ranks walked"""
+    positive.  ranks (a list): gets the number of ranks walked.  trace (a list): gets (pair, rank, entry) for every take, in the order of the definition; it only
+    listens.  A value is positive if it is above 0 in IEEE f32: a subnormal is, -0.0 is not"""
     rows = np.asarray(rows, dtype=np.uint32).reshape(-1, ROW_WORDS)
     ground = np.asarray(ground, dtype=F32)
     n = ground.shape[0]
@@ -144,6 +145,8 @@ def distances(rows, means, ground, n_draws, exits=True, order=None, ranks=None):
             at, b, t, a = at[pos], b[pos], t[pos], a[pos]
             if not len(at):
                 continue
+            if trace is not None:
+                trace.extend((int(p), i, j) for p in at)
             d = ground[b, t]
             tj = target[at, j]
             part = a < tj

@@ -12,6 +12,7 @@ from rustsolver_amd import abstraction as ab
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import np_potential as npp  # noqa: E402
+import potential_edge_inputs as pe  # noqa: E402
 
 F32 = np.float32
 SIZES = [1, 2, 3, 7, 64, 65, 300]
@@ -126,6 +127,56 @@ def test_the_host_distance_equals_the_restatement(cases, n_next, which):
 
 def test_the_cases_are_about_two_thousand_pairs(cases):
     assert sum(len(c[2]) for c in cases.values()) == 2120
+
+
+# ---- ranks above 511, the values at the edges: the inputs test_gpu_potential_edges.py runs on the device (tests/potential_edge_inputs.py) ---------------------------
+def test_a_trace_only_listens(cases):
+    ground, n_draws, rows, means, want = cases[(65, "random")]
+    trace = []
+    assert (bits(npp.distances(rows, means, ground, n_draws, trace=trace)) == bits(want)).all()
+    assert len(trace) > len(rows) and all(0 <= p < len(rows) and 0 <= r < 65 and rows[p, e] != 0 for p, r, e in trace)
+    for pair in (0, 1, 2, len(rows) - 1):            # one pair's takes come in the definition's order: by rank, then by entry
+        own = [(r, e) for p, r, e in trace if p == pair]
+        assert own == sorted(own) and len(set(own)) == len(own) > 0
+    facts = pe.rank_facts([(0, 600, 1), (0, 1030, 0), (1, 600, 1), (1, 1030, 1), (2, 100, 0), (2, 513, 1), (3, 1023, 0), (3, 1024, 1), (3, 5000, 1)])
+    assert facts == ([0, 3], 5000)                   # pair 1: one entry; pair 2: the first take is below 512
+
+
+@pytest.mark.parametrize("n_next,which", pe.HIGH_RANK_CASES)
+def test_the_high_rank_inputs_hold_their_premises(n_next, which):
+    c = pe.high_rank_case(n_next, which)
+    entries = (c["rows"] != 0).sum(axis=1)
+    assert all(npp.well_formed(r, n_next, c["n_draws"]) for r in c["rows"]) and int((c["rows"] >> 8).max()) > n_next // 2
+    assert c["pairs_ordered_by_a_high_bit"] >= 1     # two entries of one pair take at r1 < r2, r1 >= 512, (r1 & 511) > (r2 & 511): bits 9 and up put r1 first
+    assert c["highest_take_rank"] == n_next - 1 > 4032      # a take in the last, ragged round of 64 ranks (4099) or at the last rank there can be (8192)
+    assert np.isfinite(c["want"]).all()
+    if n_next == 8192:
+        assert len(c["rows"]) == 8 and entries.max() == 4 and c["means"].shape == (3, 8192)
+    else:
+        assert len(c["rows"]) == 40 and {1, 2, 47} <= set(entries.tolist()) and c["means"].shape == (6, 4099)
+        assert (bits(c["means"][0]) == bits(c["means"][1])).all() and not (pe.choice_of(c["want"])[0] == 1).any()
+        mass = c["means"].sum(axis=1, dtype=np.float64)
+        assert abs(mass[3] - 0.5) < 1e-6 and abs(mass[4] - 1.5) < 1e-6 and (c["means"][5] > 0).sum() == 5
+        assert which != "ties" or c["five_lowest_rank"] >= 512      # the five buckets of 0.2 lie above rank 512 from every bucket of the 34 rows below 1024
+
+
+@pytest.mark.parametrize("n_next,which", pe.HIGH_RANK_CASES)
+def test_the_host_distance_equals_the_restatement_at_high_ranks(n_next, which):
+    c = pe.high_rank_case(n_next, which)
+    km = host_metric(c["ground"], c["n_draws"])
+    got = np.asarray([[km.distance(r, q) for q in c["means"]] for r in c["rows"]], dtype=F32)
+    bad = np.argwhere(bits(got) != bits(c["want"]))
+    assert len(bad) == 0, (len(bad), bad[:5].tolist())
+
+
+@pytest.mark.parametrize("name", pe.VALUE_CASES)
+def test_the_host_distance_equals_the_restatement_at_value_edges(name):
+    c = pe.value_case(name)
+    pe.value_premises(name, c)
+    km = host_metric(c["ground"], c["n_draws"])
+    got = np.asarray([[km.distance(r, q) for q in c["means"]] for r in c["rows"]], dtype=F32)
+    bad = np.argwhere(bits(got) != bits(c["want"]))
+    assert len(bad) == 0, (name, len(bad), bad[:5].tolist(), got[tuple(bad[:5].T)], c["want"][tuple(bad[:5].T)])
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------------------------------------
