@@ -872,7 +872,12 @@ int rs_update_min_dists(rs_table *table, int dist, float *d_min_dists, const flo
  *   rs_kmeans_reassign      Kmeans::reassign_clusters (:287-334) = assignment_with_bounds (:213-265); d_order (may be NULL): datum i = dataset[d_order[i]]
  *   rs_kmeans_fit_regular   Kmeans::fit_regular (:497-600), `iterations` = 10 in the reference; centers in/out, d_clusters out, d_bounds / inertia out (may be NULL)
  *   rs_kmeans_fit_growbatch Kmeans::fit_growbatch AS CODED (:336-495: one pass over the first `batch` shuffled items, then `break`); the shuffle (:352) is the
- *                           caller's: d_order; stats (may be NULL) = {min_change, inertia as printed} */
+ *                           caller's: d_order; stats (may be NULL) = {min_change, inertia as printed}
+ * Limits of the two fits, refused (RS_ERR_UNSUPPORTED) before anything is launched or written -- d_clusters, d_bounds and centers are left as they were:
+ *   at most 16 384 centers (rs_kmeans_fit_regular and rs_kmeans_fit_growbatch: one LDS counter per cluster in the member lists);
+ *   at most 63 bins for rs_kmeans_fit_growbatch (one lane of a wave per bin, and one for the row of upper bounds); rs_kmeans_fit_regular takes 1..64.
+ * Inputs of the whole family (the distances, predict, update_min_dists and the loops): finite, non-negative bins with a finite f32 sum.  emd_1d casts
+ * round(n_bins / factor) to an integer, which has no defined value for NaN, so there is no contract for non-finite bins or rows whose f32 sum overflows. */
 int rs_kmeans_init_s(rs_table *table, int dist, const float *centers, int n_centers, int n_bins, float *s);
 /* Kmeans::init_random's choice among restarts (kmeans.rs:104-165): the caller draws the candidate center sets with its rng (`choose_multiple`, :120), this scores them
  * as coded (mean pairwise distance, f32 sums in index order, :133-148) and returns the most spread one (*best; the last of equal maxima, :151-156).

@@ -898,20 +898,31 @@ void two_longest(const std::vector<float> &mv, int *longest_idx, float *longest,
     }
 }
 
-int fit_check(const char *who, const rs_table *t, int dist, const void *d_dataset, size_t n, const float *centers, int k, int n_bins) {
+// the two limits of update_step's launches, refused here: before k_kmeans_init_state, init_s or reassign has written any of the caller's buffers
+constexpr size_t kKmMaxCenters = 64 * 1024 / 4;   // one LDS counter per cluster in k_kmeans_tile_hist
+constexpr int kKmMaxRows = 64;                    // one lane of k_kmeans_center_sums' wave per row: the bins, + the row of upper bounds for growbatch
+int fit_limits(int k, int n_bins, bool growbatch) {
+    if (size_t(k) > kKmMaxCenters) return fail(RS_ERR_UNSUPPORTED, "k-means training loops: at most 16 384 centers (the counting sort's LDS histogram)");
+    if (n_bins + (growbatch ? 1 : 0) > kKmMaxRows)   // fit_regular: check_args has refused more than 64 bins before this; the message holds either way
+        return fail(RS_ERR_UNSUPPORTED, growbatch ? "k-means training loops: at most 63 bins (one lane of a wave per bin)"
+                                                  : "k-means training loops: at most 64 bins (one lane of a wave per bin)");
+    return RS_OK;
+}
+
+int fit_check(const char *who, const rs_table *t, int dist, const void *d_dataset, size_t n, const float *centers, int k, int n_bins, bool growbatch) {
     if (int rc = check_args(who, t, dist, d_dataset, n, centers, k, n_bins)) return rc;
     if (k < 2) return fail(RS_ERR_INVALID, std::string(who) + ": at least two centers (Rust: index out of bounds on center_movement[1], kmeans.rs:554)");
     if (n == 0) return fail(RS_ERR_INVALID, std::string(who) + ": empty dataset");
-    return RS_OK;
+    return fit_limits(k, n_bins, growbatch);
 }
 
 // one training step after the assignment: sums in data order on the device, means / movements on the host (k * n_bins numbers), bounds shifted on the device.
 // growbatch: the `&& count > 0` form of the mean and the squared upper bounds per cluster.  new_centers / counts / sq are host outputs.
 int update_step(rs_table *t, int dist, const float *d_dataset, const uint32_t *d_order, size_t n, std::vector<float> &centers, int k, int n_bins, bool growbatch,
                 const uint32_t *d_clusters, float *d_bounds, KmDevice &w, std::vector<float> &mv, std::vector<float> &counts, std::vector<float> &sq) {
+    if (int rc = fit_limits(k, n_bins, growbatch)) return rc;   // fit_check has refused these already: no launch below exceeds 64 KB of LDS or 64 rows
     if (!w.members || w.n_tiles != (n + kKmTile - 1) / kKmTile)
         if (int rc = w.alloc_lists(n, k)) return rc;
-    if (size_t(k) * 4 > 64 * 1024) return fail(RS_ERR_UNSUPPORTED, "k-means training loops: at most 16 384 centers (the counting sort's LDS histogram)");
     hipLaunchKernelGGL(k_kmeans_tile_hist, dim3((unsigned)w.n_tiles), dim3(kKmBlock), size_t(k) * 4, t->stream, (const unsigned *)d_clusters, n, k, w.tile_hist);
     hipLaunchKernelGGL(k_kmeans_tile_scan, dim3((unsigned)((k + kKmBlock - 1) / kKmBlock)), dim3(kKmBlock), 0, t->stream, w.tile_hist, w.n_tiles, k, w.total);
     hipLaunchKernelGGL(k_kmeans_start_scan, dim3(1), dim3(kKmBlock), 0, t->stream, (const unsigned *)w.total, k, w.start);
@@ -919,7 +930,6 @@ int update_step(rs_table *t, int dist, const float *d_dataset, const uint32_t *d
                        (const unsigned *)w.start, w.members);
     RS_HIP(hipGetLastError(), "k-means member lists");
     const int rows = n_bins + (growbatch ? 1 : 0);
-    if (rows > 64) return fail(RS_ERR_UNSUPPORTED, "k-means training loops: at most 63 bins (one lane of a wave per bin)");
     if (w.staged.bytes() < (n * size_t(rows) + 4) * 4) RS_HIP(w.staged.alloc(n * size_t(rows) + 4), "k-means staging buffer");
     hipLaunchKernelGGL(k_kmeans_stage, km_grid(n), dim3(kKmBlock), 0, t->stream, d_dataset, (const unsigned *)d_order, (const unsigned *)d_clusters, (const unsigned *)w.members,
                        (const unsigned *)w.start, (const float *)d_bounds, n, n_bins, k, rows, w.staged);
@@ -1045,7 +1055,7 @@ int rs_kmeans_reassign(rs_table *t, int dist, const float *d_dataset, const uint
 int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t n, float *centers, int n_centers, int n_bins, int iterations, uint32_t *d_clusters,
                           float *d_bounds, float *inertia) {
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
-    if (int rc = fit_check("rs_kmeans_fit_regular", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
+    if (int rc = fit_check("rs_kmeans_fit_regular", t, dist, d_dataset, n, centers, n_centers, n_bins, false)) return rc;
     if (!d_clusters || iterations < 1) return fail(RS_ERR_INVALID, "rs_kmeans_fit_regular: d_clusters is NULL or iterations < 1");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     KmDevice w;
@@ -1084,7 +1094,7 @@ int rs_kmeans_fit_regular(rs_table *t, int dist, const float *d_dataset, size_t 
 int rs_kmeans_fit_growbatch(rs_table *t, int dist, const float *d_dataset, size_t n, const uint32_t *d_order, size_t batch, float *centers, int n_centers, int n_bins,
                             uint32_t *d_clusters, float *d_bounds, float *stats) {
     if (int rc_ = rs::table_settle(t, false)) return rc_;   // a held pair sweep first (rs_iterate)
-    if (int rc = fit_check("rs_kmeans_fit_growbatch", t, dist, d_dataset, n, centers, n_centers, n_bins)) return rc;
+    if (int rc = fit_check("rs_kmeans_fit_growbatch", t, dist, d_dataset, n, centers, n_centers, n_bins, true)) return rc;
     if (!d_order || !d_clusters || !d_bounds || batch == 0 || batch > n) return fail(RS_ERR_INVALID, "rs_kmeans_fit_growbatch: NULL argument or batch outside 1..n");
     RS_HIP(hipSetDevice(t->device), "hipSetDevice");
     KmDevice w;

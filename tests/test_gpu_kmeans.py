@@ -1,11 +1,17 @@
 """GPU (-m gpu): Kmeans::predict and update_min_dists (gen_abstraction/kmeans.rs:173-211, :603-619) with emd_1d / l2_dist on the device,
 through the C ABI, bit-exact against the CPU oracle."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import rustsolver_amd as rs
 from oracle import orc
 from rustsolver_amd import abstraction as ab
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kmeans_edge_inputs import histograms  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -20,20 +26,6 @@ def need_gpu():
 def table():
     n_actions, tree = rs.build_game_tree(rs.default_flop())
     return rs.create_infosets(n_actions, tree, [4], [1])
-
-
-def histograms(rng, n, n_bins, kind):
-    """EHS-like histograms: counts out of n_samples per bin (gen_abstraction/main.rs:86-160 produces such f32 rows)"""
-    if kind == "counts":
-        centres = rng.random(n)[:, None] * n_bins
-        width = (0.5 + 6 * rng.random(n))[:, None]
-        x = np.exp(-0.5 * ((np.arange(n_bins)[None, :] - centres) / width) ** 2)
-        x = np.floor(x / x.sum(axis=1, keepdims=True) * 250) / 250.0
-    elif kind == "sparse":
-        x = rng.random((n, n_bins)) * (rng.random((n, n_bins)) < 0.25)
-    else:
-        x = rng.random((n, n_bins)) ** 3
-    return x.astype(np.float32)
 
 
 @pytest.mark.parametrize("n_bins", [1, 8, 20, 30, 32, 35, 64])
