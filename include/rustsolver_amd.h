@@ -60,7 +60,9 @@ extern "C" {
                                  still 6: rake (rs_rake, rs_rake_payoffs, rs_best_response_raked, rs_node_report_raked, rs_range_cfr_create_raked) -- additions only: a call
                                  without rake runs the code it ran and returns the bits it returned;
                                  still 6: weighted dealing (rs_deal_weights_*, rs_deals_sample_weighted, rs_deal_trainer_set_weights) -- additions only: rs_deals_sample and a
-                                 trainer without weights launch the kernel they launched and deal the bits they dealt */
+                                 trainer without weights launch the kernel they launched and deal the bits they dealt;
+                                 still 6: the max-margin gadget and per-hand best-response values (rs_range_cfr_set_gadget_kind, rs_range_cfr_gadget_margins,
+                                 rs_best_response_hands) -- additions only: rs_range_cfr_set_gadget and every walk without them launch what they launched */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -414,6 +416,33 @@ int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_param
 int rs_range_cfr_set_gadget(rs_range_cfr *s, int resolver, const double *alt /* [n_hands of player 1 - resolver], HOST */);
 int rs_range_cfr_gadget_get(const rs_range_cfr *s, float *regrets /* [2][n] */, float *strategy_sum /* [2][n] */);
 int rs_range_cfr_gadget_set(rs_range_cfr *s, const float *regrets, const float *strategy_sum);
+/* ---- the max-margin gadget (Moravcik, Schmid, Ha, Hladik, Gaukrodger, AAAI 2016) on a full-width solver ----
+ * A second gadget kind: O picks the HAND on which the resolver improved least, the resolver maximises that minimum margin.  rs_range_cfr_set_gadget_kind with
+ * RS_GADGET_RESOLVE is rs_range_cfr_set_gadget in every respect; an unknown kind is RS_ERR_INVALID; the checks, the refusals (locks, rake: RS_ERR_UNSUPPORTED), the zeroing
+ * of the rows and re-arming are rs_range_cfr_set_gadget's.  The rows stay regret[2][n], ssum[2][n] and _gadget_get / _set keep their layout: under RS_GADGET_MAXMARGIN row 0
+ * is the hand-choice row, row 1 is never read and never written by a sweep (Discounted CFR ticks multiply both rows as before).
+ *   m = the root's mass row on O's side, dealt(b, h) the deal test.  M[h] = the sum of m[b][h] over dealt lanes, b ascending from 0.0: a function of the prepared game alone,
+ *     computed once per arming (in front of the first sweep, whichever traverser's) and kept on the device: no sweep launches the mass row again.  live[h] = h has a dealt lane and M[h] > 0; L = the number of live hands.
+ *   rho, from row 0 as it stands, in f64 (regret matching over hands; not infoset.rs:83-102's f32 sum: n reaches 1 176):
+ *     pos[h] = live[h] && regret[h] > 0 ? (double)regret[h] : 0.0;  norm = the sum of pos over h ascending from 0.0;
+ *     rho[h] = pos[h] / norm if norm > 0, otherwise 1.0 / L for live hands and 0.0 for dead ones (L = 0: every rho is 0).
+ *   O's sweep: the walk is unchanged (O's own reach 1.0 at the root, the table updates as always, the root row vF left as the walk wrote it).  Per live hand:
+ *       F[h] = the sum of vF[b][h] over dealt lanes, ascending      u[h] = F[h] / M[h] - alt[h]
+ *       U = the sum of rho[h] * u[h] over live h ascending from 0.0
+ *       regret[h] = (float)((double)regret[h] + (u[h] - U))          (RS_UPD_RMPLUS: a result that is not > 0 becomes 0)
+ *       ssum[h]   = (float)((double)ssum[h] + rho[h])
+ *       margin[h] = alt[h] - F[h] / M[h]                              (f64, kept on the device)
+ *     Dead hands keep their cells and have margin NaN.  *value = U.
+ *   P's sweep: O enters the tree with q[lane] = init_q[lane] * (rho[h] / M[h]) -- one division, then one multiply; dead hands 0.0.  The walk and the table updates are
+ *     otherwise unchanged, the gadget rows are not written.  *value = the root row's sum plus the sum of rho[h] * alt[h] over live h ascending from 0.0: the rho-weighted
+ *     margin under the current profile.
+ *   A deliberate simplification: O's in-tree regrets see values without the 1 / M[h] factor and O's in-tree strategy sums do not carry rho.  Both are a positive constant per
+ *     hand, which regret matching ignores where an info set is one hand; O's subgame strategy is not what gets grafted.
+ *   The sums over hands are the ascending sequential f64 sums, bit for bit, in both tree orders.
+ * rs_range_cfr_gadget_margins: the margin row of the last O sweep ([n] doubles); RS_ERR_INVALID without a max-margin gadget or before O's first sweep since arming. */
+enum { RS_GADGET_RESOLVE = 0, RS_GADGET_MAXMARGIN = 1 };
+int rs_range_cfr_set_gadget_kind(rs_range_cfr *s, int kind, int resolver, const double *alt /* [n_hands of player 1 - resolver], HOST */);
+int rs_range_cfr_gadget_margins(const rs_range_cfr *s, double *out /* [n] */);
 size_t rs_range_cfr_bytes(const rs_range_cfr *s);
 int rs_range_cfr_launches(const rs_range_cfr *s);
 
@@ -485,6 +514,20 @@ int rs_node_report_raked(rs_table *table, const rs_tree *tree, const uint8_t *bo
 int rs_range_cfr_create_raked(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0,
                               const uint8_t *hands_p1, size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights,
                               const rs_node_locks *locks, const rs_rake *rake, const rs_range_cfr_params *params /* NULL = defaults */, rs_range_cfr **out);
+
+/* ---- per-hand root values of the best-response walk (an extension) ----
+ * rs_best_response_raked's arguments (weights, locks and rake may each be NULL), ONE traverser, every mode rs_best_response_raked accepts -- RS_BR_MAX, RS_BR_AVERAGE,
+ * | RS_BR_SORTED, | RS_BR_REAL, | RS_BR_CURRENT -- with the same refusals (RS_BR_AVERAGE | RS_BR_REAL: RS_ERR_INVALID).  For hand h of the traverser, over the run-outs b
+ * ascending from 0.0, a lane that is no deal not added:
+ *   value[h] = the sum of the root's value row v[b][h]
+ *   mass[h]  = the same fold of the root's mass row: the uncontested leaf of value 1.0 on the opponent's initial reach (the node report's mass at node 0).
+ * A hand without a dealt lane gets 0.0 in both.  value[h] / mass[h] under RS_BR_MAX is the hand's counterfactual best-response value per unit of the opponent's mass: the
+ * alternative value of a re-solve (rs_range_cfr_set_gadget's alt) and, measured in a re-solved subgame, the check of its margins; the sum of value is
+ * rs_best_response_raked's out[traverser].  All arithmetic is f64 and every sum has one order: the level plan and the depth-first walk give the same bits.  The call
+ * settles a training loop's working copy, writes nothing to the table, synchronises, and leaves value and mass alone when it refuses.  mass may be NULL. */
+int rs_best_response_hands(rs_table *table, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                           size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks,
+                           const rs_rake *rake, int mode, int traverser, double *value /* [n_hands of traverser] */, double *mass /* [n_hands], may be NULL */);
 
 /* ---- iterate: MCCFRTrainer (cfr.rs) ------------------------------------------------------------
  * Lane model: lane (board b, cluster c) is one scalar cfr() traversal (cfr.rs:481-627)

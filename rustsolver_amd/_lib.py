@@ -25,6 +25,7 @@ BR_SORTED = 0x100           # | into the mode: showdowns by rank order (O(n log 
 BR_REAL = 0x200             # | into BR_MAX: the best response in the real game (info set = board cards seen + own hole cards) against the abstracted average strategy
 BR_CURRENT = 0x400          # | into any mode: the strategies read are the CURRENT ones (get_strategy of the regrets) instead of the average ones
 DEAL_SEQUENTIAL, DEAL_JOINT = 0, 1   # rs_range_weights.deal (RS_DEAL_*)
+GADGET_RESOLVE, GADGET_MAXMARGIN = 0, 1   # rs_range_cfr_set_gadget_kind (RS_GADGET_*)
 DIST_EMD, DIST_L2 = 0, 1
 EHS_MAX_BINS = 64           # RS_EHS_MAX_BINS
 OCHS_MAX_CLUSTERS, OCHS_NO_CLUSTER = 8, 255   # RS_OCHS_*
@@ -269,6 +270,10 @@ SYMBOLS = {
     "rs_range_cfr_set_gadget": (C.c_int, [_P, C.c_int, _P]),
     "rs_range_cfr_gadget_get": (C.c_int, [_P, _P, _P]),
     "rs_range_cfr_gadget_set": (C.c_int, [_P, _P, _P]),
+    "rs_range_cfr_set_gadget_kind": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "rs_range_cfr_gadget_margins": (C.c_int, [_P, _P]),
+    "rs_best_response_hands": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, C.POINTER(RangeWeights), C.POINTER(NodeLocks), C.POINTER(Rake), C.c_int,
+                                         C.c_int, _P, _P]),
     "rs_range_cfr_bytes": (C.c_size_t, [_P]),
     "rs_range_cfr_launches": (C.c_int, [_P]),
     "rs_deal_trainer_br_bytes": (C.c_size_t, [_P]),

@@ -12,6 +12,8 @@
 //  * rs_range_cfr_*: full-width CFR over the hand ranges on the same walk (the opponent plays the current strategy, the traverser's own nodes keep their info sets' sums as
 //    regrets): three more job kinds of the best response's job table and launcher.  RS_BR_CURRENT hands the readers the regret array.
 //  * rs_range_cfr_set_gadget: the re-solving gadget above the root of a full-width solver's tree (safe subgame re-solving): two more job kinds.
+//  * rs_range_cfr_set_gadget_kind: the max-margin gadget in the same two places of the plan (two launches each); rs_best_response_hands: the root's value and mass rows
+//    folded per hand behind one traverser's walk, one more job kind.
 //  * rs_node_locks: a player's per-hand strategy fixed at chosen action nodes: the locks' rows live with the prepared game, a locked node takes two more
 //    job kinds in place of its reach and value jobs, in all three walks.
 //  * rs_rake: raked pots: the tree's terminals pay three numbers (win, tie, lose) instead of +-value and 0 -- no new job kind, the leaf kernels are
@@ -1567,6 +1569,153 @@ __global__ __launch_bounds__(kBrBlock) void k_br_gadget_discount(float *__restri
     ssum[i] = ssum[i] * d_sum;
 }
 
+// ---- per-hand root values (rs_best_response_hands) and the max-margin gadget (rs_range_cfr_set_gadget_kind, RS_GADGET_MAXMARGIN) ------------------------------------
+// k_br_gadget_own's fold without its update: one THREAD per hand adds the root's value row and the root's mass row up over the run-outs, ascending from 0.0, lanes that
+// are no deal not added, kBrRealFlight loads of each row in flight.  The last round (NB = 1) is the same text with a fold of one addition.  A hand without a dealt lane
+// gets 0.0 twice.  Nothing is written but the two sums.  mass == nullptr (the max-margin gadget's sweeps: M is known): the value row alone, out_m is not written.
+__global__ __launch_bounds__(kBrBlock) void k_br_hands_fold(const uint64_t *__restrict__ mask_p, const uint64_t *__restrict__ bmask, uint32_t n_hands, uint32_t NB,
+                                                            const double *__restrict__ v, const double *__restrict__ mass, double *__restrict__ out_v,
+                                                            double *__restrict__ out_m) {
+    const uint32_t h = blockIdx.x * kBrBlock + threadIdx.x;
+    if (h >= n_hands) return;
+    const uint64_t mine = mask_p[h];
+    double F = 0.0, M = 0.0;
+    if (NB == 1) {
+        const double tf = v[h], tm = mass ? mass[h] : 0.0;
+        if (!(mine & bmask[0])) {
+            F += tf;
+            M += tm;
+        }
+    } else {
+        for (uint32_t k = 0; k < NB; k += kBrRealFlight) {
+            bool deal[kBrRealFlight];
+            double tf[kBrRealFlight], tm[kBrRealFlight];
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++) {
+                const uint32_t kk = min(k + q, NB - 1);
+                deal[q] = k + q < NB && !(mine & bmask[kk]);
+                tf[q] = v[(size_t)kk * n_hands + h];
+                tm[q] = mass ? mass[(size_t)kk * n_hands + h] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < kBrRealFlight; q++)
+                if (deal[q]) {   // ascending run-outs, one after the other
+                    F += tf[q];
+                    M += tm[q];
+                }
+        }
+    }
+    out_v[h] = F;
+    if (mass) out_m[h] = M;
+}
+
+// The max-margin gadget's sums over HANDS equal the ascending sequential f64 sum bit for bit: ONE workgroup stages the terms in LDS (1 326 hands at most, padded with
+// +0.0 to a multiple of eight: a sum that starts at +0.0 never holds -0.0, so adding +0.0 changes no bit) and its thread 0 adds them in order, eight LDS loads on their
+// way before the first addition.  Hands go to threads in trips of kBrBlock.
+constexpr int kBrHandsMax = 1328;   // 1 326 two-card hands, padded to a multiple of eight
+__device__ __forceinline__ double br_ordered_sum(const double *lds, uint32_t n8) {   // thread 0 only; n8 a multiple of eight
+    double acc = 0.0;
+    for (uint32_t i = 0; i < n8; i += 8) {
+        double t[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) t[q] = lds[i + q];
+#pragma unroll
+        for (int q = 0; q < 8; q++) acc += t[q];
+    }
+    return acc;
+}
+// rho of the hand-choice row (row 0) as it stands, in f64: regret matching over the LIVE hands (M[h] > 0: a hand without a dealt lane has M = 0.0).  Every thread of the
+// workgroup calls it; term[] and sc[] are LDS.  Returns norm and the number of live hands through sc[0], sc[1].
+__device__ __forceinline__ void br_mm_norm(const float *__restrict__ regret, const double *__restrict__ M, uint32_t n, uint32_t n8, double *term, double *sc) {
+    for (uint32_t h = threadIdx.x; h < n8; h += kBrBlock) {
+        double pos = 0.0;
+        if (h < n) {
+            const float r = regret[h];
+            pos = (M[h] > 0.0 && r > 0.0f) ? (double)r : 0.0;
+        }
+        term[h] = pos;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) sc[0] = br_ordered_sum(term, n8);
+    __syncthreads();
+    for (uint32_t h = threadIdx.x; h < n8; h += kBrBlock) term[h] = (h < n && M[h] > 0.0) ? 1.0 : 0.0;   // the live hands, counted the same way (exact: small integers)
+    __syncthreads();
+    if (threadIdx.x == 0) sc[1] = br_ordered_sum(term, n8);
+    __syncthreads();
+}
+__device__ __forceinline__ double br_mm_rho(float r, double M, double norm, double L) {
+    if (!(M > 0.0)) return 0.0;
+    if (norm > 0.0) return r > 0.0f ? (double)r / norm : 0.0;
+    return 1.0 / L;
+}
+// the resolver's sweep, first launch: scale[h] = rho[h] / M[h] (0.0 for a dead hand) and out[1] = the sum of rho[h] * alt[h] over the live hands, ascending from 0.0
+__global__ __launch_bounds__(kBrBlock) void k_br_mm_scale(const float *__restrict__ regret, const double *__restrict__ M, const double *__restrict__ alt, uint32_t n,
+                                                          double *__restrict__ scale, double *__restrict__ out) {
+    __shared__ double term[kBrHandsMax];
+    __shared__ double sc[2];
+    const uint32_t n8 = (n + 7u) & ~7u;
+    br_mm_norm(regret, M, n, n8, term, sc);
+    const double norm = sc[0], L = sc[1];
+    for (uint32_t h = threadIdx.x; h < n8; h += kBrBlock) {
+        double ta = 0.0;
+        if (h < n) {
+            const double m = M[h], rho = br_mm_rho(regret[h], m, norm, L);
+            scale[h] = m > 0.0 ? rho / m : 0.0;
+            if (m > 0.0) ta = rho * alt[h];
+        }
+        term[h] = ta;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) out[1] = br_ordered_sum(term, n8);
+}
+// ... second launch, as k_br_gadget_reach does: the opponent enters the tree with q[lane] = init_q[lane] * scale[h]
+__global__ __launch_bounds__(kBrBlock) void k_br_mm_reach(const double *__restrict__ scale, uint32_t n_hands, uint32_t n, const double *__restrict__ init_q,
+                                                          double *__restrict__ q_follow) {
+    const uint32_t lane = blockIdx.x * kBrBlock + threadIdx.x;
+    if (lane >= n) return;
+    q_follow[lane] = init_q[lane] * scale[lane % n_hands];
+}
+// the opponent's sweep, behind k_br_hands_fold (F, M): u[h] = F[h] / M[h] - alt[h], U = the sum of rho[h] * u[h] over the live hands, the hand-choice row's cells and the
+// margins.  Dead hands keep their cells and get margin NaN.  Row 1 of the gadget's rows is neither read nor written.  out[0] = U.
+__global__ __launch_bounds__(kBrBlock) void k_br_mm_update(float *__restrict__ regret, float *__restrict__ ssum, const double *__restrict__ F, const double *__restrict__ M,
+                                                           const double *__restrict__ alt, uint32_t n, double *__restrict__ margin, double *__restrict__ out, int rmplus) {
+    __shared__ double term[kBrHandsMax];
+    __shared__ double sc[3];
+    const uint32_t n8 = (n + 7u) & ~7u;
+    br_mm_norm(regret, M, n, n8, term, sc);
+    const double norm = sc[0], L = sc[1];
+    for (uint32_t h = threadIdx.x; h < n8; h += kBrBlock) {
+        double tu = 0.0;
+        if (h < n) {
+            const double m = M[h];
+            if (m > 0.0) tu = br_mm_rho(regret[h], m, norm, L) * (F[h] / m - alt[h]);
+        }
+        term[h] = tu;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double U = br_ordered_sum(term, n8);
+        sc[2] = U;
+        out[0] = U;
+    }
+    __syncthreads();
+    const double U = sc[2];
+    for (uint32_t h = threadIdx.x; h < n; h += kBrBlock) {
+        const double m = M[h];
+        if (!(m > 0.0)) {
+            margin[h] = __longlong_as_double(0x7ff8000000000000ll);
+            continue;
+        }
+        const float r = regret[h];
+        const double rho = br_mm_rho(r, m, norm, L), fm = F[h] / m, al = alt[h], u = fm - al;
+        float nr = (float)((double)r + (u - U));
+        if (rmplus && !(nr > 0.0f)) nr = 0.0f;
+        regret[h] = nr;
+        ssum[h] = (float)((double)ssum[h] + rho);
+        margin[h] = al - fm;
+    }
+}
+
 // ---- node locks (rs_node_locks): an action node whose acting player plays a given per-hand strategy, lock[(a * n_prefix + f) * n_hands + h] -------------------------
 // Two element-wise kernels in plain lane order, a thread per lane = b * n_hands + h: the reach that comes in, the A lock values of the lane's (prefix, hand) pair
 // (f = b / pp, pp the run-outs under a prefix of the node's round) and the A rows of q_out / vch are unit-stride 8-byte accesses.  Nothing is gathered by cluster id, so
@@ -1630,11 +1779,12 @@ __global__ __launch_bounds__(kBrBlock) void k_br_lock_value_jobs(const uint64_t 
 // (the full-width sweep: kBrReachOwn on the way down, kBrOwnCfrWave / kBrOwnCfrThread on the way up; the node report: kBrReachOwn on the way down, and after the value
 // job of a requested node kBrMass -- the leaf kernels on the node's q -- and kBrReport)
 // (the re-solving gadget: kBrGadgetReach in front of the root's reach on the resolver's sweep, its TERMINATE leaf a kBrMass job on the root; kBrMass and kBrGadgetOwn behind
-// the root's value job on the opponent's sweep)
+// the root's value job on the opponent's sweep; under RS_GADGET_MAXMARGIN the two kinds keep their places and are two launches each, and neither sweep has a kBrMass)
+// (rs_best_response_hands: kBrMass and kBrHands behind the root's value job)
 // (node locks: a locked node takes kBrLockReach where it would take a reach kind -- the opponent's q, and the traverser's pi where that goes down -- and kBrLockValue where it
 // would take an own-node kind; they sort with those: the last reach kind in front of kBrLeaf, the last own-node kind in front of kBrSum)
 enum BrKind { kBrGadgetReach, kBrReachGrouped, kBrReach, kBrReachOwn, kBrLockReach, kBrLeaf, kBrOwnWave, kBrOwnCols, kBrOwnGrouped, kBrOwnReal, kBrOwnCfrWave, kBrOwnCfrThread,
-              kBrOwnThread, kBrLockValue, kBrSum, kBrMass, kBrReport, kBrGadgetOwn, kBrKinds };
+              kBrOwnThread, kBrLockValue, kBrSum, kBrMass, kBrReport, kBrGadgetOwn, kBrHands, kBrKinds };
 // launched round by round (the round's groups, or its run-outs per prefix, shape the grid); every other kind takes the jobs of all rounds in one launch
 static bool br_per_round(BrKind k) { return k == kBrReachGrouped || k == kBrOwnGrouped || k == kBrOwnReal || k == kBrReport; }
 // P, Pc, O and Q of br_terminal_sorted_body
@@ -1693,6 +1843,14 @@ struct BrRun {
     int gadget = -1;
     double *d_g_alt = nullptr, *d_g_qf = nullptr, *d_g_qt = nullptr, *d_g_row[2] = {nullptr, nullptr};
     float *d_g_regret = nullptr, *d_g_ssum = nullptr;
+    // RS_GADGET_MAXMARGIN (br_cfr_set_gadget's kind 1; the buffers come with the first arming of that kind): per opponent hand F (the root row's fold of the last
+    // opponent's sweep), M (the root mass row's fold: the game's alone, computed once per arming by br_mm_mass), rho / M and the margins; d_g_out = {U, sum of rho * alt}
+    int gadget_kind = RS_GADGET_RESOLVE;
+    double *d_g_F = nullptr, *d_g_M = nullptr, *d_g_scale = nullptr, *d_g_margin = nullptr, *d_g_out = nullptr;
+    bool g_M_ready = false, g_margin_ready = false;
+    double g_out[2] = {0.0, 0.0};             // ... d_g_out of the last sweep, on the host
+    // rs_best_response_hands in flight (br_hands): the root's mass row [n_pad] and the output [2][n_hands of the traverser] on the device, nullptr otherwise
+    double *d_hands_mass = nullptr, *d_hands_out = nullptr;
     // node locks (rs_node_locks): per tree node its lock's rows [A][prefixes of its round][hands of the acting player] on the device (dalloc: the game-only half), nullptr =
     // not locked; empty when the game has no lock at all
     std::vector<const double *> lock_of;
@@ -1792,6 +1950,7 @@ struct BrRun {
         std::vector<int> own_reach_at;     // ... an own node's reach job (full-width sweep, node report)
         std::vector<int> mass_at, report_at;   // ... a requested node's mass and report jobs (node report)
         int gadget_reach_at = -1, gadget_mass_at = -1, gadget_own_at = -1;   // the gadget's jobs above the root (a full-width solver with a gadget)
+        int hands_at = -1;                 // rs_best_response_hands' fold of the root rows (its root mass job sits in gadget_mass_at)
         double *root = nullptr;            // where the root's values arrive
     };
     // host only: gives every node its buffers and fills the jobs
@@ -1843,16 +2002,29 @@ struct BrRun {
                 q_in[0] = d_g_qf;
                 jm.q = d_g_qt;
                 jm.value = -1.0;
-                add(kBrMass, 0, 0, jm);
+                if (gadget_kind == RS_GADGET_RESOLVE) add(kBrMass, 0, 0, jm);   // (max-margin has no TERMINATE leaf: the hand choice sits in the opponent's reach)
             } else {             // the opponent's sweep: the root's mass row, then the gadget's own node over the root row
                 jm.q = op.d_init_q;
                 jm.value = 1.0;
-                add(kBrMass, 0, 0, jm);
+                if (gadget_kind == RS_GADGET_RESOLVE) add(kBrMass, 0, 0, jm);   // (max-margin reads M, folded once per arming: br_mm_mass)
                 BrJob jo{};
                 jo.v = pl.root;
                 jo.sum_src[0] = d_g_row[p];
                 add(kBrGadgetOwn, 0, 0, jo);
             }
+        }
+        if (d_hands_out) {   // rs_best_response_hands: the root's mass row and the fold of both root rows, behind the root's value job in either tree order
+            BrJob jm{};
+            jm.q = op.d_init_q;
+            jm.v = d_hands_mass;
+            jm.uncontested = 1;
+            jm.value = 1.0;
+            add(kBrMass, 0, 0, jm);
+            BrJob jf{};
+            jf.v = pl.root;
+            jf.sum_src[0] = d_hands_mass;
+            jf.q_out = d_hands_out;
+            add(kBrHands, 0, 0, jf);
         }
         for (size_t id = 0; id < N; ++id) {   // parents before children: a node's q and v slot are known when it comes up
             const rs_tree_node &n = tree->nodes[id];
@@ -1980,8 +2152,10 @@ struct BrRun {
         pl.jobs.reserve(perm.size());
         for (uint32_t i : perm) {
             const BrPlan::Entry &e = entries[i];
-            if (e.kind == kBrGadgetReach || e.kind == kBrGadgetOwn || (e.kind == kBrMass && cfr)) {   // (a full-width solver's only mass job is the gadget's)
-                (e.kind == kBrGadgetReach ? pl.gadget_reach_at : (e.kind == kBrGadgetOwn ? pl.gadget_own_at : pl.gadget_mass_at)) = int(pl.jobs.size());
+            if (e.kind == kBrGadgetReach || e.kind == kBrGadgetOwn || e.kind == kBrHands || (e.kind == kBrMass && (cfr || d_hands_out))) {
+                // (a full-width solver's only mass job is the gadget's, a per-hand walk's only one the root's)
+                (e.kind == kBrGadgetReach ? pl.gadget_reach_at : (e.kind == kBrGadgetOwn ? pl.gadget_own_at : (e.kind == kBrHands ? pl.hands_at : pl.gadget_mass_at))) =
+                    int(pl.jobs.size());
                 pl.entries.push_back(e);
                 pl.jobs.push_back(jobs[i]);
                 continue;
@@ -2132,10 +2306,29 @@ struct BrRun {
             break;
         }
         case kBrGadgetReach:   // one job, whichever tree order: the same launch
+            if (gadget_kind == RS_GADGET_MAXMARGIN) {   // max-margin: rho / M per hand in one workgroup, then the per-lane scale
+                hipLaunchKernelGGL(k_br_mm_scale, dim3(1), block, 0, s, d_g_regret, d_g_M, d_g_alt, op.n_hands, d_g_scale, d_g_out);
+                err = hipGetLastError();
+                ++n_launches;
+                if (err != hipSuccess) return;
+                hipLaunchKernelGGL(k_br_mm_reach, dim3(grid1(op.n)), block, 0, s, d_g_scale, op.n_hands, op.n, h->q, h->q_out);
+                break;
+            }
             hipLaunchKernelGGL(k_br_gadget_reach, dim3(grid1(op.n)), block, 0, s, d_g_regret, d_g_alt, op.n_hands, op.n, h->q, h->q_out, h->v);
             break;
         case kBrGadgetOwn:
+            if (gadget_kind == RS_GADGET_MAXMARGIN) {   // max-margin: the fold of the root row, then the hand-level update in one workgroup
+                hipLaunchKernelGGL(k_br_hands_fold, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, h->v, (const double *)nullptr, d_g_F, d_g_M);
+                err = hipGetLastError();
+                ++n_launches;
+                if (err != hipSuccess) return;
+                hipLaunchKernelGGL(k_br_mm_update, dim3(1), block, 0, s, d_g_regret, d_g_ssum, d_g_F, d_g_M, d_g_alt, me.n_hands, d_g_margin, d_g_out, cfr_rmplus);
+                break;
+            }
             hipLaunchKernelGGL(k_br_gadget_own, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, d_g_regret, d_g_ssum, d_g_alt, h->sum_src[0], h->v, cfr_rmplus);
+            break;
+        case kBrHands:
+            hipLaunchKernelGGL(k_br_hands_fold, dim3(grid1(me.n_hands)), block, 0, s, me.d_mask, d_bmask, me.n_hands, NB, h->v, h->sum_src[0], h->q_out, h->q_out + me.n_hands);
             break;
         case kBrKinds:   // a count, no kind
             return;
@@ -2175,6 +2368,7 @@ struct BrRun {
             walk(pl, 0);
             if (pl.gadget_mass_at >= 0) one(pl, pl.gadget_mass_at);
             if (pl.gadget_own_at >= 0) one(pl, pl.gadget_own_at);
+            if (pl.hands_at >= 0) one(pl, pl.hands_at);
         } else {   // reach downwards by depth, the leaves in slices of 16 384, values upwards by depth: the plan's order
             for (size_t lo = 0, hi; lo < pl.jobs.size() && err == hipSuccess; lo = hi) {
                 const size_t most = pl.entries[lo].kind == kBrLeaf || pl.entries[lo].kind == kBrMass ? 16384 : pl.jobs.size();
@@ -2183,10 +2377,12 @@ struct BrRun {
             }
         }
         if (err == hipSuccess) err = hipMemcpyAsync(root_host, pl.root, side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
-        if (cfr && gadget == p) {   // the resolver's sweep: the TERMINATE leaf's row comes back beside the root's
+        if (cfr && gadget == p && gadget_kind == RS_GADGET_RESOLVE) {   // the resolver's sweep: the TERMINATE leaf's row comes back beside the root's
             gadget_term.resize(side[p].n);
             if (err == hipSuccess) err = hipMemcpyAsync(gadget_term.data(), d_g_row[p], side[p].n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
         }
+        if (cfr && gadget >= 0 && gadget_kind == RS_GADGET_MAXMARGIN && err == hipSuccess)   // max-margin: U (the opponent's sweep) and the sum of rho * alt (the resolver's)
+            err = hipMemcpyAsync(g_out, d_g_out, sizeof(g_out), hipMemcpyDeviceToHost, t->stream);
         const hipError_t done = hipStreamSynchronize(t->stream);   // the plan is freed on return and the next pass overwrites the job table: after an error too, nothing queued may still touch them
         if (err == hipSuccess) err = done;
         return err == hipSuccess ? RS_OK : hip_fail(err, ws_levels ? "rs_best_response (level plan)" : "rs_best_response");
@@ -2776,10 +2972,14 @@ int BrRun::traverse(int traverser, std::vector<double> &root, double *total) {
     last_launches += ws_levels ? n_launches : 0;
     double sum = 0.0;
     for (uint32_t l = 0; l < side[p].n; ++l) sum += root[l];
-    if (cfr && gadget == p) {   // plus the TERMINATE branch, summed like a root row
+    if (cfr && gadget == p && gadget_kind == RS_GADGET_RESOLVE) {   // plus the TERMINATE branch, summed like a root row
         double term = 0.0;
         for (uint32_t l = 0; l < side[p].n; ++l) term += gadget_term[l];
         sum += term;
+    }
+    if (cfr && gadget >= 0 && gadget_kind == RS_GADGET_MAXMARGIN) {   // max-margin: the rho-weighted margin under the current profile; the opponent's sweep is worth U
+        if (gadget == p) sum += g_out[1];
+        else sum = g_out[0], g_margin_ready = true;
     }
     *total = sum;
     return RS_OK;
@@ -2813,6 +3013,41 @@ int br_execute(BrRun *prepared, int mode, double *out) {
     std::vector<double> root(run.n_pad_max);
     for (int p = 0; p < 2; ++p)
         if (int rc = run.traverse(p, root, &out[p])) return rc;
+    return RS_OK;
+}
+
+// One traverser's walk with the root's mass row and the fold of both root rows behind the root's value job (rs_best_response_hands): value[h] and mass[h] of the
+// traverser's hands, mass may be NULL.  Everything that can refuse has refused before the first launch, and the outputs are written after the last copy has come back.
+int br_hands(BrRun *prepared, int mode, int traverser, double *value, double *mass) {
+    if (!prepared || !value) return fail(RS_ERR_INVALID, "rs_best_response_hands: NULL argument");
+    const bool real = (mode & RS_BR_REAL) != 0, current = (mode & RS_BR_CURRENT) != 0;
+    mode &= ~(RS_BR_REAL | RS_BR_CURRENT);
+    if (int rc = br_check_mode(mode, real)) return rc;
+    if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_best_response_hands: traverser is 0 or 1");
+    BrRun &run = *prepared;
+    if (run.cfr) return fail(RS_ERR_INVALID, "rs_best_response_hands: the prepared game belongs to a full-width solver");
+    rs_table *t = run.t;
+    if (int rc = table_settle(t)) return rc;
+    RS_HIP(hipSetDevice(t->device), "hipSetDevice");
+    run.mode = mode;
+    run.real = real;
+    run.current = current;
+    run.err = hipSuccess;
+    const size_t n = run.side[traverser].n_hands;
+    DevBuf<double> d_mass, d_out;
+    RS_HIP(d_mass.alloc(run.side[traverser].n_pad), "rs_best_response_hands: the mass row");
+    RS_HIP(d_out.alloc(2 * n), "rs_best_response_hands: the output buffer");
+    run.d_hands_mass = d_mass;
+    run.d_hands_out = d_out;
+    run.last_launches = 0;
+    std::vector<double> root(run.n_pad_max), host(2 * n);
+    double total = 0.0;
+    int rc = run.traverse(traverser, root, &total);   // synchronises: nothing queued touches the two buffers after it
+    run.d_hands_mass = run.d_hands_out = nullptr;
+    if (rc) return rc;
+    RS_HIP(hipMemcpy(host.data(), d_out, 2 * n * sizeof(double), hipMemcpyDeviceToHost), "rs_best_response_hands: the copy back");
+    std::copy(host.begin(), host.begin() + n, value);
+    if (mass) std::copy(host.begin() + n, host.end(), mass);
     return RS_OK;
 }
 
@@ -2911,6 +3146,7 @@ int br_cfr_mark(BrRun *prepared) {
     prepared->cfr = true;
     return RS_OK;
 }
+static int br_mm_mass(BrRun &run);
 int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
     if (!prepared || !prepared->cfr) return fail(RS_ERR_INVALID, "rs_range_cfr: NULL argument");
     if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_iterate: traverser is 0 or 1");
@@ -2923,6 +3159,8 @@ int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
     run.cfr_rmplus = rmplus ? 1 : 0;
     run.err = hipSuccess;
     if (int rc = br_root_reach(run, "rs_range_cfr: the root reach")) return rc;
+    if (run.gadget >= 0 && run.gadget_kind == RS_GADGET_MAXMARGIN && !run.g_M_ready)   // the first sweep since arming, whichever traverser's
+        if (int rc = br_mm_mass(run)) return rc;
     run.last_launches = 0;
     std::vector<double> root(run.n_pad_max);
     double total = 0.0;
@@ -2933,8 +3171,9 @@ int br_cfr_sweep(BrRun *prepared, int traverser, int rmplus, double *value) {
 
 // ---- the re-solving gadget on a full-width solver's prepared game ---------------------------------------------------------------------------------------------------
 // Everything that can refuse has refused before anything is written: a refused call leaves the rows and the table alone.
-int br_cfr_set_gadget(BrRun *prepared, int resolver, const double *alt) {
+int br_cfr_set_gadget(BrRun *prepared, int kind, int resolver, const double *alt) {
     if (!prepared || !prepared->cfr || !alt) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: NULL argument");
+    if (kind != RS_GADGET_RESOLVE && kind != RS_GADGET_MAXMARGIN) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget_kind: kind is RS_GADGET_RESOLVE or RS_GADGET_MAXMARGIN");
     if (resolver != 0 && resolver != 1) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: resolver is 0 or 1");
     BrRun &run = *prepared;
     if (!run.lock_of.empty()) return fail(RS_ERR_UNSUPPORTED, "rs_range_cfr_set_gadget: the object was created with node locks (a gadget and locks on one object are out of scope)");
@@ -2954,11 +3193,55 @@ int br_cfr_set_gadget(BrRun *prepared, int resolver, const double *alt) {
         if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr_set_gadget: the gadget's rows");
         run.d_g_alt = a, run.d_g_qf = qf, run.d_g_qt = qt, run.d_g_row[0] = row0, run.d_g_row[1] = row1, run.d_g_regret = rg, run.d_g_ssum = ss;
     }
+    if (kind == RS_GADGET_MAXMARGIN && !run.d_g_M) {   // first max-margin arming: the per-hand rows, sized like alt
+        const size_t most = std::max(run.side[0].n_hands, run.side[1].n_hands);
+        double *f = run.dalloc<double>(most), *m = run.dalloc<double>(most), *sc = run.dalloc<double>(most), *mg = run.dalloc<double>(most), *o = run.dalloc<double>(2);
+        if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr_set_gadget_kind: the max-margin rows");
+        run.d_g_F = f, run.d_g_M = m, run.d_g_scale = sc, run.d_g_margin = mg, run.d_g_out = o;
+    }
     RS_HIP(hipMemcpy(run.d_g_alt, alt, size_t(n) * sizeof(double), hipMemcpyHostToDevice), "rs_range_cfr_set_gadget: alt");
     RS_HIP(hipMemset(run.d_g_regret, 0, size_t(2) * n * sizeof(float)), "rs_range_cfr_set_gadget: the rows");
     RS_HIP(hipMemset(run.d_g_ssum, 0, size_t(2) * n * sizeof(float)), "rs_range_cfr_set_gadget: the rows");
     RS_HIP(hipDeviceSynchronize(), "rs_range_cfr_set_gadget");
     run.gadget = resolver;
+    run.gadget_kind = kind;
+    run.g_M_ready = run.g_margin_ready = false;
+    return RS_OK;
+}
+// max-margin, in front of the first sweep since arming: M, which both sweeps read and which is a function of the prepared game alone -- the root's mass row on the
+// opponent's lanes (the leaf kernels of the run's showdown mode on the resolver's initial reach: the kBrMass job of CFR-D's opponent sweep) and its fold, kept on the device.
+static int br_mm_mass(BrRun &run) {
+    if (int rc = br_ensure_workspace(run)) return rc;
+    const int O = 1 - run.gadget;
+    run.p = O;
+    BrJob jm{};
+    jm.q = run.side[run.gadget].d_init_q;
+    jm.v = run.d_g_row[O];
+    jm.uncontested = 1;
+    jm.value = 1.0;
+    if (run.job_table.bytes() < sizeof(BrJob)) run.err = run.job_table.alloc(1);
+    if (run.err == hipSuccess) run.err = hipMemcpyAsync(run.job_table, &jm, sizeof(BrJob), hipMemcpyHostToDevice, run.t->stream);
+    run.launch(kBrMass, 0, run.job_table, 1, &jm);
+    const BrSide &me = run.side[O];
+    if (run.err == hipSuccess) {
+        hipLaunchKernelGGL(k_br_hands_fold, dim3(grid1(me.n_hands)), dim3(kBrBlock), 0, run.t->stream, me.d_mask, run.d_bmask, me.n_hands, run.NB, run.d_g_row[O], run.d_g_row[O],
+                           run.d_g_F, run.d_g_M);
+        run.err = hipGetLastError();
+    }
+    const hipError_t done = hipStreamSynchronize(run.t->stream);   // jm leaves scope
+    if (run.err == hipSuccess) run.err = done;
+    if (run.err != hipSuccess) return hip_fail(run.err, "rs_range_cfr: the max-margin gadget's mass row");
+    run.g_M_ready = true;
+    return RS_OK;
+}
+int br_cfr_gadget_margins(BrRun *prepared, double *out) {
+    if (!prepared || !prepared->cfr || !out) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_margins: NULL argument");
+    BrRun &run = *prepared;
+    if (run.gadget < 0 || run.gadget_kind != RS_GADGET_MAXMARGIN) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_margins: the object has no max-margin gadget");
+    if (!run.g_margin_ready) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_margins: no sweep of the opponent since the gadget was armed");
+    RS_HIP(hipSetDevice(run.t->device), "hipSetDevice");
+    RS_HIP(hipStreamSynchronize(run.t->stream), "rs_range_cfr_gadget_margins");
+    RS_HIP(hipMemcpy(out, run.d_g_margin, size_t(run.side[1 - run.gadget].n_hands) * sizeof(double), hipMemcpyDeviceToHost), "rs_range_cfr_gadget_margins");
     return RS_OK;
 }
 int br_cfr_gadget_rows(BrRun *prepared, float *regrets, float *strategy_sum, const float *set_regrets, const float *set_strategy_sum, const char *fn) {
@@ -3058,7 +3341,15 @@ int rs_range_cfr_train(rs_range_cfr *s, uint64_t iterations, const rs_dcfr_param
 }
 int rs_range_cfr_set_gadget(rs_range_cfr *s, int resolver, const double *alt) {
     if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget: NULL argument");
-    return rs::br_cfr_set_gadget(s->run, resolver, alt);
+    return rs::br_cfr_set_gadget(s->run, RS_GADGET_RESOLVE, resolver, alt);
+}
+int rs_range_cfr_set_gadget_kind(rs_range_cfr *s, int kind, int resolver, const double *alt) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_set_gadget_kind: NULL argument");
+    return rs::br_cfr_set_gadget(s->run, kind, resolver, alt);
+}
+int rs_range_cfr_gadget_margins(const rs_range_cfr *s, double *out) {
+    if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_margins: NULL argument");
+    return rs::br_cfr_gadget_margins(s->run, out);
 }
 int rs_range_cfr_gadget_get(const rs_range_cfr *s, float *regrets, float *strategy_sum) {
     if (!s) return fail(RS_ERR_INVALID, "rs_range_cfr_gadget_get: NULL argument");
@@ -3132,6 +3423,24 @@ int rs_best_response_raked(rs_table *t, const rs_tree *tree, const uint8_t *boar
     if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
     rs::br_set_rake(run, rake);
     const int rc = rs::br_execute(run, mode, out);
+    rs::br_free(run);
+    return rc;
+}
+
+int rs_best_response_hands(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
+                           size_t n_hands_p1, const uint32_t *const *cluster, int n_rounds, const rs_range_weights *weights, const rs_node_locks *locks, const rs_rake *rake,
+                           int mode, int traverser, double *value, double *mass) {
+    if (!value) return fail(RS_ERR_INVALID, "rs_best_response_hands: NULL argument");
+    if (traverser != 0 && traverser != 1) return fail(RS_ERR_INVALID, "rs_best_response_hands: traverser is 0 or 1");
+    const bool sorted = (mode & RS_BR_SORTED) != 0;
+    mode &= ~RS_BR_SORTED;
+    if (int rc = rs::br_check_mode(mode & ~(RS_BR_REAL | RS_BR_CURRENT), (mode & RS_BR_REAL) != 0)) return rc;
+    if (int rc = rs::br_check_rake(rake)) return rc;
+    if (int rc = rs::br_check_locks(locks, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1)) return rc;   // before anything is allocated
+    rs::BrRun *run = nullptr;
+    if (int rc = rs::br_prepare(t, tree, board0, n_board0, hands_p0, n_hands_p0, hands_p1, n_hands_p1, cluster, n_rounds, sorted, weights, &run, locks)) return rc;
+    rs::br_set_rake(run, rake);
+    const int rc = rs::br_hands(run, mode, traverser, value, mass);
     rs::br_free(run);
     return rc;
 }

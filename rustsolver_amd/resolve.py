@@ -78,6 +78,45 @@ def prepare(table, tree, board0, hands, clusters, node, prefix, resolver, curren
     return Prepared(sub, node_map, index_map, np.array(board, dtype=np.uint8), kept_hands, kept_clusters, kept_w, np.ascontiguousarray(alt[keep[O]]), P, r0, keep, foreign)
 
 
+def trunk_rows(trunk_table, prepared):
+    """a new F32 table of the subtree's action nodes holding the trunk's rows (regrets and strategy sums) of those nodes, through index_map: the trunk's profile as a
+    profile of the subgame, to be READ (best_response_alt, margins, a node report), not trained on -- the cells of an I32 trunk are copied as numbers, without their
+    integer scale, which the strategies read from them do not depend on"""
+    from .solver import InfosetTable
+    descs, rows = [], []
+    for t in prepared.index_map:
+        d = trunk_table.node_desc(int(t))
+        descs.append((d.n_actions, d.n_clusters, d.n_boards, d.player, d.round_idx - prepared.round0))
+        rows.append(trunk_table.download_node(int(t)))
+    sub = InfosetTable.create(descs, dtype=L.F32)
+    for k, (R, S) in enumerate(rows):
+        sub.upload_node(k, R.astype(np.float32), S.astype(np.float32))
+    return sub
+
+
+def _opponent_hands(sub_table, prepared, current):
+    O = 1 - prepared.resolver
+    return sub_table.best_response_hands(prepared.tree, prepared.board, prepared.hands[0], prepared.hands[1], prepared.clusters, O,
+                                         mode=L.BR_MAX | L.BR_REAL | L.BR_SORTED, current=current, weights=prepared.weights, deal="joint")
+
+
+def best_response_alt(sub_table, prepared, current=False):
+    """the counterfactual best-response alt: per kept hand of the opponent, value / mass of its best response in the real game (best_response_hands, BR_MAX | BR_REAL |
+    BR_SORTED) against sub_table's profile on the subgame's weights; 0.0 where the mass is 0.  With sub_table = trunk_rows(...) this is the alternative value both
+    re-solving papers assume; prepared.alt is the value under the trunk profile itself."""
+    value, mass = _opponent_hands(sub_table, prepared, current)
+    return np.where(mass > 0, value / np.where(mass > 0, mass, 1.0), 0.0)
+
+
+def margins(sub_table, prepared, alt=None, current=False):
+    """the check of a re-solve: alt - value / mass per kept hand of the opponent, value / mass its best-response value against sub_table's profile (as best_response_alt);
+    a re-solve is safe for a hand whose margin is >= 0.  alt=None: prepared.alt.  NaN where the mass is 0."""
+    alt = prepared.alt if alt is None else np.asarray(alt, dtype=np.float64).reshape(-1)
+    value, mass = _opponent_hands(sub_table, prepared, current)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(mass > 0, alt - value / np.where(mass > 0, mass, 1.0), np.nan)
+
+
 def graft(sub_table, trunk_table, prepared, player):
     """copies the player's re-solved rows (regrets and strategy sums) of the subtree's nodes back into the trunk table, for the cluster ids that occur under the prefix"""
     todo = []

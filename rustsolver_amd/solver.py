@@ -518,6 +518,31 @@ class InfosetTable:
                                               _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
         return _restore_columns(_report_blocks(tree, n_hands, ids, offsets, out), kept[traverser])
 
+    def best_response_hands(self, tree, board0, hands0, hands1, clusters, traverser, mode=L.BR_MAX | L.BR_REAL, current=False, weights=None, deal="sequential", locks=None,
+                            rake=None):
+        """per-hand root values of one traverser's best-response walk (rs_best_response_hands) -> (value, mass), float64 [hands of the traverser]: the root's value row
+        and the root's mass row (the opponent range the hand faces) summed over the run-outs.  Every mode of best_response_rounds; value.sum() is its result for the
+        traverser, value / mass under BR_MAX the hand's counterfactual best-response value.  weights, deal, locks, rake: as best_response_rounds; a hand of weight 0.0
+        has 0.0 in both arrays."""
+        mode |= L.BR_CURRENT if current else 0
+        b = np.ascontiguousarray(board0, dtype=np.uint8)
+        (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
+        keep = [c for row in cl for c in row]
+        arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        if traverser not in (0, 1):
+            raise L.RsError(L.ERR_INVALID, "rs_best_response_hands: traverser is 0 or 1")
+        n_hands = len(h1) if traverser else len(h0)
+        out = np.zeros((2, n_hands), dtype=np.float64)
+        lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
+        rk, rk_alive = raked.arg(rake)
+        L.check(L.load().rs_best_response_hands(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk, mode,
+                                                int(traverser), _vp(out[0]), _vp(out[1])))
+        if kept[traverser] is None:
+            return out[0].copy(), out[1].copy()
+        full = np.zeros((2, len(kept[traverser])), dtype=np.float64)
+        full[:, kept[traverser]] = out
+        return full[0], full[1]
+
     def update_node(self, node, action_utils, reach=None, scale=100.0, mode=L.UPD_CLAMP_I64):
         """One traverser visit of every lane (cfr.rs:370-466 / :571-623).  Returns node util [lanes]."""
         a = self.node_desc(node).n_actions
@@ -1047,7 +1072,7 @@ class RangeCFR:
                                                        C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
             self._hs[rmplus] = h
             if getattr(self, "_gadget", None) is not None:      # a handle created after set_gadget starts armed, from zero rows
-                L.check(L.load().rs_range_cfr_set_gadget(h, self._gadget[0], _vp(self._gadget[1])))
+                self._arm(h, *self._gadget)
         self._last = self._hs[rmplus]
         return self._last
 
@@ -1063,9 +1088,22 @@ class RangeCFR:
         L.check(L.load().rs_range_cfr_train(self._handle(rmplus), int(iterations), _dcfr_arg(dcfr), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def set_gadget(self, resolver, alt):
+    GADGET_KINDS = {"resolve": L.GADGET_RESOLVE, "maxmargin": L.GADGET_MAXMARGIN}
+
+    @staticmethod
+    def _arm(h, resolver, alt, kind):
+        if kind == L.GADGET_RESOLVE:
+            L.check(L.load().rs_range_cfr_set_gadget(h, resolver, _vp(alt)))
+        else:
+            L.check(L.load().rs_range_cfr_set_gadget_kind(h, kind, resolver, _vp(alt)))
+
+    def set_gadget(self, resolver, alt, kind="resolve"):
         """rs_range_cfr_set_gadget: arms the re-solving gadget above the root -- player 1 - resolver chooses per hand between alt[h] (TERMINATE) and the tree (FOLLOW);
-        alt = one float64 per hand of that player as handed to the constructor (hands of weight 0 dropped with the range).  Zeroes the gadget rows of every update rule."""
+        alt = one float64 per hand of that player as handed to the constructor (hands of weight 0 dropped with the range).  Zeroes the gadget rows of every update rule.
+        kind="maxmargin" (rs_range_cfr_set_gadget_kind, RS_GADGET_MAXMARGIN): player 1 - resolver picks the HAND on which the resolver improved least instead; row 0 of
+        the gadget rows is then the hand-choice row and gadget_margins() returns alt - value / mass per hand after that player's sweep."""
+        if kind not in self.GADGET_KINDS:
+            raise ValueError("kind is one of %s" % sorted(self.GADGET_KINDS))
         keep = self._keep[1 - int(resolver)] if int(resolver) in (0, 1) else None
         alt = np.ascontiguousarray(alt, dtype=np.float64).reshape(-1)
         if keep is not None and len(alt) == len(keep):
@@ -1074,8 +1112,17 @@ class RangeCFR:
         if len(alt) != n:
             raise ValueError("one alt per hand of the opponent: %d for %d hands" % (len(alt), n))
         for h in self._hs.values():
-            L.check(L.load().rs_range_cfr_set_gadget(h, int(resolver), _vp(alt)))
-        self._gadget = (int(resolver), alt)
+            self._arm(h, int(resolver), alt, self.GADGET_KINDS[kind])
+        self._gadget = (int(resolver), alt, self.GADGET_KINDS[kind])
+
+    def gadget_margins(self, rmplus=None):
+        """rs_range_cfr_gadget_margins -> float64 [n]: alt[h] - F[h] / M[h] of the opponent's last sweep under the max-margin gadget, NaN for a hand that is never dealt
+        or faces no mass"""
+        h = self._handle(rmplus)
+        n = len((self._h0, self._h1)[1 - self._gadget[0]]) if getattr(self, "_gadget", None) is not None else 0
+        out = np.zeros(n, dtype=np.float64)
+        L.check(L.load().rs_range_cfr_gadget_margins(h, _vp(out)))
+        return out
 
     def gadget(self, rmplus=None):
         """rs_range_cfr_gadget_get -> (regrets, ssum), float32 [2][n]: row 0 TERMINATE, row 1 FOLLOW"""

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Times one full-width iteration (both traversers) of a turn-start game with and without the re-solving gadget above the root (rs_range_cfr_set_gadget).
+"""Times one full-width iteration (both traversers) of a turn-start game without a gadget above the root and with one of either kind (rs_range_cfr_set_gadget,
+rs_range_cfr_set_gadget_kind), and rs_best_response_hands against rs_best_response_raked on the same game.
 
-    python tools/time_resolve.py [rounds]             # 7h8hQc2d, HANDS (default 200) combos a side, one info set per (board, hand), one pot-size bet per street
-    rocprofv3 --kernel-trace --stats -d out -- python tools/time_resolve.py 5      # the per-kernel split profiles/resolve.md records
+    python tools/time_resolve.py [rounds] [--kind resolve|maxmargin|both]      # 7h8hQc2d, HANDS (default 200) combos a side, one info set per (board, hand), one pot-size bet per street
+    rocprofv3 --kernel-trace --stats -d out -- python tools/time_resolve.py 5      # the per-kernel split profiles/resolve.md and profiles/maxmargin.md record
 
-Prints the medians in milliseconds, the launches per sweep and the bytes the object holds, without and with the gadget.
+Prints the medians in milliseconds, the launches per sweep and the bytes the object holds; --kind both (the default) measures the two kinds in the same run.
 """
 import os
 import sys
@@ -19,7 +20,15 @@ from rustsolver_amd import abstraction as ab  # noqa: E402
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    args = sys.argv[1:]
+    kind = "both"
+    if "--kind" in args:
+        at = args.index("--kind")
+        kind = args[at + 1]
+        del args[at:at + 2]
+    if kind not in ("resolve", "maxmargin", "both"):
+        sys.exit("--kind is resolve, maxmargin or both")
+    rounds = int(args[0]) if args else 10
     n = int(os.environ.get("HANDS", "200"))
     rng = np.random.Generator(np.random.PCG64(11))
     mask = ab.card_mask("7h8hQc2d")
@@ -40,12 +49,28 @@ def main():
                 solver.iterate(p)
                 launches.append(solver.launches())
             ms.append((time.perf_counter() - t) * 1e3)
-        print("%-16s median %.3f ms per iteration (min %.3f), launches per sweep %s, %d bytes held" % (label, float(np.median(ms)), min(ms), launches[-2:], solver.nbytes))
+        print("%-24s median %.3f ms per iteration (min %.3f), launches per sweep %s, %d bytes held" % (label, float(np.median(ms)), min(ms), launches[-2:], solver.nbytes))
 
     measure("without gadget")
-    solver.set_gadget(0, rng.standard_normal(n) * 10.0)
-    measure("with gadget")
+    alt = rng.standard_normal(n) * 10.0
+    for k in ("resolve", "maxmargin"):
+        if kind in (k, "both"):
+            solver.set_gadget(0, alt, kind=k)
+            measure("with gadget, kind %s" % k)
     solver.destroy()
+
+    def timed(label, call):
+        call()                                            # the index kernels' first launches
+        ms = []
+        for _ in range(rounds):
+            t = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t) * 1e3)
+        print("%-44s median %.3f ms per call (min %.3f)" % (label, float(np.median(ms)), min(ms)))
+
+    mode = L.BR_MAX | L.BR_REAL | L.BR_SORTED             # each call prepares the game, walks, and frees it: rs_best_response_raked both traversers, _hands one
+    timed("rs_best_response_raked (two traversers)", lambda: table.best_response_rounds(tree, board0, hands[0], hands[1], clusters, mode))
+    timed("rs_best_response_hands (traverser 1)", lambda: table.best_response_hands(tree, board0, hands[0], hands[1], clusters, 1, mode=mode))
 
 
 if __name__ == "__main__":
