@@ -130,17 +130,32 @@ struct CompactJob {
 };
 // best response over run-outs (rs_br.hip): what depends on the game only is prepared once, the walk runs against the table as it stands
 struct BrRun;
-int br_prepare(rs_table *t, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1, size_t n_hands_p1,
-               const uint32_t *const *cluster, int n_rounds, bool sorted, const rs_range_weights *weights /* NULL = every hand counts the same */, BrRun **prepared,
-               const rs_node_locks *locks = nullptr /* NULL or n == 0 = no node is locked; the caller has put them through br_check_locks */);
-int br_check_weights(const rs_range_weights *weights, size_t n_hands_p0, size_t n_hands_p1);   // RS_ERR_INVALID as the header lists; touches nothing
-// rs_node_locks as the header states them (NULL or n == 0: nothing to check, whatever the other arguments are); RS_ERR_INVALID; touches nothing
-int br_check_locks(const rs_node_locks *locks, const rs_tree *tree, const uint8_t *board0, int n_board0, const uint8_t *hands_p0, size_t n_hands_p0, const uint8_t *hands_p1,
-                   size_t n_hands_p1);
-// rs_rake as the header states it (NULL: nothing to check); RS_ERR_INVALID; touches nothing
-int br_check_rake(const rs_rake *rake);
-// the rake of a prepared game that has not walked yet (checked by the caller: br_check_rake); NULL, rate == 0 or cap == 0 = none
-void br_set_rake(BrRun *prepared, const rs_rake *rake);
+// the game as the entry points of rustsolver_amd.h describe it; what a call leaves out is NULL
+struct BrGame {
+    const rs_tree *tree = nullptr;
+    const uint8_t *board0 = nullptr;                   // n_board0 cards
+    int n_board0 = 0;
+    const uint8_t *hands[2] = {nullptr, nullptr};      // [n_hands[p]][2]
+    size_t n_hands[2] = {0, 0};
+    const uint32_t *const *cluster = nullptr;          // [n_rounds * 2]
+    int n_rounds = 0;
+    const rs_range_weights *weights = nullptr;         // NULL = every hand counts the same
+    const rs_node_locks *locks = nullptr;              // NULL or n == 0 = no node is locked
+    const rs_rake *rake = nullptr;                     // NULL, rate == 0 or cap == 0 = none
+};
+// the game-only half of a walk; the caller has put the game's locks through br_check_locks and its rake through br_check_rake
+int br_prepare(rs_table *t, const BrGame &game, bool sorted, BrRun **prepared);
+// ---- rs_br_game.cpp: host only, touches nothing -- the refusals as the header lists them (RS_ERR_INVALID) and the shapes they need
+size_t enumerate_runouts(const uint8_t *board0, int n_board0, std::vector<uint8_t> *out /* may be NULL */);   // the run-outs in the lanes' order, [NB][5]; returns NB
+int br_check_weights(const BrGame &game);           // game.weights over game.n_hands (NULL: nothing to check)
+int br_check_locks(const BrGame &game);             // game.locks (NULL or n == 0: nothing to check, whatever the other fields are)
+int br_check_rake(const rs_rake *rake);             // NULL: nothing to check
+int br_check_mode(int mode /* without RS_BR_SORTED, RS_BR_REAL and RS_BR_CURRENT */, bool real);
+int br_report_check_mode(int mode /* without RS_BR_SORTED */, int traverser);
+// doubles of a lock's rows / of a report's blocks (rs_node_lock_size, rs_node_report_size); 0 and rs_last_error on bad arguments
+size_t br_lock_layout(const rs_tree *tree, int n_board0, size_t n_hands, int node, size_t *prefixes /* may be NULL */);
+size_t br_report_layout(const rs_tree *tree, int n_board0, size_t n_hands, const int32_t *nodes, size_t n_nodes, uint64_t *offsets /* may be NULL */);
+// ---- rs_br.hip: the walks on a prepared game
 int br_execute(BrRun *prepared, int mode /* RS_BR_MAX (| RS_BR_REAL) / RS_BR_AVERAGE */, double *out /* [2] */);
 // one traverser's node report (rs_node_report) on the prepared game; mode without RS_BR_SORTED.  A workspace that lacks the report's rows is traded for a larger one
 int br_report(BrRun *prepared, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles);

@@ -500,35 +500,44 @@ static int trainer_game(rs_deal_trainer *tr, uint8_t (&board)[5], int &n_board0,
     return RS_OK;
 }
 
-extern "C" {
-
-int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
-    if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_best_response: NULL argument");
+// The prepared game of a showdown form (which: 0 = pair loop, 1 = rank order), made from trainer_game on first use and kept: the best response's, or (cfr) the full-width
+// solver's own with its larger workspace
+static int trainer_prepared(rs_deal_trainer *tr, int which, bool cfr, rs::BrRun **prepared) {
+    rs::BrRun *&kept = (cfr ? tr->cfr_prepared : tr->br_prepared)[which];
     uint8_t board[5];
     int n_board0 = 0;
     const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
     if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
-    const int which = (mode & RS_BR_SORTED) ? 1 : 0;
-    if (!tr->br_prepared[which])
-        if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, tr->game_weights(), &tr->br_prepared[which]))
-            return rc;
-    return rs::br_execute(tr->br_prepared[which], mode & ~RS_BR_SORTED, out);
+    if (!kept) {
+        const rs::BrGame game{tr->tree, board, n_board0, {tr->h_hands[0].data(), tr->h_hands[1].data()}, {tr->n_hands[0], tr->n_hands[1]}, ptrs, tr->n_rounds, tr->game_weights()};
+        rs::BrRun *run = nullptr;
+        if (int rc = rs::br_prepare(tr->table, game, which == 1, &run)) return rc;
+        if (cfr)
+            if (int rc = rs::br_cfr_mark(run)) {
+                rs::br_free(run);
+                return rc;
+            }
+        kept = run;
+    }
+    *prepared = kept;
+    return RS_OK;
+}
+
+extern "C" {
+
+int rs_deal_trainer_best_response(rs_deal_trainer *tr, int mode, double *out) {
+    if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_best_response: NULL argument");
+    rs::BrRun *run = nullptr;
+    if (int rc = trainer_prepared(tr, (mode & RS_BR_SORTED) ? 1 : 0, false, &run)) return rc;
+    return rs::br_execute(run, mode & ~RS_BR_SORTED, out);
 }
 
 // rs_node_report on the trainer's own game, on the prepared game and workspace rs_deal_trainer_best_response keeps for the showdown mode
 int rs_deal_trainer_node_report(rs_deal_trainer *tr, int mode, int traverser, const int32_t *nodes, size_t n_nodes, double *out, size_t out_doubles) {
     if (!tr || !out) return fail(RS_ERR_INVALID, "rs_deal_trainer_node_report: NULL argument");
-    uint8_t board[5];
-    int n_board0 = 0;
-    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
-    if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
-    const int which = (mode & RS_BR_SORTED) ? 1 : 0;
-    if (!tr->br_prepared[which])
-        if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, tr->game_weights(), &tr->br_prepared[which]))
-            return rc;
-    return rs::br_report(tr->br_prepared[which], mode & ~RS_BR_SORTED, traverser, nodes, n_nodes, out, out_doubles);
+    rs::BrRun *run = nullptr;
+    if (int rc = trainer_prepared(tr, (mode & RS_BR_SORTED) ? 1 : 0, false, &run)) return rc;
+    return rs::br_report(run, mode & ~RS_BR_SORTED, traverser, nodes, n_nodes, out, out_doubles);
 }
 
 // full-width CFR on the trainer's own game (rs_range_cfr_train): a prepared game of its own per showdown form, beside the best response's two
@@ -538,23 +547,9 @@ int rs_deal_trainer_range_cfr(rs_deal_trainer *tr, uint64_t iterations, const rs
     if (mode != 0 && mode != RS_UPD_RMPLUS) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: params->mode is 0 or RS_UPD_RMPLUS");
     if (params && (params->sorted < RS_FORM_DEFAULT || params->sorted > RS_FORM_OFF)) return fail(RS_ERR_INVALID, "rs_deal_trainer_range_cfr: params->sorted is an RS_FORM_* value");
     if (tr->params.table_dtype != RS_F32) return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_range_cfr: RS_F32 trainers only (rs_range_cfr_create)");
-    uint8_t board[5];
-    int n_board0 = 0;
-    const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
-    if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
-    const int which = (params && params->sorted == RS_FORM_OFF) ? 0 : 1;
-    if (!tr->cfr_prepared[which]) {
-        rs::BrRun *run = nullptr;
-        if (int rc = rs::br_prepare(tr->table, tr->tree, board, n_board0, tr->h_hands[0].data(), tr->n_hands[0], tr->h_hands[1].data(), tr->n_hands[1], ptrs, tr->n_rounds,
-                                    which == 1, tr->game_weights(), &run))
-            return rc;
-        if (int rc = rs::br_cfr_mark(run)) {
-            rs::br_free(run);
-            return rc;
-        }
-        tr->cfr_prepared[which] = run;
-    }
-    return rs::br_cfr_train(tr->cfr_prepared[which], tr->table, mode == RS_UPD_RMPLUS, iterations, dcfr, values);
+    rs::BrRun *run = nullptr;
+    if (int rc = trainer_prepared(tr, (params && params->sorted == RS_FORM_OFF) ? 0 : 1, true, &run)) return rc;
+    return rs::br_cfr_train(run, tr->table, mode == RS_UPD_RMPLUS, iterations, dcfr, values);
 }
 
 // what the best-response objects a trainer keeps between calls hold on the device (the game-only index of both showdown modes + the walks' workspaces), and a way to give
@@ -580,7 +575,10 @@ int rs_deal_trainer_set_weights(rs_deal_trainer *tr, const rs_range_weights *wei
     if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_weights: trainer is NULL");
     if (tr->batches > 0 || tr->staged) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_weights: attach the weights before the trainer's first batch");
-    if (int rc = rs::br_check_weights(weights, tr->n_hands[0], tr->n_hands[1])) return rc;
+    rs::BrGame ranges;
+    ranges.n_hands[0] = tr->n_hands[0], ranges.n_hands[1] = tr->n_hands[1];
+    ranges.weights = weights;
+    if (int rc = rs::br_check_weights(ranges)) return rc;
     rs_deal_weights *dw = nullptr;
     if (weights)
         if (int rc = rs_deal_weights_create(tr->table, weights->w[0], tr->n_hands[0], weights->w[1], tr->n_hands[1], weights->deal, &dw)) return rc;

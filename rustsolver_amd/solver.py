@@ -200,6 +200,27 @@ def _range_weights(w, deal):
     return C.byref(rw)
 
 
+class _GameArgs:
+    """The game as the rs_*_raked entry points take it, from the arguments of InfosetTable.best_response_rounds: normalised at construction (contiguous arrays, the hands
+    of weight 0.0 dropped; kept[p] = the mask of player p's hands that stay, or None) and turned into the leading ctypes arguments, tree .. rake, by leading().  The
+    object holds what those point at: it outlives the call."""
+
+    def __init__(self, tree, board0, hands0, hands1, clusters, weights, deal, locks, rake):
+        self.tree, self.deal, self.locks, self.rake = tree, deal, locks, rake
+        self.b = np.ascontiguousarray(board0, dtype=np.uint8)
+        self.hands, cl, self.w, self.kept = drop_zero_weights((hands0, hands1), clusters, weights)
+        self.cl = [c for row in cl for c in row]
+        self.n_hands = (len(self.hands[0]), len(self.hands[1]))
+
+    def leading(self):
+        arr = (C.c_void_p * len(self.cl))(*[k.ctypes.data for k in self.cl])
+        lk, lk_alive = node_locks.arg(self.tree, len(self.b), self.n_hands, node_locks.drop_columns(self.tree, self.locks, self.kept))   # (the library copies the rows)
+        rk, rk_alive = raked.arg(self.rake)
+        self._alive = (arr, lk_alive, rk_alive)
+        return (self.tree._h, _vp(self.b), len(self.b), _vp(self.hands[0]), self.n_hands[0], _vp(self.hands[1]), self.n_hands[1], arr, len(self.cl) // 2,
+                _range_weights(self.w, self.deal), lk, rk)
+
+
 def _restore_columns(res, keep):
     """a node report's rows with all-0.0 columns for the hands drop_zero_weights took out of the traverser's range"""
     if keep is None or keep.all():
@@ -485,15 +506,9 @@ class InfosetTable:
         rake = (rate, cap): raked pots (rs_best_response_raked, rustsolver_amd.rake, which states the units); the game is then general-sum -- under BR_AVERAGE
         -(out[0] + out[1]) is the rake paid per deal, and a profile's exploitability is rake.exploitability(max_values, avg_values)"""
         mode |= L.BR_CURRENT if current else 0
-        b = np.ascontiguousarray(board0, dtype=np.uint8)
-        (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
-        keep = [c for row in cl for c in row]
-        arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        g = _GameArgs(tree, board0, hands0, hands1, clusters, weights, deal, locks, rake)
         out = np.zeros(2, dtype=np.float64)
-        lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
-        rk, rk_alive = raked.arg(rake)
-        L.check(L.load().rs_best_response_raked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk, mode,
-                                                out.ctypes.data_as(C.POINTER(C.c_double))))
+        L.check(L.load().rs_best_response_raked(self._h, *g.leading(), mode, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def node_report(self, tree, board0, hands0, hands1, clusters, traverser, nodes, current=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None,
@@ -504,19 +519,13 @@ class InfosetTable:
         given that the hand is there), own the traverser's own probability of getting there.  weights, deal: as best_response_rounds (rs_node_report_weighted); a hand of
         weight 0.0 has 0.0 in every row.  locks: as best_response_rounds (rs_node_report_locked); a locked node reports its value by the lock.
         rake: as best_response_rounds (rs_node_report_raked); the tree's terminals are raked, the mass rows are not"""
-        b = np.ascontiguousarray(board0, dtype=np.uint8)
-        (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
-        keep = [c for row in cl for c in row]
-        arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        g = _GameArgs(tree, board0, hands0, hands1, clusters, weights, deal, locks, rake)
         if traverser not in (0, 1):
             raise L.RsError(L.ERR_INVALID, "rs_node_report: traverser is 0 or 1")
-        n_hands = len(h1) if traverser else len(h0)
-        ids, offsets, out = _report_request(tree, len(b), n_hands, nodes)
-        lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
-        rk, rk_alive = raked.arg(rake)
-        L.check(L.load().rs_node_report_raked(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk,
-                                              _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
-        return _restore_columns(_report_blocks(tree, n_hands, ids, offsets, out), kept[traverser])
+        n_hands = g.n_hands[traverser]
+        ids, offsets, out = _report_request(tree, len(g.b), n_hands, nodes)
+        L.check(L.load().rs_node_report_raked(self._h, *g.leading(), _report_mode(current, sorted_showdowns), int(traverser), _vp(ids), len(ids), _vp(out), len(out)))
+        return _restore_columns(_report_blocks(tree, n_hands, ids, offsets, out), g.kept[traverser])
 
     def best_response_hands(self, tree, board0, hands0, hands1, clusters, traverser, mode=L.BR_MAX | L.BR_REAL, current=False, weights=None, deal="sequential", locks=None,
                             rake=None):
@@ -525,22 +534,16 @@ class InfosetTable:
         traverser, value / mass under BR_MAX the hand's counterfactual best-response value.  weights, deal, locks, rake: as best_response_rounds; a hand of weight 0.0
         has 0.0 in both arrays."""
         mode |= L.BR_CURRENT if current else 0
-        b = np.ascontiguousarray(board0, dtype=np.uint8)
-        (h0, h1), cl, w, kept = drop_zero_weights((hands0, hands1), clusters, weights)
-        keep = [c for row in cl for c in row]
-        arr = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        g = _GameArgs(tree, board0, hands0, hands1, clusters, weights, deal, locks, rake)
         if traverser not in (0, 1):
             raise L.RsError(L.ERR_INVALID, "rs_best_response_hands: traverser is 0 or 1")
-        n_hands = len(h1) if traverser else len(h0)
-        out = np.zeros((2, n_hands), dtype=np.float64)
-        lk, lk_alive = node_locks.arg(tree, len(b), (len(h0), len(h1)), node_locks.drop_columns(tree, locks, kept))
-        rk, rk_alive = raked.arg(rake)
-        L.check(L.load().rs_best_response_hands(self._h, tree._h, _vp(b), len(b), _vp(h0), len(h0), _vp(h1), len(h1), arr, len(clusters), _range_weights(w, deal), lk, rk, mode,
-                                                int(traverser), _vp(out[0]), _vp(out[1])))
-        if kept[traverser] is None:
+        out = np.zeros((2, g.n_hands[traverser]), dtype=np.float64)
+        L.check(L.load().rs_best_response_hands(self._h, *g.leading(), mode, int(traverser), _vp(out[0]), _vp(out[1])))
+        kept = g.kept[traverser]
+        if kept is None:
             return out[0].copy(), out[1].copy()
-        full = np.zeros((2, len(kept[traverser])), dtype=np.float64)
-        full[:, kept[traverser]] = out
+        full = np.zeros((2, len(kept)), dtype=np.float64)
+        full[:, kept] = out
         return full[0], full[1]
 
     def update_node(self, node, action_utils, reach=None, scale=100.0, mode=L.UPD_CLAMP_I64):
@@ -1051,25 +1054,16 @@ class RangeCFR:
 
     def __init__(self, table, tree, board0, hands0, hands1, clusters, rmplus=False, sorted_showdowns=True, weights=None, deal="sequential", locks=None, rake=None):
         self.table, self.tree = table, tree
-        self._rake = rake
-        self._b = np.ascontiguousarray(board0, dtype=np.uint8)
-        (self._h0, self._h1), cl, self._w, self._keep = drop_zero_weights((hands0, hands1), clusters, weights)   # weights, deal: as InfosetTable.best_response_rounds
-        self._locks = node_locks.drop_columns(tree, locks, self._keep)
-        self._cl = [c for row in cl for c in row]
-        self._deal = deal
+        self._game = _GameArgs(tree, board0, hands0, hands1, clusters, weights, deal, locks, rake)   # weights, deal: as InfosetTable.best_response_rounds
+        (self._h0, self._h1), self._keep = self._game.hands, self._game.kept
         self._sorted, self._rmplus, self._hs = bool(sorted_showdowns), bool(rmplus), {}
         self._handle(self._rmplus)
 
     def _handle(self, rmplus):
         rmplus = self._rmplus if rmplus is None else bool(rmplus)
         if rmplus not in self._hs:
-            arr = (C.c_void_p * len(self._cl))(*[k.ctypes.data for k in self._cl])
             h = C.c_void_p()
-            lk, lk_alive = node_locks.arg(self.tree, len(self._b), (len(self._h0), len(self._h1)), self._locks)   # (the library copies the rows)
-            rk, rk_alive = raked.arg(self._rake)
-            L.check(L.load().rs_range_cfr_create_raked(self.table._h, self.tree._h, _vp(self._b), len(self._b), _vp(self._h0), len(self._h0), _vp(self._h1), len(self._h1),
-                                                       arr, len(self._cl) // 2, _range_weights(self._w, self._deal), lk, rk,
-                                                       C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
+            L.check(L.load().rs_range_cfr_create_raked(self.table._h, *self._game.leading(), C.byref(_range_cfr_params(rmplus, self._sorted)), C.byref(h)))
             self._hs[rmplus] = h
             if getattr(self, "_gadget", None) is not None:      # a handle created after set_gadget starts armed, from zero rows
                 self._arm(h, *self._gadget)

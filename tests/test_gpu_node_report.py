@@ -6,6 +6,7 @@ workgroup ends inside a row, last-round form), a turn game of 48 run-outs and 9 
 (mass 0, all-zero pairs), and a flop-start game of 6 x 5 hands where the fold lengths 2 352 / 48 / 1 meet in one call.  Then: the same bits from the level plan and the
 depth-first walk, from a call repeated and from a subset of the nodes; no side effects on the table or on the calls that share its walk; i32 and binary16 tables and the
 trainer's form on the trainers of test_gpu_br_pinned; refusals that leave the output buffer and the table alone."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,7 @@ import np_node_report as nnr
 import rustsolver_amd as rs
 from oracle import np_br as nbr
 from rustsolver_amd import _lib as L
+from rustsolver_amd import abstraction as ab
 from test_gpu_br_pinned import depth_first
 from test_gpu_range_cfr import SLICES, Device, same_tables, trainer_game
 from test_node_report_cpu import CASES, close, report_case, restated, rows_of, setup
@@ -220,4 +222,41 @@ def test_refused_calls_leave_the_buffer_and_the_table_alone():
         assert lib.rs_deal_trainer_node_report(tr._h, mode, 0, vp(n), len(n), vp(buf), len(buf)) == L.ERR_INVALID
         assert (buf == 7.0).all()
     assert lib.rs_deal_trainer_node_report(tr._h, L.BR_AVERAGE, 0, vp(n), len(n), vp(buf), len(buf) - 1) == L.ERR_INVALID and (buf == 7.0).all()
+    tr.destroy()
+
+
+@pytest.mark.parametrize("order", ["level plan", "depth first"])
+def test_a_kept_game_keeps_nothing_of_a_finished_or_refused_report(order):
+    """One DealTrainer keeps its prepared game between calls: a best response, a report of two nodes, a report that the library refuses on that kept game (a node id
+    out of range) and the best response again -- the same bits and the same launch count as the first.  The 40-node river tree, seven and six hands; in both tree
+    orders (the knob is read whenever a workspace is allocated: br_release() inside it)."""
+    lib = L.load()
+    mask = ab.card_mask("4d5dAs3cKs")
+    rng = np.random.Generator(np.random.PCG64(40))
+    allh = ab.random_range(mask)
+    ranges = [allh[np.sort(rng.choice(len(allh), n, replace=False))] for n in (7, 6)]
+    _, tree = rs.build_game_tree(rs.default_flop())
+    assert tree.n_nodes == 40
+    tr = rs.DealTrainer(tree, [ab.CardAbstraction.init(ranges, mask, 2, None)], ranges, mask, 1 << 12, seed=9, discount_interval=0)
+    tr.train(2)
+    tr.status()
+    ids = [i for i, nd in enumerate(tree.nodes) if nd.kind == L.NODE_ACTION]
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    with depth_first() if order == "depth first" else contextlib.nullcontext():
+        tr.br_release()
+        first = tr.best_response(L.BR_MAX | L.BR_SORTED)
+        launches = tr.br_launches()
+        assert (launches == -1) == (order == "depth first") and launches != 0
+        two = tr.node_report(0, ids[:2])
+        assert sorted(two) == ids[:2]
+        bad, buf = np.asarray([tree.n_nodes], dtype=np.int32), np.full(64, 7.0)
+        with pytest.raises(rs.RsError):                              # past the Python layer's own check of the request: the kept game's br_report refuses
+            L.check(lib.rs_deal_trainer_node_report(tr._h, L.BR_AVERAGE | L.BR_SORTED, 0, vp(bad), len(bad), vp(buf), len(buf)))
+        assert (buf == 7.0).all()
+        with pytest.raises(rs.RsError):
+            tr.node_report(0, [tree.n_nodes])
+        again = tr.best_response(L.BR_MAX | L.BR_SORTED)
+        assert again.tobytes() == first.tobytes() and np.isfinite(first).all()
+        assert tr.br_launches() == launches
+        assert same_reports(tr.node_report(0, ids[:2]), two)
     tr.destroy()
