@@ -62,7 +62,9 @@ extern "C" {
                                  still 6: weighted dealing (rs_deal_weights_*, rs_deals_sample_weighted, rs_deal_trainer_set_weights) -- additions only: rs_deals_sample and a
                                  trainer without weights launch the kernel they launched and deal the bits they dealt;
                                  still 6: the max-margin gadget and per-hand best-response values (rs_range_cfr_set_gadget_kind, rs_range_cfr_gadget_margins,
-                                 rs_best_response_hands) -- additions only: rs_range_cfr_set_gadget and every walk without them launch what they launched */
+                                 rs_best_response_hands) -- additions only: rs_range_cfr_set_gadget and every walk without them launch what they launched;
+                                 still 6: rake on the deal path (rs_solver_create_deals_raked, rs_deal_trainer_set_rake) -- additions only: a deal solver and a trainer without
+                                 rake generate the kernel sources they generated and return the bits they returned */
 #define RS_MAX_ACTIONS 8
 #define RS_MAX_ROUNDS 3
 #define RS_MAX_SIZES 4
@@ -500,7 +502,8 @@ int rs_range_cfr_create_locked(rs_table *table, const rs_tree *tree, const uint8
  * Checked before anything is allocated or the table is settled -- RS_ERR_INVALID, outputs and table left alone: rate not finite, < 0 or > 1; cap NaN or < 0; a non-zero
  * reserved.  rake == NULL, rate == 0 and cap == 0 are the _locked call in every respect: the same bits, the same launches, the same rs_range_cfr_bytes.
  * rs_range_cfr_set_gadget on an object created with rake returns RS_ERR_UNSUPPORTED (the TERMINATE branch pays the resolver minus the opponent's alternative: a zero-sum
- * construction).  The rs_deal_trainer_* forms, the sampled trainer's leaves (rs_leaf_desc) and the single-round rs_best_response stay unraked.
+ * construction).  The sampled trainer takes the same rake through rs_solver_create_deals_raked / rs_deal_trainer_set_rake (below); the lane solvers (rs_solver_create),
+ * rs_deal_trainer_calc_br and the single-round rs_best_response stay unraked.
  * rs_rake_payoffs: host only; out = {win, tie, lose} of `player` at terminal `node` -- an uncontested terminal fills all three with the player's one payoff; rake == NULL
  * gives {pot, 0, -pot} (uncontested: +-pot); a node that is no terminal, a bad player or a bad rake: RS_ERR_INVALID, out untouched. */
 typedef struct rs_rake { double rate; double cap; int32_t reserved[2]; } rs_rake;
@@ -643,6 +646,15 @@ typedef struct rs_deal_batch {
 } rs_deal_batch;
 int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
                            const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out);
+/* The same with raked pots (rs_rake above): an RS_LEAF_SIGN leaf pays the traverser (float)(pot - r) where it wins, (float)(-0.5 r) on a tie and (float)(-pot) where it
+ * loses, an uncontested terminal (float)(-pot) to the folder and (float)(pot - r) to the other player -- rs_rake_payoffs' numbers, each rounded to f32 once.  RS_LEAF_UTIL
+ * buffers are used verbatim.  Three wave-uniform constants per showdown terminal and two selects in the generated round subtrees; i32, f32 and binary16 tables, every
+ * rs_kernel_forms choice.  rake == NULL, rate == 0 and cap == 0 are rs_solver_create_deals in every respect: the same sources, the same bits, the same
+ * rs_solver_n_launches.  Checked before anything is allocated or compiled: RS_ERR_INVALID for a rake rs_best_response_raked refuses; RS_ERR_UNSUPPORTED with
+ * fuse_subtrees = 0 (the level-by-level node kernels take no rake), without hipRTC, and for a tree whose first node below the root is no action node.
+ * rs_solver_attach_comm on a raked solver returns RS_ERR_UNSUPPORTED: nothing in the sweep depends on the rank, but no multi-process test holds the combination. */
+int rs_solver_create_deals_raked(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
+                                 const rs_leaf_desc *leaves_p1, const rs_solver_params *params, const rs_rake *rake, rs_solver **out);
 void rs_solver_destroy(rs_solver *solver);
 /* one traverser sweep over every lane: `self.cfr(0, player, hand, 1f32, ..)` (cfr.rs:217) for all lanes.
  * d_root_util[pitch of the root round] (NULL = discard) receives the value returned at node 0.
@@ -869,6 +881,13 @@ int rs_deal_trainer_set_dcfr(rs_deal_trainer *trainer, const rs_dcfr_params *par
  * set the same weights deal the union batch of one GPU.  rs_deal_trainer_best_response, _node_report and _range_cfr prepare their game with weights (double)q and the
  * same `deal`; the prepared games kept from earlier calls are dropped here. */
 int rs_deal_trainer_set_weights(rs_deal_trainer *trainer, const rs_range_weights *weights);
+/* Raked pots in the trainer's sweeps (rs_solver_create_deals_raked).  Only before the first batch is dealt: RS_ERR_INVALID once a batch has been dealt or staged, and for a
+ * rake rs_best_response_raked refuses.  NULL (or rate == 0, cap == 0): unraked.  The trainer's solver is built again with the rake -- rs_deal_trainer_solver returns another
+ * object afterwards; a refused call leaves the trainer as it was (RS_ERR_UNSUPPORTED: a solver with fuse_subtrees = 0, or a trainer with a communicator;
+ * rs_deal_trainer_attach_comm on a raked trainer returns the same).  rs_deal_trainer_best_response, _node_report and _range_cfr prepare their game with the same rake, so the
+ * trainer measures the general-sum game it trains; the prepared games kept from earlier calls are dropped here.  Weights and rake compose, in either order.
+ * rs_deal_trainer_calc_br and the calc_br at the ticks stay unraked. */
+int rs_deal_trainer_set_rake(rs_deal_trainer *trainer, const rs_rake *rake);
 int rs_deal_trainer_last_br(const rs_deal_trainer *trainer, float *out /*[2]*/, uint64_t *iterations);
 int rs_deal_trainer_calc_br(rs_deal_trainer *trainer, float *out /*[2]*/);
 int rs_deal_trainer_best_response(rs_deal_trainer *trainer, int mode, double *out /*[2]*/);

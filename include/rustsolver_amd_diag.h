@@ -55,6 +55,10 @@ int rs_jit_check_tree(const rs_tree *tree, int dtype, int mode, int opp_mode, in
 /* the same for deal batches (rs_solver_create_deals): the kernels of every round subtree -- reach-down half and table-updating walk, dense and
  * over a live-deal list, with and without LDS tiles */
 int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_kernels);
+/* ... in their raked forms (rs_solver_create_deals_raked): every kernel of the call above with three-valued sign leaves.  RS_ERR_INVALID for a rake
+ * rs_best_response_raked refuses; RS_ERR_MISMATCH if generating the raked forms moves the unraked sources of the same inputs, or if a rake that is none (NULL,
+ * rate == 0, cap == 0) gives anything but them */
+int rs_jit_check_tree_deals_raked(const rs_tree *tree, int mode, int opp_mode, const rs_rake *rake, int *n_kernels);
 /* the pair kernel (rs_kernel_forms.pair_sweeps: both traversers of a lane sweep in one walk per lane) of every topmost chance-free subtree, generated and compiled the same way */
 int rs_jit_check_pair(const rs_tree *tree, int dtype, int mode, int opp_mode, int *n_kernels);
 

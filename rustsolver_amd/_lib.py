@@ -184,6 +184,8 @@ SYMBOLS = {
     "rs_solver_create": (C.c_int, [_P, _P, C.POINTER(LeafDesc), C.POINTER(LeafDesc), C.POINTER(SolverParams), _PP]),
     "rs_solver_create_deals": (C.c_int, [_P, _P, C.POINTER(DealBatch), C.POINTER(LeafDesc), C.POINTER(LeafDesc),
                                         C.POINTER(SolverParams), _PP]),
+    "rs_solver_create_deals_raked": (C.c_int, [_P, _P, C.POINTER(DealBatch), C.POINTER(LeafDesc), C.POINTER(LeafDesc),
+                                              C.POINTER(SolverParams), C.POINTER(Rake), _PP]),
     "rs_solver_destroy": (None, [_P]),
     "rs_iterate": (C.c_int, [_P, C.c_int, _P]),
     "rs_train": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64]),
@@ -210,6 +212,7 @@ SYMBOLS = {
     "rs_jit_available": (C.c_int, []),
     "rs_jit_check_tree": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rs_jit_check_tree_deals": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "rs_jit_check_tree_deals_raked": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(Rake), C.POINTER(C.c_int)]),
     "rs_jit_check_pair": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rs_cluster_file_read": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]),
     "rs_cluster_file_write": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_size_t]),
@@ -245,6 +248,7 @@ SYMBOLS = {
     "rs_deal_weights_quanta": (C.c_int, [_P, C.c_int, _P]),
     "rs_deals_sample_weighted": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
     "rs_deal_trainer_set_weights": (C.c_int, [_P, C.POINTER(RangeWeights)]),
+    "rs_deal_trainer_set_rake": (C.c_int, [_P, C.POINTER(Rake)]),
     "rs_deal_trainer_create": (C.c_int, [_P, _PP, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(DealTrainerParams), C.c_int, _PP]),
     "rs_deal_trainer_destroy": (None, [_P]),
     "rs_deal_trainer_table": (C.c_void_p, [_P]),

@@ -28,15 +28,23 @@ def _stale(target, deps):
 
 
 def _embed_device_source():
-    """rs_device.hpp as a C++ raw string literal (rs_device_src.inc) for the hipRTC kernels of rs_jit.cpp"""
+    """rs_device.hpp as C++ raw string literals for the hipRTC kernels of rs_jit.cpp: rs_device_src.inc, the prelude of every kernel, without the lines from
+    RS_RAKE_BEGIN to RS_RAKE_END, and rs_device_rake_src.inc, those lines, which only the kernels of a raked deal walk get (behind the prelude)"""
     src = os.path.join(CSRC, "rs_device.hpp")
     inc = os.path.join(HERE, "_build", "rs_device_src.inc")
     text = open(src).read().replace("#pragma once\n", "")
     assert ')RSDEV"' not in text
-    body = 'R"RSDEV(' + text + ')RSDEV"\n'
-    if not os.path.exists(inc) or open(inc).read() != body:
-        with open(inc, "w") as f:
-            f.write(body)
+    lines = text.splitlines(keepends=True)
+    first = [i for i, l in enumerate(lines) if l.startswith("// RS_RAKE_BEGIN")]
+    last = [i for i, l in enumerate(lines) if l.startswith("// RS_RAKE_END")]
+    assert len(first) == 1 and len(last) == 1 and first[0] < last[0]
+    parts = {inc: "".join(lines[:first[0]] + lines[last[0] + 1:]),
+             os.path.join(HERE, "_build", "rs_device_rake_src.inc"): "".join(lines[first[0]:last[0] + 1])}
+    for path, part in parts.items():
+        body = 'R"RSDEV(' + part + ')RSDEV"\n'
+        if not os.path.exists(path) or open(path).read() != body:
+            with open(path, "w") as f:
+                f.write(body)
     return inc
 
 

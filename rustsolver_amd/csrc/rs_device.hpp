@@ -161,6 +161,18 @@ __device__ __forceinline__ void sign_to_util(float (&x)[kVecD], bool p1, float p
         x[j] = (s == 0.0f) ? 0.0f : (wins ? pot : -pot);
     }
 }
+// RS_RAKE_BEGIN -- up to RS_RAKE_END: embedded behind the prelude of the generated kernels of a RAKED deal walk only (build.py cuts it out of the text every other kernel gets,
+// whose sources and cache keys must not move)
+// ... of a raked pot (rs_rake): what the traverser gets when it wins, ties, loses -- three wave-uniform numbers, two selects
+__device__ __forceinline__ void sign_to_util3(float (&x)[kVecD], bool p1, float win, float tie, float lose) {
+#pragma unroll
+    for (int j = 0; j < kVecD; j++) {
+        const float s = x[j];
+        const bool wins = p1 ? (s < 0.0f) : (s > 0.0f);
+        x[j] = (s == 0.0f) ? tie : (wins ? win : lose);
+    }
+}
+// RS_RAKE_END
 
 // ---- deal batches: get-infoset addressing through per-lane cluster ids (cfr.rs:361-375) -------------------------
 // A lane is a deal; idx[j] is the dense cluster id get_cluster() returned for the acting player on this round.

@@ -382,6 +382,7 @@ struct JitSubtree {
     std::vector<int> node_ids;     // tree node id of every action node, in the order the kernel indexes reg[] / ssm[]
     std::vector<int> leaf_terms;   // one terminal id per distinct leaf buffer, in the order of leaf[]
     std::vector<int> const_terms;  // terminal ids in the order of cval[]
+    std::vector<int> const_pay;    // ... and which number of rs_rake_payoffs the entry holds (0 win, 1 tie, 2 lose): 0 everywhere but at the sign leaves of a raked deal walk
     int max_actions = 0;
     size_t off_reg = 0, off_ssm = 0, off_leaf = 0, off_reach = 0, off_out = 0, off_seed = 0, off_cval = 0, off_nidx = 0,
            off_reach_const = 0, off_scale = 0, off_n_vec = 0, off_pitch = 0, off_row_stride = 0, off_tile_shift = 0, args_size = 0;

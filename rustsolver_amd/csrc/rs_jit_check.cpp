@@ -76,9 +76,8 @@ int rs_jit_check_tree(const rs_tree *tree, int dtype, int mode, int opp_mode, in
     return RS_OK;
 }
 // the same for deal batches: every round subtree (cut at the chance nodes) in the forms rs_solver_create_deals can pick -- the DOWN half and the
-// table-updating walk, each dense and over a live-deal list, the walk with and without LDS tiles
-int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_kernels) {
-    if (!tree || tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_jit_check_tree_deals: bad tree");
+// table-updating walk, each dense and over a live-deal list, the walk with and without LDS tiles.  `raked`: the forms of rs_solver_create_deals_raked (sign leaves flagged 3)
+static void deal_sources(const rs_tree *tree, int mode, int opp_mode, bool raked, const Knobs &knobs, std::map<std::string, int> &seen) {
     const std::vector<rs_tree_node> &nodes = tree->nodes;
     const size_t n = nodes.size();
     auto resolve = [&](int c) {
@@ -93,8 +92,6 @@ int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_
             const int c = resolve(int(i));
             if (nodes[size_t(c)].kind == RS_NODE_ACTION && nodes[size_t(c)].n_children > 0) root[size_t(c)] = 1;
         }
-    std::map<std::string, int> seen;
-    const Knobs knobs = knobs_resolve(nullptr);
     const std::vector<char> sigma_all(n, 1);
     for (int p = 0; p < 2; ++p) {
         std::vector<char> has_own(n, 0);
@@ -106,7 +103,7 @@ int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_
             has_own[i] = own;
             if (nd.kind == RS_NODE_TERMINAL && nd.ttype != RS_TERM_UNCONTESTED) {
                 leaf_buf[i] = 0;
-                leaf_flags[i] = 1;
+                leaf_flags[i] = raked ? 3 : 1;
             }
         }
         for (size_t i = 0; i < n; ++i) {
@@ -205,7 +202,35 @@ int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_
             }
         }
     }
+}
+int rs_jit_check_tree_deals(const rs_tree *tree, int mode, int opp_mode, int *n_kernels) {
+    if (!tree || tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_jit_check_tree_deals: bad tree");
+    std::map<std::string, int> seen;
+    const Knobs knobs = knobs_resolve(nullptr);
+    deal_sources(tree, mode, opp_mode, false, knobs, seen);
     if (int rc = jit_compile_many(seen, knobs.dump != 0)) return rc;   // every distinct source, by helper processes side by side (rs_jit_cache.cpp)
+    if (n_kernels) *n_kernels = int(seen.size());
+    return RS_OK;
+}
+// ... in the forms of rs_solver_create_deals_raked.  The unraked sources of the same inputs are generated before and after: their text must not move, and a rake that is
+// none (NULL, rate == 0, cap == 0) must give exactly them.
+int rs_jit_check_tree_deals_raked(const rs_tree *tree, int mode, int opp_mode, const rs_rake *rake, int *n_kernels) {
+    if (!tree || tree->nodes.empty()) return fail(RS_ERR_INVALID, "rs_jit_check_tree_deals_raked: bad tree");
+    if (int rc = br_check_rake(rake)) return rc;
+    const bool raked = rake && rake->rate > 0.0 && rake->cap > 0.0;
+    std::map<std::string, int> plain, seen, again;
+    const Knobs knobs = knobs_resolve(nullptr);
+    deal_sources(tree, mode, opp_mode, false, knobs, plain);
+    deal_sources(tree, mode, opp_mode, raked, knobs, seen);
+    deal_sources(tree, mode, opp_mode, false, knobs, again);
+    if (plain != again) return fail(RS_ERR_MISMATCH, "rs_jit_check_tree_deals_raked: the unraked kernels' sources changed once the raked forms had been generated");
+    if (!raked && seen != plain) return fail(RS_ERR_MISMATCH, "rs_jit_check_tree_deals_raked: a rake that is none changed a generated source");
+    if (raked) {
+        if (seen.size() != plain.size()) return fail(RS_ERR_MISMATCH, "rs_jit_check_tree_deals_raked: the raked walk has another number of kernels than the unraked one");
+        for (const auto &kv : seen)
+            if (plain.count(kv.first)) return fail(RS_ERR_MISMATCH, "rs_jit_check_tree_deals_raked: a raked kernel has an unraked kernel's source (they must not share a cache key)");
+    }
+    if (int rc = jit_compile_many(seen, knobs.dump != 0)) return rc;
     if (n_kernels) *n_kernels = int(seen.size());
     return RS_OK;
 }

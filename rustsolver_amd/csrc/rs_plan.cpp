@@ -305,7 +305,9 @@ int PlanBuilder::build() {
                      nodes[first_root].n_children > 0;
         if (s->deal_mode && s->table->dtype != RS_I32 && !round_mode)
             return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: float tables run through the generated round subtrees only (the first node below the root must be an action node)");
-        want_lists = s->deal_mode && s->params.opp_mode == RS_OPP_SAMPLE && s->table->dtype == RS_I32;   // f32 deal sweeps walk every deal (their delta rows are per deal)
+        if (s->raked && !round_mode)
+            return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals_raked: raked pots run through the generated round subtrees only (fuse_subtrees = 1, the first node below the root an action node)");
+        want_lists = s->deal_mode &&s->params.opp_mode == RS_OPP_SAMPLE && s->table->dtype == RS_I32;   // f32 deal sweeps walk every deal (their delta rows are per deal)
         want_parts = round_mode && want_lists;
         // three streets, 4 M deals per batch: 13.49 -> 12.51 ms; 1 M: 5.98 -> 5.74; but 64 K: 2.14 -> 2.34 (latency-bound: the list adds a dependent load per entry),
         // so only batches beyond the small-batch switch (RS_JIT_SCAN_ALL = 1 / 0 forces either)
@@ -370,7 +372,7 @@ int PlanBuilder::add_jit_job(int id, bool down, const std::vector<int> &sparse_s
         auto it = leaf_ids.find(lf.d_buf);
         if (it == leaf_ids.end()) it = leaf_ids.emplace(lf.d_buf, int(leaf_ids.size())).first;
         leaf_buf[t2] = it->second;
-        leaf_flags[t2] = lf.kind == RS_LEAF_UTIL ? 0 : 1;
+        leaf_flags[t2] = lf.kind == RS_LEAF_UTIL ? 0 : (s->raked ? 3 : 1);
     }
     // deal batches: privatise the deltas of a traverser node in LDS when [2][A][table pitch] ints fit in what the device gives
     // ONE workgroup (MI355X: 160 KiB, launchable without any attribute -- probed; a 5 000-cluster node needs 121 KiB)
@@ -529,7 +531,11 @@ int PlanBuilder::add_jit_job(int id, bool down, const std::vector<int> &sparse_s
     for (size_t k = 0; k < js.const_terms.size(); ++k) {
         const rs_tree_node &tn = nodes[js.const_terms[k]];
         const float pot = float(tn.value);   // `tn.value as f32`
-        put_f32(js.off_cval + 4 * k, tn.ttype == RS_TERM_UNCONTESTED ? ((p == tn.last_to_act) ? -1.0f * pot : 1.0f * pot) : pot);
+        if (s->raked) {   // the one place the formulas live: rs_rake_payoffs, in f64; each number rounded to f32 once
+            double pay[3];
+            if (int rc = rs_rake_payoffs(&s->tree, js.const_terms[k], &s->rake, p, pay)) return rc;
+            put_f32(js.off_cval + 4 * k, float(pay[js.const_pay[k]]));
+        } else put_f32(js.off_cval + 4 * k,tn.ttype == RS_TERM_UNCONTESTED ? ((p == tn.last_to_act) ? -1.0f * pot : 1.0f * pot) : pot);
     }
     put_ptr(js.off_reach, reach[id].ptr);
     put_ptr(js.off_out, uptr(id));

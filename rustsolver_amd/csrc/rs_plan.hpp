@@ -266,6 +266,10 @@ struct rs_solver : rs::SolverDevice {
     int first_round = 0;                // betting round of the first action node: its subtree walks the whole batch and keeps its tiles unless RS_JIT_ROWS = 2
     bool deal_mode = false;             // lanes are deals (rs_solver_create_deals)
     rs_deal_batch deals{};
+    // Raked pots (rs_solver_create_deals_raked, rate > 0 and cap > 0): the generated round subtrees' sign leaves pay win / tie / lose by rs_rake_payoffs, their uncontested
+    // leaves its one number; nothing else of the sweep knows
+    bool raked = false;
+    rs_rake rake{};
     // Pair sweeps (rs_kernel_forms.pair_sweeps): lane solvers whose traverser plans are one chance-free subtree kernel each walk both traversers in ONE launch
     // (rs_jit.cpp pair kernels).  rs_iterate(s, 0) HOLDS that sweep (held, held_util); rs_iterate(s, 1) then issues the pair.  Anything else issues a held sweep as the plain
     // traverser-0 plan first (solver_settle_held: table_settle, rs_sync, rs_stream, destroy, another solver's sweep on the table).

@@ -296,22 +296,22 @@ int copy_root(rs_solver *s, int traverser, float *d_root_util) {
 extern "C" {
 
 static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
-                              const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out);
+                              const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out, const rs_rake *rake = nullptr /* deal solvers: checked, rate > 0 and cap > 0 */);
 
 int rs_solver_create(rs_table *table, const rs_tree *tree, const rs_leaf_desc *leaves_p0, const rs_leaf_desc *leaves_p1,
                      const rs_solver_params *params, rs_solver **out) {
     return solver_create_impl(table, tree, nullptr, leaves_p0, leaves_p1, params, out);
 }
 
-int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
-                           const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out) {
+static int create_deals(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
+                        const rs_leaf_desc *leaves_p1, const rs_solver_params *params, const rs_rake *rake, rs_solver **out) {
     if (!deals || deals->n_deals == 0) return fail(RS_ERR_INVALID, "rs_solver_create_deals: empty deal batch");
     if (table && table->dtype != RS_I32) {   // the float form (binary32 or binary16 tables, f32 arithmetic): dense walks, no atomics, every cell's f32 deltas added in deal order
                                              // (bit-identical to the oracle's sequential loop), ONE rounding to the table's type and the RM+ floor on the write-back
         if (!params || !params->fuse_subtrees) return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: float tables need fuse_subtrees = 1 (the generated kernels)");
         if (params->mode & RS_UPD_PRUNE) return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: RS_UPD_PRUNE needs an RS_I32 table (cfr.rs:352 compares i32 regrets)");
         if (params->chance_mode != RS_CHANCE_PASS) return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: a deal has one run-out: use RS_CHANCE_PASS (cfr.rs:306-313)");
-        return solver_create_impl(table, tree, deals, leaves_p0, leaves_p1, params, out);
+        return solver_create_impl(table, tree, deals, leaves_p0, leaves_p1, params, out, rake);
     }
     if (params && params->chance_mode != RS_CHANCE_PASS)
         return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals: a deal has one run-out: use RS_CHANCE_PASS (cfr.rs:306-313)");
@@ -324,7 +324,25 @@ int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_b
         if (e == hipSuccess) e = hipMemsetAsync(table->d_dssum, 0, bytes, table->stream);
         if (e != hipSuccess) return hip_fail(e, "rs_solver_create_deals: delta tables");
     }
-    return solver_create_impl(table, tree, deals, leaves_p0, leaves_p1, params, out);
+    return solver_create_impl(table, tree, deals, leaves_p0, leaves_p1, params, out, rake);
+}
+
+int rs_solver_create_deals(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
+                           const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out) {
+    return create_deals(table, tree, deals, leaves_p0, leaves_p1, params, nullptr, out);
+}
+
+// Raked pots on the deal path: the sign leaves of the generated round subtrees pay win / tie / lose.  No rake (NULL, rate == 0 or cap == 0) is
+// rs_solver_create_deals itself; the refusals come before anything is allocated or compiled.
+int rs_solver_create_deals_raked(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
+                                 const rs_leaf_desc *leaves_p1, const rs_solver_params *params, const rs_rake *rake, rs_solver **out) {
+    if (int rc = br_check_rake(rake)) return rc;
+    if (!rake || !(rake->rate > 0.0) || !(rake->cap > 0.0)) return create_deals(table, tree, deals, leaves_p0, leaves_p1, params, nullptr, out);
+    if (params && !params->fuse_subtrees)
+        return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals_raked: raked pots need fuse_subtrees = 1 (the generated kernels; the level-by-level node kernels take no rake)");
+    if (!jit_available()) return fail(RS_ERR_UNSUPPORTED, "rs_solver_create_deals_raked: raked pots need libhiprtc.so (the generated kernels)");
+    if (int rc_ = rs::table_settle(table, false)) return rc_;   // a held pair sweep of a lane solver on the same table first (rs_iterate)
+    return create_deals(table, tree, deals, leaves_p0, leaves_p1, params, rake, out);
 }
 
 }  // extern "C"
@@ -1125,7 +1143,7 @@ static int run_dcfr_iteration(rs_solver *s, bool pending, const float *f) {
 }
 
 static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_deal_batch *deals, const rs_leaf_desc *leaves_p0,
-                              const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out) {
+                              const rs_leaf_desc *leaves_p1, const rs_solver_params *params, rs_solver **out, const rs_rake *rake) {
     if (!table || !tree || !leaves_p0 || !leaves_p1 || !params || !out)
         return fail(RS_ERR_INVALID, "rs_solver_create: NULL argument");
     const int arith = params->mode & RS_UPD_ARITH_MASK;
@@ -1161,6 +1179,10 @@ static int solver_create_impl(rs_table *table, const rs_tree *tree, const rs_dea
     if (deals) {
         s->deal_mode = true;
         s->deals = *deals;
+        if (rake) {
+            s->raked = true;
+            s->rake = *rake;
+        }
     }
     const size_t n = tree->nodes.size();
     s->leaves[0].assign(leaves_p0, leaves_p0 + n);
@@ -1498,6 +1520,7 @@ int rs_iterate_phase(rs_solver *s, int traverser, int phase, float *d_root_util)
 int rs_solver_attach_comm(rs_solver *s, rs_comm *comm) {
     if (int rc_ = rs::table_settle(s ? s->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!s) return fail(RS_ERR_INVALID, "rs_solver_attach_comm: solver is NULL");
+    if (comm && s->raked) return fail(RS_ERR_UNSUPPORTED, "rs_solver_attach_comm: the solver is raked (raked pots under a communicator are out of scope)");
     if (comm && s->order_ahead) return fail(RS_ERR_UNSUPPORTED, "rs_solver_attach_comm: this solver's deal records are sorted ahead by its trainer (one GPU); attach the communicator through rs_deal_trainer_attach_comm before the first batch");
     if (comm && s->deal_mode && s->table && s->table->dtype == RS_I32) {   // the buffers of solver_exchange_deltas
         rs_table *t = s->table;

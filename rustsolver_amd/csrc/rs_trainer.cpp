@@ -51,6 +51,11 @@ struct rs_deal_trainer {
     std::vector<double> br_w[2];
     rs_range_weights br_weights{};
     const rs_range_weights *game_weights() const { return deal_weights ? &br_weights : nullptr; }
+    // raked pots (rs_deal_trainer_set_rake): the solver's sign leaves pay by it, and the measuring calls prepare their game with the same rake
+    bool raked = false;
+    rs_rake rake{};
+    const rs_rake *game_rake() const { return raked ? &rake : nullptr; }
+    rs_comm *comm = nullptr;       // rs_deal_trainer_attach_comm
     uint32_t world = 1, rank = 0;  // data-parallel training: this rank's share of every global batch
     // The NEXT batch is dealt (sample -> clusters -> showdown) into staging buffers on a second stream while the current one is swept -- the
     // sweep kernels leave most wave slots of a CU idle -- and swapped in with device-to-device copies.  Same deal numbers, same results.
@@ -73,6 +78,28 @@ struct rs_deal_trainer {
 };
 
 static int before_sweep(void *ctx, int p);
+
+// the trainer's deal solver over its live buffers: every showdown / all-in terminal compares the one sign row (cfr.rs:323-347), raked or not
+static int make_solver(rs_deal_trainer *tr, const rs_rake *rake, rs_solver **out) {
+    const rs_deal_trainer_params *params = &tr->params;
+    rs_deal_batch batch{};
+    batch.n_deals = params->deals_per_batch;
+    batch.d_prune = tr->d_prune;
+    for (int r = 0; r < tr->n_rounds; ++r)
+        for (int p = 0; p < 2; ++p) batch.d_cluster[r][p] = tr->d_cluster[r][p];
+    const int n = rs_tree_n_nodes(tr->tree);
+    std::vector<rs_leaf_desc> leaves(size_t(n), rs_leaf_desc{RS_LEAF_UNCONTESTED, nullptr});
+    for (int i = 0; i < n; ++i) {
+        rs_tree_node nd;
+        rs_tree_get_node(tr->tree, i, &nd);
+        if (nd.kind == RS_NODE_TERMINAL && nd.ttype != RS_TERM_UNCONTESTED) leaves[size_t(i)] = rs_leaf_desc{RS_LEAF_SIGN, tr->d_sign};
+    }
+    rs_solver_params sp = params->solver;
+    sp.chance_mode = RS_CHANCE_PASS;   // one run-out per deal: the board is dealt up front (cfr.rs:115-122, :306-313)
+    sp.deal_offset = tr->rank * params->deals_per_batch;
+    if (params->prune_threshold != UINT64_MAX) sp.mode |= RS_UPD_PRUNE;   // cfr.rs:352, :379-386, :419-441, per deal through batch.d_prune
+    return rs_solver_create_deals_raked(tr->table, tr->tree, &batch, leaves.data(), leaves.data(), &sp, rake, out);
+}
 
 extern "C" {
 
@@ -212,28 +239,13 @@ int rs_deal_trainer_create(const rs_tree *tree, rs_card_abs *const *card_abs, in
     }
     if (rc == RS_OK) rc = dalloc(tr->d_prune, pitch);
     if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_prune, 0, pitch);
-    rs_deal_batch batch{};
-    batch.n_deals = params->deals_per_batch;
-    batch.d_prune = tr->d_prune;
     for (int r = 0; rc == RS_OK && r < n_rounds; ++r)
         for (int p = 0; rc == RS_OK && p < 2; ++p) {
             rc = dalloc(tr->d_cluster[r][p], pitch);
             if (rc == RS_OK) rc = rs_dmemset(tr->table, tr->d_cluster[r][p], 0, pitch * sizeof(uint32_t));
-            batch.d_cluster[r][p] = tr->d_cluster[r][p];
         }
     if (rc == RS_OK) {
-        const int n = rs_tree_n_nodes(tr->tree);
-        std::vector<rs_leaf_desc> leaves(size_t(n), rs_leaf_desc{RS_LEAF_UNCONTESTED, nullptr});
-        for (int i = 0; i < n; ++i) {
-            rs_tree_node nd;
-            rs_tree_get_node(tr->tree, i, &nd);
-            if (nd.kind == RS_NODE_TERMINAL && nd.ttype != RS_TERM_UNCONTESTED) leaves[size_t(i)] = rs_leaf_desc{RS_LEAF_SIGN, tr->d_sign};
-        }
-        rs_solver_params sp = params->solver;
-        sp.chance_mode = RS_CHANCE_PASS;   // one run-out per deal: the board is dealt up front (cfr.rs:115-122, :306-313)
-        sp.deal_offset = tr->rank * params->deals_per_batch;
-        if (params->prune_threshold != UINT64_MAX) sp.mode |= RS_UPD_PRUNE;   // cfr.rs:352, :379-386, :419-441, per deal through batch.d_prune
-        rc = rs_solver_create_deals(tr->table, tr->tree, &batch, leaves.data(), leaves.data(), &sp, &tr->solver);
+        rc = make_solver(tr, nullptr, &tr->solver);
         if (rc == RS_OK && tr->deal_stream && tr->world == 1) tr->ahead = solver_order_ahead(tr->solver, true, before_sweep, tr);   // false: not an ordered solver
         if (rc == RS_OK && tr->deal_stream && !tr->ahead && params->prefetch != RS_FORM_ON && params->deals_per_batch <= (1u << 18)) {
             // dealt ahead from 64 K deals on BECAUSE the records can be sorted ahead with it; sweeps that are not ordered (more last-round clusters than the sort has bins: the
@@ -509,7 +521,7 @@ static int trainer_prepared(rs_deal_trainer *tr, int which, bool cfr, rs::BrRun 
     const uint32_t *ptrs[RS_MAX_ROUNDS * 2] = {};
     if (int rc = trainer_game(tr, board, n_board0, ptrs)) return rc;
     if (!kept) {
-        const rs::BrGame game{tr->tree, board, n_board0, {tr->h_hands[0].data(), tr->h_hands[1].data()}, {tr->n_hands[0], tr->n_hands[1]}, ptrs, tr->n_rounds, tr->game_weights()};
+        const rs::BrGame game{tr->tree, board, n_board0, {tr->h_hands[0].data(), tr->h_hands[1].data()}, {tr->n_hands[0], tr->n_hands[1]}, ptrs, tr->n_rounds, tr->game_weights(), nullptr, tr->game_rake()};
         rs::BrRun *run = nullptr;
         if (int rc = rs::br_prepare(tr->table, game, which == 1, &run)) return rc;
         if (cfr)
@@ -600,15 +612,43 @@ int rs_deal_trainer_set_weights(rs_deal_trainer *tr, const rs_range_weights *wei
     return RS_OK;
 }
 
+// Raked pots: only while no batch has been dealt or staged, as the weights.  The trainer's solver is built again with the rake (the table is still what rs_create_infosets
+// made), the new one before the old one goes, so that a refused rake leaves the trainer as it was.
+int rs_deal_trainer_set_rake(rs_deal_trainer *tr, const rs_rake *rake) {
+    if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
+    if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_rake: trainer is NULL");
+    if (tr->batches > 0 || tr->staged) return fail(RS_ERR_INVALID, "rs_deal_trainer_set_rake: attach the rake before the trainer's first batch");
+    if (int rc = rs::br_check_rake(rake)) return rc;
+    if (tr->comm) return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_set_rake: the trainer has a communicator (raked pots under a communicator are out of scope)");
+    const bool raked = rake && rake->rate > 0.0 && rake->cap > 0.0;
+    rs_solver *fresh = nullptr;
+    if (int rc = make_solver(tr, raked ? rake : nullptr, &fresh)) return rc;
+    if (tr->ahead) (void)solver_order_ahead(tr->solver, false, nullptr, nullptr);
+    rs_solver_destroy(tr->solver);
+    tr->solver = fresh;
+    if (tr->ahead) tr->ahead = solver_order_ahead(tr->solver, true, before_sweep, tr);
+    for (int k = 0; k < 2; ++k) {   // the prepared games were made for the pots before
+        if (tr->br_prepared[k]) rs::br_free(tr->br_prepared[k]);
+        if (tr->cfr_prepared[k]) rs::br_free(tr->cfr_prepared[k]);
+        tr->br_prepared[k] = tr->cfr_prepared[k] = nullptr;
+    }
+    tr->raked = raked;
+    tr->rake = raked ? *rake : rs_rake{};
+    return RS_OK;
+}
+
 int rs_deal_trainer_attach_comm(rs_deal_trainer *tr, rs_comm *comm) {
     if (int rc_ = rs::table_settle(tr ? tr->table : nullptr, false)) return rc_;   // a held pair sweep first (rs_iterate)
     if (!tr) return fail(RS_ERR_INVALID, "rs_deal_trainer_attach_comm: trainer is NULL");
+    if (comm && tr->raked) return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_attach_comm: the trainer is raked (raked pots under a communicator are out of scope)");
     if (comm && tr->ahead) {   // sweeps under a communicator run phase by phase and sort their records themselves
         if (!solver_order_ahead(tr->solver, false, nullptr, nullptr))
             return fail(RS_ERR_UNSUPPORTED, "rs_deal_trainer_attach_comm: attach the communicator before the trainer's first batch");
         tr->ahead = false;
     }
-    return rs_solver_attach_comm(tr->solver, comm);
+    if (int rc = rs_solver_attach_comm(tr->solver, comm)) return rc;
+    tr->comm = comm;
+    return RS_OK;
 }
 
 // train(): every batch is deals_per_batch iterations of cfr.rs:207-226 on this rank (world times as many over all ranks)

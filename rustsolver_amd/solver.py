@@ -670,10 +670,13 @@ class MCCFRTrainer:
     DISCOUNT_CAP = 20_000_000     # cfr.rs:194
 
     def __init__(self, tree, infosets, leaves, scale=10000.0, mode=L.UPD_WRAP_I32, chance_mode=L.CHANCE_ENUM,
-                 use_graph=False, leaves_p1=None, fuse_subtrees=None, opp_mode=L.OPP_FULL, sample_seed=0, deals=None, shard=None, prune_deal=None, forms=None):
+                 use_graph=False, leaves_p1=None, fuse_subtrees=None, opp_mode=L.OPP_FULL, sample_seed=0, deals=None, shard=None, prune_deal=None, forms=None, rake=None):
         """leaves: dict tree-node-id -> (LEAF_* kind, DeviceBuffer) for every showdown / all-in terminal.
         deals: None (lane model) or dict (round_idx, player) -> uint32 array of dense cluster ids, one per deal
-        (what get_cluster() returned, cfr.rs:361-365): batch-synchronous deal sweeps on the reference-shaped table."""
+        (what get_cluster() returned, cfr.rs:361-365): batch-synchronous deal sweeps on the reference-shaped table.
+        rake = (rate, cap): raked pots in a deal solver's LEAF_SIGN and uncontested leaves (rs_solver_create_deals_raked, rustsolver_amd.rake); lane solvers take none."""
+        if rake is not None and deals is None:
+            raise L.RsError(L.ERR_UNSUPPORTED, "MCCFRTrainer: rake goes with deals= (rs_solver_create_deals_raked); lane solvers are unraked")
         self.game_tree, self.infosets = tree, infosets
         self._keep = [leaves, leaves_p1]
         if fuse_subtrees is None:   # tree-specialised kernels need hipRTC at run time; the level plan does not
@@ -713,8 +716,11 @@ class MCCFRTrainer:
         h = C.c_void_p()
         if batch is None:
             L.check(L.load().rs_solver_create(infosets._h, tree._h, arrs[0], arrs[1], C.byref(p), C.byref(h)))
-        else:
+        elif rake is None:
             L.check(L.load().rs_solver_create_deals(infosets._h, tree._h, C.byref(batch), arrs[0], arrs[1], C.byref(p), C.byref(h)))
+        else:
+            rk, _alive = raked.arg(rake)
+            L.check(L.load().rs_solver_create_deals_raked(infosets._h, tree._h, C.byref(batch), arrs[0], arrs[1], C.byref(p), rk, C.byref(h)))
         self._h = h
         infosets._solvers.add(self)
         self.workspace_bytes = L.load().rs_solver_workspace_bytes(h)
@@ -842,8 +848,10 @@ class DealTrainer:
     def __init__(self, tree, card_abs, hand_ranges, board_mask, deals_per_batch, seed=0, scale=100.0, mode=L.UPD_CLAMP_I64,
                  opp_mode=L.OPP_SAMPLE, discount_interval=MCCFRTrainer.DISCOUNT_INTERVAL, discount_cap=MCCFRTrainer.DISCOUNT_CAP,
                  use_graph=False, fuse_subtrees=None, device=0, world=1, rank=0, prune_threshold=10_000_000, forms=None, prefetch=None, dtype=L.I32,
-                 weights=None, deal="sequential"):
-        """weights = (w0, w1), either None: per-hand range weights the deals are drawn with (rs_deal_trainer_set_weights; deal: "sequential" or "joint", as
+                 weights=None, deal="sequential", rake=None):
+        """rake = (rate, cap): raked pots (rs_deal_trainer_set_rake, rustsolver_amd.rake): the sweeps train the raked, general-sum game, and best_response(), node_report(),
+        train_full_width() and exploitability() measure it.
+        weights = (w0, w1), either None: per-hand range weights the deals are drawn with (rs_deal_trainer_set_weights; deal: "sequential" or "joint", as
         InfosetTable.best_response_rounds); best_response(), node_report() and train_full_width() then work on the weighted game.  A weight of exactly 0.0 raises ValueError: drop
         the hand from the range before the card abstractions are built, they are made from the same lists.
         prune_threshold: cfr.rs:190 PRUNE_THRESHOLD (None = never prune).  forms: rs_kernel_forms fields by name, as for MCCFRTrainer.  world / rank: data-parallel training on replicated tables (one process per GPU): this rank deals its share of every global
@@ -875,6 +883,15 @@ class DealTrainer:
         self.infosets = InfosetTable(C.c_void_p(L.load().rs_deal_trainer_table(h)), owned=False)
         if weights is not None or deal != "sequential":
             self.set_weights(weights, deal)
+        self._rake = None
+        if rake is not None:
+            self.set_rake(rake)
+
+    def set_rake(self, rake):
+        """rs_deal_trainer_set_rake: only before the first batch.  rake = (rate, cap), or None: unraked"""
+        rk, _alive = raked.arg(rake)
+        L.check(L.load().rs_deal_trainer_set_rake(self._h, rk))
+        self._rake = rake if rake is not None and float(rake[0]) > 0.0 and float(rake[1]) > 0.0 else None
 
     def set_weights(self, weights, deal="sequential"):
         """rs_deal_trainer_set_weights: only before the first batch.  weights=None with deal="sequential": back to unweighted dealing"""
@@ -994,7 +1011,11 @@ class DealTrainer:
     def exploitability(self, sorted_showdowns=True, real=False, current=False):
         """(BR value of player 0 + BR value of player 1) / 2 against the current average strategies, per deal, in pot units of the leaves.  sorted_showdowns: the leaves by
         rank order (RS_BR_SORTED: O(n log n) per run-out, equal to the pair loop of cfr.rs:323-347 within f64 rounding).  real: the responder plays the real game
-        (RS_BR_REAL: an info set is the board seen so far and its own two cards) instead of the abstraction -- never the smaller number, and the one to compare abstractions by"""
+        (RS_BR_REAL: an info set is the board seen so far and its own two cards) instead of the abstraction -- never the smaller number, and the one to compare abstractions by.
+        A raked trainer's game is general-sum: rake.exploitability(max, avg), from two calls"""
+        if self._rake is not None:
+            srt = L.BR_SORTED if sorted_showdowns else 0
+            return raked.exploitability(self.best_response(L.BR_MAX | srt | (L.BR_REAL if real else 0), current=current), self.best_response(L.BR_AVERAGE | srt, current=current))
         return float(self.best_response(L.BR_MAX | (L.BR_SORTED if sorted_showdowns else 0) | (L.BR_REAL if real else 0), current=current).sum() / 2.0)
 
     def _download(self, ptr, dtype, count):
@@ -1226,9 +1247,14 @@ def dcfr_factors(alpha, beta, gamma, p):
     return np.array(out[:], dtype=np.float32)
 
 
-def jit_check_tree_deals(tree, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_SAMPLE):
-    """compile (no GPU needed) every deal-batch kernel of `tree`: round subtrees, reach-down and walk, dense / listed, LDS / direct"""
+def jit_check_tree_deals(tree, mode=L.UPD_CLAMP_I64, opp_mode=L.OPP_SAMPLE, rake=None):
+    """compile (no GPU needed) every deal-batch kernel of `tree`: round subtrees, reach-down and walk, dense / listed, LDS / direct.  rake = (rate, cap): their raked forms
+    (rs_jit_check_tree_deals_raked), with the library's check that the unraked sources stay what they are"""
     n = C.c_int()
+    if rake is not None:
+        rk, _alive = raked.arg(rake)
+        L.check(L.load().rs_jit_check_tree_deals_raked(tree._h, mode, opp_mode, rk, C.byref(n)))
+        return n.value
     L.check(L.load().rs_jit_check_tree_deals(tree._h, mode, opp_mode, C.byref(n)))
     return n.value
 
